@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the NVSF render hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run builds (if stale), sets up, spins up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is
+given (`dump_outputs`) and prints the line: the contract keys only.  Everything below that the headline does not need (roofline,
+kernel breakdown, fresh batches, cpu_baseline, the oracle check, the secondary legs, the detail file) runs with --full only.
 
 N > 1 runs one rank per GPU.  Under a launcher (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`:
 RANK / LOCAL_RANK / WORLD_SIZE in the environment) this process is one of the ranks.  Without one (`python bench.py --gpus N`)
@@ -67,6 +71,11 @@ def parse():
     ap.add_argument("--no-kernel-breakdown", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the occupancy-grid (config 3) and dynamic-field (config 5) legs")
     ap.add_argument("--train-steps", type=int, default=40, help="extra leg: timed training steps reported under `train` (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: kernel breakdown + roofline, fresh batches, "
+                    "cpu_baseline + oracle check, the secondary legs, eval and train (the options above select among them), and the detail file; "
+                    "without it a run only times the headline and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step (rank 0) to "
+                    "DIR/<name>.npy, float32, at most 64 MB in all (a fixed, seeded sample of rays beyond that)")
     return ap.parse_args()
 
 
@@ -1001,6 +1010,43 @@ def rank_agreement(dist, nvsf_build):
     return dict(mine, ranks_agree=True, ranks_seen={"min": min(worlds), "max": max(worlds), "answered": len({v["rank"] for v in views})})
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6  # all .npy files of --dump-outputs together, headers included
+
+
+def dump_outputs(out, out_dir, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """Writes what one timed step returned -- the render dictionaries of the LiDAR and the camera batch, i.e. depth / image /
+    weights_sum per ray and weights / z_vals per sample -- as out_dir/<lidar|camera>_<key>.npy (the `_lidar` suffix of the keys
+    dropped), float32 (float64 stays float64).  Over `max_bytes` in all, every array of a batch keeps the same fixed, seeded,
+    sorted sample of its rays, the same fraction of each batch.  Returns {name: shape}."""
+    batches = []
+    for modality, res in zip(("lidar", "camera"), out):
+        arrays = {}
+        for key, v in res.items():
+            if not torch.is_tensor(v):
+                continue
+            a = v.detach().cpu().numpy()
+            a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+            if a.ndim >= 2 and a.shape[0] == 1:  # [1, N, ...]: the batch dimension of the reference's interface
+                a = a[0]
+            name = key[:-len("_lidar")] if key.endswith("_lidar") else key
+            arrays[f"{modality}_{name}"] = a
+        batches.append(arrays)
+    total = sum(a.nbytes for arrays in batches for a in arrays.values())
+    max_bytes -= 4096 * sum(len(arrays) for arrays in batches)  # room for the .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for k, arrays in enumerate(batches):
+        n_rays = max((a.shape[0] for a in arrays.values() if a.ndim), default=0)
+        if total > max_bytes and n_rays:
+            keep = max(1, n_rays * max_bytes // total)
+            rows = np.sort(np.random.default_rng(seed + k).choice(n_rays, keep, replace=False))
+            arrays = {name: a[rows] if a.ndim and a.shape[0] == n_rays else a for name, a in arrays.items()}
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1105,11 +1151,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     finite = bool(torch.isfinite(out[0]["image_lidar"]).all() and torch.isfinite(out[1]["image"]).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     # Second figure (not `value`): a FRESH ray batch every step with the sampler's jitter on (perturb = True), as an epoch of the
     # reference's loader delivers them -- the timed loop above re-renders one batch, which is cache-warm in the coarse levels.
     fresh = None
-    if not args.no_extra_legs or os.environ.get("NVSF_BENCH_FRESH") == "1":
+    if args.full and (not args.no_extra_legs or os.environ.get("NVSF_BENCH_FRESH") == "1"):
         n_b = 8
         batches = []
         for b in range(n_b):
@@ -1157,7 +1205,7 @@ def main():
             line["fresh_batches"] = fresh
         if same_device:
             line["invalid"] = "NVSF_BENCH_SAME_DEVICE=1: all ranks shared cuda:0 (control-flow check only)"
-        if not args.no_kernel_breakdown:
+        if args.full and not args.no_kernel_breakdown:
             rows = kernel_breakdown(model, {"lidar": (tl[0][0], tl[1][0], True), "camera": (tc[0][0], tc[1][0], False)}, T,
                                     min(max(5, args.steps), 40))
             line["kernels"] = rows
@@ -1167,7 +1215,7 @@ def main():
                                 "algorithmic": pick["per_unit"], "units_per_launch": pick["units"]}
             line["roofline"].update(pmc_traffic(pick["kernel"]))
             line["kernel_ms_sum"] = sum(r["ms"] for r in rows)
-        if args.cpu_rays > 0 and world == 1:
+        if args.full and args.cpu_rays > 0 and world == 1:
             rays = {True: (lo, ld), False: (co, cd)}
             n1 = min(args.cpu_rays, args.num_rays, args.num_rays_lidar)
             base, ref_out = cpu_baseline(model, T, rays, n1)  # one core: the scalar port as it is
@@ -1180,22 +1228,22 @@ def main():
             line["cpu_baseline"] = base
             # the cpu_baseline leg's renders double as the checker of the timed outputs (the oracle is never on the timed path)
             line["outputs_match_oracle"] = outputs_match_oracle(out, ref_out)
-        if not args.no_extra_legs and world == 1:  # secondary figures for BASELINE configs 3 and 5 (never `value`)
+        if args.full and not args.no_extra_legs and world == 1:  # secondary figures for BASELINE configs 3 and 5 (never `value`)
             line["occupancy"] = occupancy_leg(NeRFNetworkStatic, dev, args.num_rays, 10)
             line["dynamic"] = dynamic_leg(dev, args.num_rays, T, 3)
             line["reference_default_grid"] = reference_default_grid_leg(NeRFNetworkStatic, dev, args.num_rays, T, 10)
             line["raymarching"] = raymarching_leg(dev)
             line["field_ops"] = field_ops_leg(dev, args.num_rays, T)
-    if not args.no_extra_legs:
+    if args.full and not args.no_extra_legs:
         ev = eval_leg(model, dev, T, 3, dist)
         if rank == 0:
             line["eval"] = ev
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         tr = train_leg(model, tl, tc, tm, T, args.train_steps, dev, dist)
         if rank == 0:
             line["train"] = tr
     if rank == 0:
-        detail_path = write_detail(line)
+        detail_path = write_detail(line) if args.full else None
         try:
             final = compact_line(line, detail_path)
         except Exception as e:  # the figures are measured: a summary that trips over an unexpected leg shape must not lose the line

@@ -176,3 +176,53 @@ def test_two_rank_line_carries_what_a_scaling_run_is_checked_by():
 def pytest_approx(v, rel=1e-6):
     import pytest
     return pytest.approx(v, rel=rel)
+
+
+def test_plain_run_is_the_default_and_dump_is_opt_in(monkeypatch):
+    """A plain `bench.py` run times the headline only (the legs need --full); outputs are written only when asked for."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d", "--steps", "7"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "d" and a.steps == 7
+
+
+def _render_like(n, t, lidar, seed):
+    """Tensors shaped like one modality's render dictionary; every entry of ray i carries i in its integer part."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    ray = torch.arange(n, dtype=torch.float32)
+    sfx, c = ("_lidar", 2) if lidar else ("", 3)
+    frac = lambda *s: torch.rand(*s, generator=g) * 0.5
+    return {"depth" + sfx: (ray + frac(n))[None], "image" + sfx: (ray[:, None] + frac(n, c))[None],
+            "weights_sum" + sfx: ray + frac(n), "weights": ray[:, None] + frac(n, t), "z_vals": (ray[:, None] + frac(n, t)).double()}
+
+
+def test_dump_outputs_names_dtypes_and_bounded_sample(tmp_path):
+    import numpy as np
+    b = _bench()
+    out = (_render_like(96, 40, True, 1), _render_like(64, 40, False, 2))
+    shapes = b.dump_outputs(out, str(tmp_path / "all"))
+    assert sorted(shapes) == sorted(f"{m}_{k}" for m in ("lidar", "camera") for k in ("depth", "image", "weights_sum", "weights", "z_vals"))
+    for name, shape in shapes.items():
+        a = np.load(tmp_path / "all" / f"{name}.npy")
+        assert list(a.shape) == shape and a.dtype == (np.float64 if name.endswith("z_vals") else np.float32)
+        src = out[0 if name.startswith("lidar") else 1]
+        key = [k for k in src if name.endswith("_" + k.replace("_lidar", ""))][-1]
+        assert np.array_equal(a, src[key].numpy().reshape(a.shape))  # complete: below the limit nothing is sampled
+    assert shapes["lidar_image"] == [96, 2] and shapes["camera_weights"] == [64, 40]
+    # over the limit: one fixed sorted sample of rays per batch, the same rows in every array of that batch, within the limit
+    limit = 60000
+    small = b.dump_outputs(out, str(tmp_path / "a"), max_bytes=limit)
+    again = b.dump_outputs(out, str(tmp_path / "b"), max_bytes=limit)
+    assert small == again and sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) <= limit
+    for m in ("lidar", "camera"):
+        rows = {name: np.floor(np.load(tmp_path / "a" / f"{name}.npy")).reshape(small[name][0], -1) for name in small if name.startswith(m)}
+        ref = next(iter(rows.values()))[:, 0]
+        assert 0 < len(ref) < (96 if m == "lidar" else 64) and np.all(np.diff(ref) > 0)
+        for r in rows.values():
+            assert np.array_equal(r, np.repeat(ref[:, None], r.shape[1], 1))
+        for name in rows:
+            assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))

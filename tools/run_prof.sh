@@ -6,12 +6,12 @@ T=${1:-d}
 O=$R/gpurun_out/$T
 mkdir -p $O
 # 1. two-rank control-flow check on one device (numbers meaningless, tagged invalid)
-NVSF_BENCH_SAME_DEVICE=1 timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 --train-steps 2 --no-extra-legs --cpu-rays 0 > $O/bench2.log 2>&1
+NVSF_BENCH_SAME_DEVICE=1 timeout 600 python bench.py --full --gpus 2 --steps 5 --warmup 2 --train-steps 2 --no-extra-legs --cpu-rays 0 > $O/bench2.log 2>&1
 rc2=$?   # of the bench run itself (captured before the copy below replaces $?)
 cp $R/gpurun_out/bench_detail.json $O/bench2_detail.json
 echo "rc2=$rc2" >> $O/bench2.log
 # 2. default bench line
-timeout 900 python bench.py > $O/bench1.log 2>&1
+timeout 900 python bench.py --full > $O/bench1.log 2>&1
 cp $R/gpurun_out/bench_detail.json $O/bench1_detail.json   # (the profiled runs below overwrite gpurun_out/bench_detail.json)
 cd /tmp
 B="python3 $R/bench.py --cpu-rays 0 --no-kernel-breakdown --no-extra-legs --train-steps 0"
@@ -20,7 +20,7 @@ timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- $B 
 timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pf -- $B --steps 3 --warmup 1 > $O/pf.log 2>&1
 timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pw -- $B --steps 3 --warmup 1 > $O/pw.log 2>&1
 # 5b. MFMA pipe occupancy of the render kernels (SQ counters only, their own pass)
-timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU_MFMA_MOPS_F16 --output-format csv -d $O/pm -- python3 $R/bench.py --cpu-rays 0 --no-extra-legs --train-steps 0 --steps 5 --warmup 1 > $O/pm.log 2>&1
+timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU_MFMA_MOPS_F16 --output-format csv -d $O/pm -- python3 $R/bench.py --full --cpu-rays 0 --no-extra-legs --train-steps 0 --steps 5 --warmup 1 > $O/pm.log 2>&1
 # 6. kernel traces of the secondary legs
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_train -- python3 $R/tools/bench_train.py > $O/kt_train.log 2>&1
 # 6b. counters of the training step's kernels: MFMA pipe (SQ) and 64-byte atomic requests (TCC), separate passes
