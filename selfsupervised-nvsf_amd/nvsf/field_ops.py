@@ -215,9 +215,7 @@ class HashGridFn(Function):
         out = hashgrid_forward_level_major(x, table_f16, spec) if level_major else hashgrid_forward(x, cols, table_f16, spec)
         ctx.save_for_backward(x)
         ctx.spec, ctx.cols, ctx.rows_per_ray = spec, cols, rows_per_ray
-        ctx.train_ctx, ctx.table_param = train_ctx, params
-        if train_ctx is not None and isinstance(params, torch.nn.Parameter) and params.requires_grad and torch.is_grad_enabled():
-            train_ctx.expect(params)
+        announce(ctx, train_ctx, params)
         return out
 
     @staticmethod
@@ -228,8 +226,8 @@ class HashGridFn(Function):
         fine = _bin_from(ctx.spec, x.shape[0], ctx.rows_per_ray)
         if grad_out.dim() == 3 and (fine is None or _hip.hashgrid_bwd_ws_bytes(x.shape[0], ctx.spec, fine[0], fine[1]) <= 0 or x.shape[0] > _BIN_ROWS_MAX):
             grad_out = grad_out.permute(1, 0, 2).reshape(x.shape[0], -1)  # only the binned entry point reads level-major gradients
-        done = scatter_beside_backward(ctx.train_ctx, ctx.table_param, (x, grad_out), lambda view, pool: hashgrid_backward(
-            x, ctx.cols, ctx.spec, grad_out, grad_table=view.view(-1), fine_from=fine, ws_pool=pool))
+        done = scatter_to_sink(ctx, (x, grad_out), lambda views, pool: hashgrid_backward(
+            x, ctx.cols, ctx.spec, grad_out, grad_table=views[0].view(-1), fine_from=fine, ws_pool=pool))
         grad_params = None if done else hashgrid_backward(x, ctx.cols, ctx.spec, grad_out, fine_from=fine)
         return None, grad_params, None, None, None, None, None, None
 
@@ -611,13 +609,15 @@ def cast_cols_f16(src, dst):
     return dst
 
 
-# ---- table-gradient scatter beside the rest of backward -------------------------------------------------------------------------
-# The table scatter (coarse levels at the memory-side float-atomic rate, fine levels as two streaming passes: ~2 ms per config-2 batch)
-# with the vector and matrix pipes idle; the MLP backward kernels of the OTHER modality's branch are MFMA / LDS work.  DensityFn
-# therefore issues the scatter on a side stream: the main stream goes on with the next branch of backward and only the consumers
-# of the table gradient (gradient all-reduce, overflow check, optimiser) wait for it (`sync_side_streams`).
-# Only a caller that synchronises afterwards turns this on (`TrainContext.overlap` around backward, then `sync_side_streams()`:
-# nvsf.nerf.train_step.RenderTrainStep.step); everywhere else the scatter stays on the calling stream.
+# ---- table gradients into the training step's gradient sink ---------------------------------------------------------------------
+# The large tables (hash grids, K-planes texels, time slices, the flow grid) do not return their gradient to autograd inside a
+# training step: their nodes ADD it straight into the step's gradient sink (the parameter's .grad or its bucket view), under one
+# contract -- `announce` at forward, `scatter_to_sink` at backward, `TrainContext.end_pass` after each backward pass.
+# The scatter (coarse levels at the memory-side float-atomic rate, fine levels as two streaming passes: ~2 ms per config-2 batch)
+# leaves the vector and matrix pipes idle; the MLP backward kernels of the OTHER modality's branch are MFMA / LDS work.  With
+# `TrainContext.overlap` the scatters therefore run on a side stream: the main stream goes on with the next branch of backward and only
+# the consumers of the table gradients (gradient all-reduce, overflow check, optimiser) wait for them (`sync_side_streams`).
+# Only a caller that synchronises afterwards turns this on (nvsf.nerf.train_step.RenderTrainStep, around backward).
 _SIDE_STREAMS = {}  # (device) -> the stream table scatters are issued on beside backward (a device resource, shared by design)
 
 
@@ -625,11 +625,11 @@ class LocalGradSink:
     """Single-process destination of the side-stream table scatters: the parameter's own `.grad`, zero-filled on the CALLING
     (main) stream when the first scatter of a step asks for it.  Every scatter of that table then accumulates into this one
     buffer on the side stream and the autograd node returns no tensor for the table: nothing the autograd engine could clone,
-    add or read on the main stream while the side stream still writes (a table that receives more than one DensityFn.backward
-    per pass -- RenderTrainStep(ray_chunks > 1) -- would otherwise be summed by the engine without any wait on the side stream)."""
+    add or read on the main stream while the side stream still writes (a table that receives more than one scatter per pass --
+    RenderTrainStep(ray_chunks > 1) -- would otherwise be summed by the engine without any wait on the side stream)."""
 
     def __init__(self):
-        self.side_scatters = []  # (parameter, event recorded on the side stream behind its LAST scatter of the step), in issue order
+        self.side_scatters = []  # (parameter, event recorded on the side stream behind its LAST scatter of a pass), in issue order
 
     def view_for(self, p):
         if p.grad is None:
@@ -637,7 +637,7 @@ class LocalGradSink:
         return p.grad
 
     def mark_ready(self, p):
-        """Called on the stream that ran the last scatter of table `p` in this step, right behind it."""
+        """Called on the stream that ran the last scatter of table `p` in this pass, right behind it."""
         stream = torch.cuda.current_stream(p.device)
         if p.is_cuda and stream != torch.cuda.default_stream(p.device):
             ev = torch.cuda.Event()
@@ -646,91 +646,103 @@ class LocalGradSink:
 
 
 class TrainContext:
-    """What the table-scatter nodes (DensityFn / DensityRaysFn) need to know about the training step they run in -- owned by the step
-    object (RenderTrainStep.train_ctx), attached to its model (`model._train_ctx`), read by the nodes at `forward` and carried to
-    `backward` on the autograd ctx.  Nothing here is process-wide: two steps / two models in one process keep separate state.
-      sink     where table gradients are scattered: frame_shard.GradBuckets (multi-rank) or a LocalGradSink; None: the node returns
-               the gradient tensor to autograd
-      overlap  issue the scatters on the side stream beside the rest of backward; only a caller that waits for them afterwards
-               turns this on (RenderTrainStep, around backward)
-      left     scatters a table still has to receive in the running step (counted at forward): a sink may only be told that a
-               table's gradient is final -- and send its bucket to the all-reduce -- after the LAST of them."""
+    """What the table-scatter nodes need to know about the training step they run in -- owned by the step object
+    (RenderTrainStep.train_ctx), attached to its model (`model._train_ctx`), handed to the nodes at `forward` (train_context) and
+    carried to `backward` on the autograd ctx (announce).  Nothing here is process-wide: two steps / two models in one process keep
+    separate state.
+      sink      where table gradients are scattered: frame_shard.GradBuckets (multi-rank) or a LocalGradSink; None: the node returns
+                the gradient tensor to autograd
+      overlap   issue the scatters on the side stream beside the rest of backward; only a caller that waits for them afterwards
+                turns this on (RenderTrainStep, around backward)
+      left      scatters a table still has to receive in the running pass (counted at forward): a sink may only be told that a
+                table's gradient is final -- and send its bucket to the all-reduce -- after the LAST of them
+      partial   tables that received a scatter into the sink in this pass, but not their last one -> the stream it ran on
+      leftover  tables announced in the last pass that did not receive all their scatters (end_pass; expected empty)"""
 
     def __init__(self):
-        self.sink, self.overlap, self.left = None, False, None
+        self.sink, self.overlap, self.left, self.partial, self.leftover = None, False, None, {}, set()
         self.ws_pool = {}  # (device, stream) -> scratch of the binned table scatters of this step's tables
 
     def begin_step(self):
-        self.left = {}
+        self.left, self.partial = {}, {}
 
     def end_step(self):
-        self.left = None
+        self.left, self.partial = None, {}
 
     def expect(self, p):
-        if self.left is not None and p is not None:
+        if self.left is not None:
             self.left[p] = self.left.get(p, 0) + 1
 
     def done(self, p):
-        """True when this was the last outstanding scatter of table `p` in the step (always, outside a counted step)."""
+        """True when this was the last outstanding scatter of table `p` in the pass (always, outside a counted step)."""
         if self.left is None or p not in self.left:
             return True
         self.left[p] -= 1
         return self.left[p] <= 0
 
+    def end_pass(self):
+        """After a backward pass: a table announced more often than it was scattered into is marked ready behind the scatters it did
+        receive (a wait on it must not be lost); the counts start afresh for the next pass.  -> the set of such tables."""
+        if self.left is None:
+            return set()
+        self.leftover = {p for p, n in self.left.items() if n > 0}
+        for p in self.leftover:
+            if p in self.partial:
+                with torch.cuda.stream(self.partial[p]):
+                    self.sink.mark_ready(p)
+        self.left, self.partial = {}, {}
+        return self.leftover
+
 
 def train_context(module):
-    return module.__dict__.get("_train_ctx") if module is not None else None
+    """The TrainContext of the step `module` is trained by, to be passed to a node's forward -- None outside a step and when the
+    caller records no graph (inside `Function.forward` grad mode is always off, so this is decided here, at the call site)."""
+    return module.__dict__.get("_train_ctx") if module is not None and torch.is_grad_enabled() else None
 
 
-def scatter_beside_backward(tctx, param, tensors, scatter):
-    """Runs `scatter(view, scratch pool)` -- which ADDS a table gradient into `view` -- on the side stream of the training step `tctx`
-    belongs to, into the step's gradient sink (the parameter's .grad or its bucket view); the autograd node then returns no tensor
-    for the table.  Returns False (nothing done) outside such a step: the caller scatters on its own stream and returns the
-    gradient to autograd.  `tensors`: what the scatter reads (kept alive for the side stream)."""
-    if tctx is None or not tctx.overlap or tctx.sink is None or not isinstance(param, torch.nn.Parameter) or not param.is_cuda:
-        if tctx is not None and isinstance(param, torch.nn.Parameter):
-            tctx.done(param)
+def announce(ctx, train_ctx, params):
+    """Forward half of the sink contract: `params` (one tensor or several) are the tables this node will scatter into.  Keeps the
+    step's context and the distinct trainable nn.Parameters among them on `ctx` (ctx.train_ctx, ctx.tables) and counts one expected
+    scatter for each (TrainContext.expect)."""
+    tables = []
+    for p in (params if isinstance(params, (tuple, list)) else (params,)):
+        if isinstance(p, torch.nn.Parameter) and p.requires_grad and not any(p is q for q in tables):
+            tables.append(p)
+    ctx.train_ctx, ctx.tables = train_ctx, tuple(tables)
+    if train_ctx is not None:
+        for p in tables:
+            train_ctx.expect(p)
+
+
+def scatter_to_sink(ctx, tensors, scatter):
+    """Backward half of the sink contract: settles the scatters `announce` counted for this node and, when the step has a gradient
+    sink, runs `scatter(views, scratch pool)` -- which ADDS the gradient of ctx.tables[i] into views[i], the sink's buffer of that
+    table -- on the step's side stream (TrainContext.overlap) or on the calling stream, then tells the sink which tables are final
+    (mark_ready, behind their last scatter of the pass).  True: done, the node returns no tensor for its tables.  False (nothing run):
+    no sink, no table, or `scatter` None -- the node returns the gradients to autograd.  `tensors`: what the scatter reads (kept alive
+    for the side stream)."""
+    tctx, tables = ctx.train_ctx, ctx.tables
+    if tctx is None:
         return False
-    last = tctx.done(param)
-    view = tctx.sink.view_for(param)  # obtained (and, the first time, zero-filled) on the main stream
-    if view is None:
-        raise _hip.NvsfHipError("the gradient sink has no buffer for this table")
-    main, side = torch.cuda.current_stream(param.device), side_stream(param.device)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        for t in tensors:
-            t.record_stream(side)
-        scatter(view, tctx.ws_pool)
-        if last:
-            tctx.sink.mark_ready(param)
-    return True
-
-
-def scatter_beside_backward_multi(tctx, params, tensors, scatter):
-    """scatter_beside_backward for a node whose ONE scatter feeds several parameters (the time slices of the space-time grids: one
-    launch sums G[row] per coordinate pair, every slice's gradient is a multiple of it): `scatter(views, scratch pool)` adds into
-    `views[i]` = the sink's buffer of `params[i]` (distinct parameters), on the side stream.  False: nothing done (see above)."""
-    ok = (tctx is not None and tctx.overlap and tctx.sink is not None
-          and all(isinstance(p, torch.nn.Parameter) and p.is_cuda and p.dtype == torch.float32 for p in params))
-    if not ok:
-        if tctx is not None:
-            for p in params:
-                if isinstance(p, torch.nn.Parameter):
-                    tctx.done(p)
+    last = [tctx.done(p) for p in tables]
+    if scatter is None or tctx.sink is None or not tables:
         return False
-    last = [tctx.done(p) for p in params]
-    views = [tctx.sink.view_for(p) for p in params]  # obtained (and, the first time, zero-filled) on the main stream
+    views = [tctx.sink.view_for(p) for p in tables]  # obtained (and, the first time, zero-filled) on the calling stream
     if any(v is None for v in views):
-        raise _hip.NvsfHipError("the gradient sink has no buffer for one of these tables")
-    main, side = torch.cuda.current_stream(params[0].device), side_stream(params[0].device)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
+        raise _hip.NvsfHipError("the gradient sink has no buffer for this table")
+    stream = None  # the calling stream
+    if tctx.overlap and tables[0].is_cuda:
+        stream = side_stream(tables[0].device)
+        stream.wait_stream(torch.cuda.current_stream(tables[0].device))
         for t in tensors:
-            t.record_stream(side)
+            t.record_stream(stream)
+    with torch.cuda.stream(stream):
         scatter(views, tctx.ws_pool)
-        for p, is_last in zip(params, last):
+        for p, is_last in zip(tables, last):
             if is_last:
                 tctx.sink.mark_ready(p)
+            else:
+                tctx.partial[p] = stream
     return True
 
 
@@ -764,12 +776,9 @@ class DensityFn(Function):
         sigma = torch.empty(h.shape[0], dtype=torch.float32, device=h.device)
         _hip.call("nvsf_exp_col", _hip.ptr(h), h.stride(0), 0, h.shape[0], _hip.ptr(sigma))
         ctx.save_for_backward(x01, feat, sigma, mlp_w16)
-        ctx.grid_spec, ctx.mlp_spec, ctx.clamp = grid_spec, mlp_spec, (float(sigma_lo), float(sigma_hi))
-        ctx.table_param = table_params
-        ctx.rows_per_ray, ctx.train_ctx = rows_per_ray, train_ctx
+        ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray = grid_spec, mlp_spec, (float(sigma_lo), float(sigma_hi)), rows_per_ray
         ctx.need_table, ctx.need_w = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
-        if train_ctx is not None and table_params is not None and table_params.requires_grad and torch.is_grad_enabled():
-            train_ctx.expect(table_params)
+        announce(ctx, train_ctx, table_params)
         return sigma, h[:, 1:mlp_spec.n_out]
 
     @staticmethod
@@ -809,36 +818,10 @@ def _density_backward(ctx, g_sigma, g_geo):
     grad_feat, grad_w = mlp_backward(feat, mlp_w16, spec, None if grad_h is None else grad_h[:, :spec.n_out], need_grad_x=need_table,
                                      grad_x_blocks=blocks, density_grad=parts)
     grad_table = None
-    if need_table:
-        tctx = getattr(ctx, "train_ctx", None)
-        last = tctx.done(ctx.table_param) if tctx is not None else True
-        sink = tctx.sink if tctx is not None else None
-        pool = tctx.ws_pool if tctx is not None else None
-        if not (tctx is not None and tctx.overlap and x01.is_cuda):
-            view = sink.view_for(ctx.table_param) if sink is not None else None
-            if view is not None:
-                hashgrid_backward(x01, (0, 1, 2), ctx.grid_spec, grad_feat, grad_table=view.view(-1), fine_from=fine, ws_pool=pool)
-                if last:
-                    sink.mark_ready(ctx.table_param)
-            else:
-                grad_table = hashgrid_backward(x01, (0, 1, 2), ctx.grid_spec, grad_feat, fine_from=fine, ws_pool=pool)
-        else:
-            # Side stream.  The destination is ONE buffer per table and step, obtained (and, the first time, zero-filled) on the
-            # main stream BEFORE the side stream is made to wait for it: a bucket view (multi-rank) or the parameter's .grad
-            # (LocalGradSink).  The node returns no tensor for the table, so the autograd engine never touches the buffer.
-            if sink is None:
-                raise _hip.NvsfHipError("TrainContext.overlap needs a gradient sink (RenderTrainStep sets TrainContext.sink)")
-            view = sink.view_for(ctx.table_param)
-            if view is None:
-                raise _hip.NvsfHipError("the gradient sink has no buffer for this table")
-            main, side = torch.cuda.current_stream(x01.device), side_stream(x01.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                x01.record_stream(side)
-                grad_feat.record_stream(side)
-                hashgrid_backward(x01, (0, 1, 2), ctx.grid_spec, grad_feat, grad_table=view.view(-1), fine_from=fine, ws_pool=pool)
-                if last:  # the table's gradient is final: its bucket may go out (event recorded on the side stream)
-                    sink.mark_ready(ctx.table_param)
+    if need_table and not scatter_to_sink(ctx, (x01, grad_feat), lambda views, pool: hashgrid_backward(
+            x01, (0, 1, 2), ctx.grid_spec, grad_feat, grad_table=views[0].view(-1), fine_from=fine, ws_pool=pool)):
+        pool = ctx.train_ctx.ws_pool if ctx.train_ctx is not None else None
+        grad_table = hashgrid_backward(x01, (0, 1, 2), ctx.grid_spec, grad_feat, fine_from=fine, ws_pool=pool)
     return grad_table, None, None, (grad_w if need_w else None), None, None, None, None
 
 
@@ -878,12 +861,9 @@ class DensityRaysFn(Function):
         z_vals, sigma, geo16, x01, feat, h32 = density_uniform_train_forward(rays_o, rays_d, nears, fars, T, aabb_host, bound, noise, table_f16,
                                                                              grid_spec, mlp_w16, sliced)
         ctx.save_for_backward(x01, feat, sigma, mlp_w16)
-        ctx.grid_spec, ctx.mlp_spec, ctx.clamp = grid_spec, mlp_spec, (float(sigma_lo), float(sigma_hi))
-        ctx.table_param = table_params
+        ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray = grid_spec, mlp_spec, (float(sigma_lo), float(sigma_hi)), T
         ctx.need_table, ctx.need_w = ctx.needs_input_grad[8], ctx.needs_input_grad[11]
-        ctx.rows_per_ray, ctx.train_ctx = T, train_ctx
-        if train_ctx is not None and table_params is not None and table_params.requires_grad and torch.is_grad_enabled():
-            train_ctx.expect(table_params)
+        announce(ctx, train_ctx, table_params)
         ctx.mark_non_differentiable(z_vals, geo16)
         return z_vals, sigma, h32[:, 1:mlp_spec.n_out], geo16
 
@@ -941,11 +921,10 @@ class RenderRaysFn(Function):
         ctx.save_for_backward(x01, feat, sigma, sigma_w16, geo16, rgbs, weights, z_vals, nears, fars, head_a_w16, head_b_w16, enc_ray)
         ctx.dims = (N, T, C, int(n_enc), bool(lidar), float(k_scale), None if bg_host is None or lidar else tuple(float(v) for v in bg_host))
         ctx.grid_spec, ctx.mlp_spec, ctx.head_spec, ctx.clamp = grid_spec, sigma_spec, head_spec, (float(sigma_lo), float(sigma_hi))
-        ctx.table_param, ctx.rows_per_ray, ctx.train_ctx = table_params, T, train_ctx
+        ctx.rows_per_ray = T
         ctx.need_table, ctx.need_w = ctx.needs_input_grad[8], ctx.needs_input_grad[11]
         ctx.need_heads = (ctx.needs_input_grad[14], ctx.needs_input_grad[16])
-        if train_ctx is not None and table_params is not None and table_params.requires_grad and torch.is_grad_enabled():
-            train_ctx.expect(table_params)
+        announce(ctx, train_ctx, table_params)
         ctx.mark_non_differentiable(z_vals)
         return z_vals, weights, ws, depth, image
 
@@ -997,7 +976,7 @@ class RenderRaysFn(Function):
                   _hip.ptr(g_depth), N, T, k_scale, _hip.ptr(g_sigma))
         # ---- density MLP + table scatter: DensityFn's backward on what this node saved
         dctx = types.SimpleNamespace(saved_tensors=(x01, feat, sigma, sigma_w16), mlp_spec=ctx.mlp_spec, clamp=ctx.clamp, grid_spec=ctx.grid_spec,
-                                     table_param=ctx.table_param, rows_per_ray=ctx.rows_per_ray, train_ctx=ctx.train_ctx, need_table=ctx.need_table,
+                                     tables=ctx.tables, rows_per_ray=ctx.rows_per_ray, train_ctx=ctx.train_ctx, need_table=ctx.need_table,
                                      need_w=ctx.need_w, g_geo_b=grad_geo_b)
         d = _density_backward(dctx, g_sigma.view(-1), grad_geo)  # (grad_table, None, None, grad_w_sigma, ...)
         out = [None] * 29
@@ -1032,10 +1011,8 @@ class PlanesFn(Function):
         _hip.call("nvsf_planes_fwd", _hip.ptr(xt), M, _hip.ptr(cl), S, 8, _hip.host_u32(res_host), int(want), _hip.ptr(out_s),
                   _hip.ptr(out_d))
         ctx.save_for_backward(xt, cl)
-        ctx.res_host, ctx.want = res_host, want
-        ctx.train_ctx, ctx.planes_param = train_ctx, planes_cl
-        if train_ctx is not None and isinstance(planes_cl, torch.nn.Parameter) and planes_cl.requires_grad and torch.is_grad_enabled():
-            train_ctx.expect(planes_cl)
+        ctx.res_host, ctx.want, ctx.planes_param = res_host, want, planes_cl  # (planes_param: the parameter this node feeds)
+        announce(ctx, train_ctx, planes_cl)
         outs = tuple(o for o in (out_s, out_d) if o is not None)
         return outs if len(outs) > 1 else outs[0]
 
@@ -1047,39 +1024,22 @@ class PlanesFn(Function):
         g_s = next(gi).float().contiguous() if want & 1 else None
         g_d = next(gi).float().contiguous() if want & 2 else None
         need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        # Inside a training step the texel gradients are ADDED straight into the step's gradient sink (the parameter's .grad or its
-        # bucket view), as the table scatters are: a space-time model evaluates its planes three times per ray batch, and autograd
-        # would zero-fill a 67 MB buffer per evaluation and add the three up again.
-        tctx, param = ctx.train_ctx, ctx.planes_param
         res = _hip.host_u32(ctx.res_host)
 
         def launch(g_planes, g_xt):  # the coordinate gradients and the texel scatter are separate kernels: either pointer may be NULL
             _hip.call("nvsf_planes_bwd", _hip.ptr(xt), xt.shape[0], _hip.ptr(planes_cl), S, 8, res, int(want), _hip.ptr(g_s), _hip.ptr(g_d),
                       _hip.ptr(g_planes), _hip.ptr(g_xt))
+        # the coordinate gradients (what the flow field's backward waits for) on this stream first; then the texel scatter -- the longest
+        # kernel of a space-time step -- into the step's gradient sink (a space-time model evaluates its planes three times per ray
+        # batch: autograd would zero-fill a 67 MB buffer per evaluation and add the three up again), else into a buffer for autograd
         g_xt = torch.empty_like(xt) if need_x else None
-        sink_ok = (need_p and tctx is not None and tctx.sink is not None and isinstance(param, torch.nn.Parameter) and param.is_cuda
-                   and param.dtype == torch.float32)
-        if sink_ok and tctx.overlap:
-            # the coordinate gradients (what the flow field's backward waits for) on this stream, the texel scatter -- the longest
-            # kernel of a space-time step -- on the step's side stream beside the rest of backward, as the table scatters
-            if need_x:
-                launch(None, g_xt)
-            tensors = tuple(t for t in (xt, planes_cl, g_s, g_d) if t is not None)
-            if scatter_beside_backward(tctx, param, tensors, lambda view, pool: launch(view, None)):
-                return g_xt, None, None, None, None
-            raise _hip.NvsfHipError("PlanesFn: the step's gradient sink refused the planes parameter")
-        if sink_ok:
-            last = tctx.done(param)
-            view = tctx.sink.view_for(param)
-            launch(view, g_xt)
-            if last:
-                tctx.sink.mark_ready(param)
-            return g_xt, None, None, None, None
-        if tctx is not None and isinstance(param, torch.nn.Parameter):
-            tctx.done(param)
-        g_planes = torch.zeros_like(planes_cl) if need_p else None
-        if need_p or need_x:
-            launch(g_planes, g_xt)
+        if need_x:
+            launch(None, g_xt)
+        g_planes = None
+        if need_p and not scatter_to_sink(ctx, tuple(t for t in (xt, planes_cl, g_s, g_d) if t is not None),
+                                          lambda views, pool: launch(views[0], None)):
+            g_planes = torch.zeros_like(planes_cl)
+            launch(g_planes, None)
         return g_xt, g_planes, None, None, None
 
 
@@ -1151,10 +1111,8 @@ class PlanesMultiFn(Function):
         outs = planes_multi_forward(x, evals, cl, res_host, blend=bool(blend))
         ctx.save_for_backward(x, cl) if fl is None else ctx.save_for_backward(x, cl, fl)
         ctx.evals_meta = [(e[0], e[2], e[3], e[1] is not None) for e in evals]
-        ctx.slots, ctx.res_host, ctx.blend = slots, res_host, bool(blend)
-        ctx.train_ctx, ctx.planes_param = train_ctx, planes_cl
-        if train_ctx is not None and isinstance(planes_cl, torch.nn.Parameter) and planes_cl.requires_grad and torch.is_grad_enabled():
-            train_ctx.expect(planes_cl)
+        ctx.slots, ctx.res_host, ctx.blend, ctx.planes_param = slots, res_host, bool(blend), planes_cl  # (planes_param: as PlanesFn's)
+        announce(ctx, train_ctx, planes_cl)
         full = [x.new_zeros(0)] * 4
         for slot, o in zip(slots, outs):  # (blend: two outputs)
             full[slot] = o
@@ -1208,29 +1166,12 @@ class PlanesMultiFn(Function):
             # columns of an absent neighbour, or of one whose features received no gradient, stay zero
             complete = sum(has_off) == 2 and all(g[i] is not None for i in range(n) if has_off[i])
             g_flow = (torch.empty if complete else torch.zeros)(M, 6, dtype=torch.float32, device=x.device)
-        tctx, param = ctx.train_ctx, ctx.planes_param
-        sink_ok = (need_p and tctx is not None and tctx.sink is not None and isinstance(param, torch.nn.Parameter) and param.is_cuda
-                   and param.dtype == torch.float32)
-        none = (None,) * 6
-        if sink_ok and tctx.overlap:
-            if g_flow is not None:
-                launch(None, g_flow)  # what the flow field's backward waits for: on this stream
-            tensors = tuple(t for t in (x, cl, fl, *g) if t is not None)
-            if scatter_beside_backward(tctx, param, tensors, lambda view, pool: launch(view, None)):
-                return (None, g_flow, None) + none
-            raise _hip.NvsfHipError("PlanesMultiFn: the step's gradient sink refused the planes parameter")
-        if sink_ok:
-            last = tctx.done(param)
-            launch(tctx.sink.view_for(param), g_flow)
-            if last:
-                tctx.sink.mark_ready(param)
-            return (None, g_flow, None) + none
-        if tctx is not None and isinstance(param, torch.nn.Parameter):
-            tctx.done(param)
-        g_planes = torch.zeros_like(cl) if need_p else None
-        if g_planes is not None or g_flow is not None:
-            launch(g_planes, g_flow)
-        return (None, g_flow, g_planes) + none
+            launch(None, g_flow)  # what the flow field's backward waits for: on this stream, before the texel scatter
+        g_planes = None
+        if need_p and not scatter_to_sink(ctx, tuple(t for t in (x, cl, fl, *g) if t is not None), lambda views, pool: launch(views[0], None)):
+            g_planes = torch.zeros_like(cl)
+            launch(g_planes, None)
+        return (None, g_flow, g_planes) + (None,) * 6
 
 
 # ------------------------------------------------------------------------------------------------

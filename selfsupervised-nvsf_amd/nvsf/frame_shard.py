@@ -177,7 +177,7 @@ class GradBuckets:
         for p in self.params:
             p.grad = self.views[p]
         if self._cuda and self.train_ctx is not None:  # kernels that scatter a gradient straight into its bucket view ask for it here
-            self.train_ctx.sink = self                  # (field_ops.DensityFn, through the step's TrainContext)
+            self.train_ctx.sink = self                  # (field_ops.scatter_to_sink, through the step's TrainContext)
 
     def view_for(self, p):
         return self.views.get(p)
@@ -204,7 +204,8 @@ class GradBuckets:
 
     def mark_ready(self, p):
         """The gradient of `p` (in its bucket view) is final.  Called by the hook, or by a kernel wrapper that scattered straight
-        into the view (field_ops.DensityFn on its side stream: the collective is then issued from that stream)."""
+        into the view (field_ops.scatter_to_sink, behind a table's last scatter of the pass -- on the side stream with
+        TrainContext.overlap: the collective then waits for that stream)."""
         if self._hold:
             self._held.append(p)
             return

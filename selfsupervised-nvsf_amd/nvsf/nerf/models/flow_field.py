@@ -76,7 +76,7 @@ class FlowField(nn.Module):
                 if self.grid_train_mode == "fused" and self.n_features_per_level == 8 and self.num_basis == 4 and not xt.requires_grad:
                     # grid lookup + Lagrange reduction as the fused forward kernel, the table gradient straight from dL/d(reduced)
                     t_h = float(t) if t_host is None else t_host
-                    h.append(FlowGridFn.apply(self, xt.float().contiguous(), t_h, self.grid_enc.params))
+                    h.append(FlowGridFn.apply(self, xt.float().contiguous(), t_h, ops.train_context(self), self.grid_enc.params))
                 else:
                     feat = self.grid_enc.encode_columns(xt, (0, 1, 2)).float()
                     h.append(lagrange_reduce(feat, t, self.n_levels, self.n_features_per_level, self.num_basis))
@@ -185,12 +185,10 @@ class FlowGridFn(torch.autograd.Function):
     the gradient of reduced column e) and scatters it with the hash-grid backward kernel."""
 
     @staticmethod
-    def forward(ctx, field, xt, t_host, params):
+    def forward(ctx, field, xt, t_host, train_ctx, params):
         ctx.save_for_backward(xt)
         ctx.field, ctx.t_host, ctx.rows_per_ray = field, t_host, ops.rows_hint(field)
-        ctx.train_ctx, ctx.table_param = ops.train_context(field), params
-        if ctx.train_ctx is not None and params.requires_grad and torch.is_grad_enabled():
-            ctx.train_ctx.expect(params)
+        ops.announce(ctx, train_ctx, params)
         return field._grid_lagrange(xt, t_host)
 
     @staticmethod
@@ -212,11 +210,11 @@ class FlowGridFn(torch.autograd.Function):
         g = grad_red.float().contiguous()
         fine = ops._bin_from(spec2, xt.shape[0], ctx.rows_per_ray)
 
-        def scatter(view, pool):  # on the step's side stream: scatter the 2-feature sums, expand them into the table's gradient
+        def scatter(views, pool):  # into the step's gradient sink: scatter the 2-feature sums, expand them into the table's gradient
             G = ops.hashgrid_backward(xt, (0, 1, 2), spec2, g, fine_from=fine, ws_pool=pool)
-            view.view(-1, 4, 2).addcmul_(G.view(-1, 1, 2), w.view(1, 4, 1))
-        if ops.scatter_beside_backward(ctx.train_ctx, ctx.table_param, (xt, g, w), scatter):
-            return None, None, None, None
+            views[0].view(-1, 4, 2).addcmul_(G.view(-1, 1, 2), w.view(1, 4, 1))
+        if ops.scatter_to_sink(ctx, (xt, g, w), scatter):
+            return None, None, None, None, None
         G = ops.hashgrid_backward(xt, (0, 1, 2), spec2, g, fine_from=fine)
         grad_table = (G.view(-1, 1, 2) * w.view(1, 4, 1)).reshape(-1)
-        return None, None, None, grad_table
+        return None, None, None, None, grad_table

@@ -182,7 +182,7 @@ class HashGrid4D(nn.Module):
                 idx = np.float32(t_host) * np.float32(first.time_resolution - 1)
                 k1, k2 = int(math.floor(idx)), int(math.ceil(idx))
                 params = [pl.hash_t[k1].params for pl in self.hash_dynamic] + [pl.hash_t[k2].params for pl in self.hash_dynamic]
-                return self._reduce(HashDynFn.apply(self, x, t, t_host, k1, k2, *params))
+                return self._reduce(HashDynFn.apply(self, x, t, t_host, k1, k2, _ops.train_context(self), *params))
             return self._reduce(torch.cat([plane(x, t, t_host) for plane in self.hash_dynamic], dim=-1))
         return self._reduce(self._forward_dynamic_fused(x, t, t_host, offset, offset_col))
 
@@ -232,7 +232,7 @@ class HashGrid4D(nn.Module):
         if nb[0] is None and nb[1] is None:
             return None
         params = [pl.hash_t[k1].params for pl in self.hash_dynamic] + [pl.hash_t[k2].params for pl in self.hash_dynamic]
-        return tuple(o if o is None else self._reduce(o) for o in HashDyn3Fn.apply(self, x, t, t_host, k1, k2, flow, nb[0], nb[1], *params))
+        return tuple(o if o is None else self._reduce(o) for o in HashDyn3Fn.apply(self, x, t, t_host, k1, k2, flow, nb[0], nb[1], _ops.train_context(self), *params))
 
     def forward_dynamic3(self, x, t, t_host, offsets, neighbours):
         """No-autograd: the dynamic features of one density query in one launch (csrc/hashgrid4d.hip, k_hash_dynamic3):
@@ -291,33 +291,21 @@ class HashDynFn(torch.autograd.Function):
     gradients reach exactly the tensors the per-slice path would have touched."""
 
     @staticmethod
-    def forward(ctx, enc, x, t, t_host, k1, k2, *params):
+    def forward(ctx, enc, x, t, t_host, k1, k2, train_ctx, *params):
         x = x.float().contiguous()
         out = enc._forward_dynamic_fused(x, t, t_host, None, 0)
         ctx.save_for_backward(x)
-        ctx.enc, ctx.t, ctx.t_host, ctx.k1, ctx.k2 = enc, t, t_host, k1, k2
-        HashDynFn._expect(ctx, enc, params)
+        ctx.enc, ctx.t, ctx.t_host, ctx.k1, ctx.k2, ctx.params = enc, t, t_host, k1, k2, params
+        _ops.announce(ctx, train_ctx, params)
         return out
 
     @staticmethod
-    def _expect(ctx, enc, params):
-        """The slice parameters this node will scatter into, announced to the training step (ops.TrainContext.expect) so that the
-        step's gradient sink knows when each of them has received its last scatter."""
-        ctx.params = params
-        ctx.train_ctx = _ops.train_context(enc)
-        if ctx.train_ctx is not None and torch.is_grad_enabled():
-            seen = []
-            for p in params:
-                if isinstance(p, torch.nn.Parameter) and p.requires_grad and not any(p is q for q in seen):
-                    seen.append(p)
-                    ctx.train_ctx.expect(p)
-
-    @staticmethod
     def backward(ctx, grad_out):
-        return HashDynFn._backward(ctx, grad_out)
+        return (None,) * 7 + HashDynFn._backward(ctx, grad_out)
 
     @staticmethod
     def _backward(ctx, grad_out):
+        """-> the gradients of ctx.params."""
         from nvsf import _hip
         import ctypes
         (x,) = ctx.saved_tensors
@@ -359,31 +347,23 @@ class HashDynFn(torch.autograd.Function):
         # Inside a training step the scatter and its expansion run on the step's side stream, straight into the gradient sink (round 6: the
         # step's main stream is its critical path -- 30.4 ms busy without a gap at 4096 + 4096 rays -- and these 2.5 ms per pass were on
         # it, while the side stream idled for 10 ms per step); nothing on the main stream reads these gradients before the optimiser.
-        params, tctx = getattr(ctx, "params", None), getattr(ctx, "train_ctx", None)
-        settled = False
-        if params is not None and tctx is not None and len(params) == 6 and testing.get("hash4d_scatter") == "side":
-            plan = [(params[i], i, 1.0) for i in range(3)] if same else [(params[i], i % 3, b_lo if i < 3 else b_hi) for i in range(6)]
-            if len({id(p) for p, _, _ in plan}) == len(plan):
-                def scatter(views, pool):
-                    sums = scatter_sums(g_out, col_major)
-                    for view, (_, pair, factor) in zip(views, plan):
-                        view.view(-1, 4).addcmul_(sums[pair].view(-1, 1), lag_t.view(1, 4), value=factor)
-                if _ops.scatter_beside_backward_multi(tctx, [p for p, _, _ in plan], (x, g_out, lag_t), scatter):
-                    return (None,) * 6 + (None,) * len(params)
-                settled = True  # (a refusal has settled them)
-        if params is not None and tctx is not None and not settled:  # the gradients go back through autograd: the announced scatters are settled here
-            seen = []
-            for p in params:
-                if isinstance(p, torch.nn.Parameter) and p.requires_grad and not any(p is q for q in seen):
-                    seen.append(p)
-                    tctx.done(p)
+        # plan: slice parameter -> (pair, blend factor); k1 == k2 passes the same three tensors twice: the first occurrence takes it all
+        plan = {}
+        for i, p in enumerate(ctx.params):
+            plan.setdefault(p, (i % 3, 1.0 if same else (b_lo if i < 3 else b_hi)))
+
+        def scatter(views, pool):
+            sums = scatter_sums(g_out, col_major)
+            for view, p in zip(views, ctx.tables):
+                pair, factor = plan[p]
+                view.view(-1, 4).addcmul_(sums[pair].view(-1, 1), lag_t.view(1, 4), value=factor)
+        if _ops.scatter_to_sink(ctx, (x, g_out, lag_t), scatter if testing.get("hash4d_scatter") == "side" else None):
+            return (None,) * len(ctx.params)
         sums = scatter_sums(g_out, col_major)
         acc = [(g.view(-1, 1) * lag_t.view(1, 4)).reshape(-1) for g in sums]
-        if same:  # the same parameter tensors were passed twice: the whole gradient goes to the first occurrence
-            grads = acc + [None, None, None]
-        else:
-            grads = [g * b_lo for g in acc] + [g * b_hi for g in acc]
-        return (None, None, None, None, None, None, *grads)
+        if same:
+            return tuple(acc) + (None, None, None)
+        return tuple(g * b_lo for g in acc) + tuple(g * b_hi for g in acc)
 
 
 class HashDyn3Fn(torch.autograd.Function):
@@ -392,17 +372,16 @@ class HashDyn3Fn(torch.autograd.Function):
     evaluates them under no_grad), the table gradients of hash_d come from the fused backward kernel."""
 
     @staticmethod
-    def forward(ctx, enc, x, t, t_host, k1, k2, offsets, nb1, nb2, *params):
+    def forward(ctx, enc, x, t, t_host, k1, k2, offsets, nb1, nb2, train_ctx, *params):
         x = x.float().contiguous()
         out0, out1, out2 = enc.forward_dynamic3(x, t, t_host, offsets.detach(), [nb1, nb2])
         ctx.save_for_backward(x)
-        ctx.enc, ctx.t, ctx.t_host, ctx.k1, ctx.k2 = enc, t, t_host, k1, k2
-        HashDynFn._expect(ctx, enc, params)
+        ctx.enc, ctx.t, ctx.t_host, ctx.k1, ctx.k2, ctx.params = enc, t, t_host, k1, k2, params
+        _ops.announce(ctx, train_ctx, params)
         outs = [out0, out1 if out1 is not None else out0.new_zeros(0), out2 if out2 is not None else out0.new_zeros(0)]
         ctx.mark_non_differentiable(outs[1], outs[2])
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, grad_out, _g1, _g2):
-        g = HashDynFn._backward(ctx, grad_out)  # (None x 6, *grads)
-        return (None,) * 9 + tuple(g[6:])
+        return (None,) * 10 + HashDynFn._backward(ctx, grad_out)

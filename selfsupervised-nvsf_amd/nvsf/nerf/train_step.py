@@ -215,12 +215,12 @@ class RenderTrainStep:
         self._cham = None
         self.global_step = 0
         self.failed_to_load = []  # components of the last load_checkpoint whose state could not be restored
-        self.scatter_overlap = True  # table scatters on a side stream beside the rest of backward (field_ops.DensityFn)
+        self.scatter_overlap = True  # table scatters on a side stream beside the rest of backward (field_ops.scatter_to_sink)
         self.split_backward = bool(split_backward)
         self.ray_chunks = max(1, int(ray_chunks))
         # more than one rank: gradients live in flat buckets that are all-reduced while backward still runs (frame_shard.GradBuckets)
         # what the table-scatter nodes of the model need to know about this step (gradient sink, side-stream overlap, scatters still
-        # expected): an object of the step, attached to the model -- not process-wide state
+        # expected: field_ops.announce / scatter_to_sink): an object of the step, attached to the model -- not process-wide state
         from nvsf import field_ops
         self.train_ctx = field_ops.TrainContext()
         for mod in model.modules():
@@ -428,6 +428,7 @@ class RenderTrainStep:
                 tctx.sink, local_sink = self._sink, True
         try:
             self.scaler.scale(loss).backward()
+            tctx.end_pass()  # a table announced but not scattered into as often is marked ready behind what it received
         finally:
             if overlap:
                 tctx.overlap = False
@@ -544,7 +545,7 @@ class RenderTrainStep:
         if self.model.__dict__.get("_train_ctx") is not self.train_ctx:  # another step object was built on this model since
             for mod in self.model.modules():
                 mod.__dict__["_train_ctx"] = self.train_ctx
-        self.train_ctx.begin_step()  # a table is final after the LAST scatter it receives in this step (ray_chunks > 1: several)
+        self.train_ctx.begin_step()  # a table is final after the LAST scatter it receives in a backward pass (ray_chunks > 1: several)
         self._sink = None
         try:
             return self._forward_backward(batch, defer)

@@ -1,5 +1,5 @@
 """GPU: table gradients that arrive in several scatters per step (RenderTrainStep(ray_chunks=2): each slice of the ray batch is its
-own autograd sub-graph, each with its own DensityFn.backward) -- on one process and on two ranks that share cuda:0 over gloo (the
+own autograd sub-graph, each with its own table-scatter nodes) -- on one process and on two ranks that share cuda:0 over gloo (the
 N > 1 control flow without a second GPU: GradBuckets, hold / release, the side-stream scatter into bucket views).  The scatters of
 one table accumulate into ONE buffer on the side stream; a table's bucket may only be all-reduced after its LAST scatter."""
 import os
@@ -104,6 +104,40 @@ def test_ray_chunks_give_the_same_gradients_on_one_process(dev, overlap, split):
         train_step.RenderTrainStep.__init__ = real
     assert n_coll == 0 and abs(loss - loss_ref) <= 1e-5 * abs(loss_ref)
     _assert_same(ref, got)
+
+
+@pytest.mark.parametrize("dynamic", [False, True])
+def test_ray_chunks_mark_each_table_ready_once_per_pass(dev, dynamic, monkeypatch):
+    """ray_chunks = 2 on one process: every table is announced twice per backward pass (one node per slice) and the step's sink is told
+    it is final exactly once per pass, behind the second scatter; no announcement is left unsettled (TrainContext.end_pass)."""
+    from nvsf import field_ops
+    student, batch, S = _model_and_batch(dev, 2, dynamic=dynamic)
+    announced, ready, passes = {}, [], []
+    real_expect, real_mark, real_end = field_ops.TrainContext.expect, field_ops.LocalGradSink.mark_ready, field_ops.TrainContext.end_pass
+
+    def expect(self, p):
+        announced[id(p)] = announced.get(id(p), 0) + 1
+        real_expect(self, p)
+
+    def mark_ready(self, p):
+        ready.append(id(p))
+        real_mark(self, p)
+
+    def end_pass(self):
+        leftover = real_end(self)
+        passes.append((dict(announced), list(ready), set(leftover)))
+        announced.clear()
+        ready.clear()
+        return leftover
+    monkeypatch.setattr(field_ops.TrainContext, "expect", expect)
+    monkeypatch.setattr(field_ops.LocalGradSink, "mark_ready", mark_ready)
+    monkeypatch.setattr(field_ops.TrainContext, "end_pass", end_pass)
+    _grads_of_one_step(student, batch, S, ray_chunks=2)
+    assert len(passes) == 2  # camera pass, LiDAR pass
+    for counts, marked, leftover in passes:
+        assert counts and all(n >= 2 and n % 2 == 0 for n in counts.values()), counts  # the batch was sliced: every node twice
+        assert sorted(marked) == sorted(counts), (marked, counts)  # one mark_ready per table, for every table scattered into
+        assert leftover == set()
 
 
 def _free_port():
