@@ -312,13 +312,15 @@ def mlp_forward(x, weights_f16, spec, out=None, prefix=None, n_store=None):
 MLP_GRAD_SCALE = 128.0  # fp16 gradients inside nvsf_mlp_bwd are multiplied by this (tcnn's default loss_scale)
 
 
-def density_logit_gradient_parts(g_sigma, sigma, g_geo, g_geo_b, n_geo, clamp):
+def density_logit_gradient_parts(g_sigma, sigma, g_geo, g_geo_b, n_geo, clamp, n_hidden=1):
     """(grad_sigma, sigma, geo_a, geo_b, n_geo, lo, hi) for mlp_backward(density_grad=...) when the pieces have the layout
-    nvsf_mlp_bwd_density reads (fp32, geometry-gradient rows of >= 16 floats, 16-byte aligned), else None."""
+    nvsf_mlp_bwd_density reads (fp32, geometry-gradient rows of >= 16 floats, 16-byte aligned) and the density network has the one
+    hidden layer that kernel is built for (`n_hidden` of the density network's MlpSpec: a two-hidden-layer sigma_net,
+    num_layers_sigma=3, takes the matrix form), else None."""
     def rows_ok(t):
         return (t is not None and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= 16
                 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 and t.shape[1] >= n_geo)
-    if not (1 <= n_geo <= 15 and rows_ok(g_geo) and (g_geo_b is None or (rows_ok(g_geo_b) and g_geo_b.stride(0) == g_geo.stride(0)))):
+    if n_hidden != 1 or not (1 <= n_geo <= 15 and rows_ok(g_geo) and (g_geo_b is None or (rows_ok(g_geo_b) and g_geo_b.stride(0) == g_geo.stride(0)))):
         return None
     if sigma is None or sigma.dtype != torch.float32 or not sigma.is_contiguous():
         return None
@@ -799,7 +801,7 @@ def _density_backward(ctx, g_sigma, g_geo):
     g_geo_b = getattr(ctx, "g_geo_b", None)
     parts = None
     if _testing.get("density_grad") == "composed" and x01.is_cuda:
-        parts = density_logit_gradient_parts(g_sigma, sigma.view(-1), g_geo, g_geo_b, spec.n_out - 1, ctx.clamp)
+        parts = density_logit_gradient_parts(g_sigma, sigma.view(-1), g_geo, g_geo_b, spec.n_out - 1, ctx.clamp, n_hidden=spec.n_hidden)
     grad_h = None
     if parts is None:
         if g_geo_b is not None:

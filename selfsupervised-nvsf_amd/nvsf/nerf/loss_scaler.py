@@ -24,6 +24,8 @@ A table that receives its feature gradient through an fp16 hand-over (the static
 the side stream behind their scatter: the deferred Adam pass skips on (early OR late), and an overflow found only there reaches
 `update` one step later (tests/test_dynamic_gpu.py::test_overflow_only_in_a_deferred_table_gradient_never_reaches_the_table).
 """
+import math
+
 import torch
 
 
@@ -35,6 +37,7 @@ class LossScaler:
         self._backoff_factor, self._growth_interval = float(backoff_factor), int(growth_interval)
         self._init_growth_tracker = 0
         self._scale = self._growth_tracker = self._one = None
+        self._held = None  # device bool: the last `update(hold=True)` completed a growth interval, its doubling awaits `release_growth`
 
     def is_enabled(self):
         return self._enabled
@@ -99,24 +102,42 @@ class LossScaler:
                 optimizer.step()
         return found_inf
 
-    def hold_growth(self):
-        """The next `update` cannot complete a growth interval (device-side clamp of the tracker, no read-back): for a step whose
-        overflow decision is not final yet (RenderTrainStep's deferred table check)."""
-        if self._enabled and self._growth_interval >= 2:
-            self._lazy_init()
-            self._growth_tracker.clamp_(max=self._growth_interval - 2)
-
-    def update(self, found_inf):
+    def update(self, found_inf, hold=False):
+        """GradScaler.update.  `hold`: the step's overflow decision is not final yet (RenderTrainStep's deferred table check): the
+        update runs as GradScaler's -- a clean step advances the tracker, an interval it completes restarts it -- but the doubling
+        that interval earns is held on the device until `release_growth` is given the late check's outcome (no read-back)."""
         if not self._enabled:
             return
         self._lazy_init()
-        torch._amp_update_scale_(self._scale, self._growth_tracker, found_inf, self._growth_factor, self._backoff_factor, self._growth_interval)
+        if self._held is not None:
+            raise RuntimeError("LossScaler.update: the growth held by the previous update has not been released (release_growth)")
+        if hold:
+            self._held = (found_inf.view(()) == 0) & (self._growth_tracker + 1 == self._growth_interval)
+            torch._amp_update_scale_(self._scale, self._growth_tracker, found_inf, 1.0, self._backoff_factor, self._growth_interval)
+        else:
+            torch._amp_update_scale_(self._scale, self._growth_tracker, found_inf, self._growth_factor, self._backoff_factor, self._growth_interval)
+
+    def release_growth(self, late_found):
+        """Settles a held doubling: the scale grows now if the held update completed its interval and `late_found` (device fp32 [1],
+        the deferred check of that same step) is 0.  A late overflow drops it; the caller's next `update` then sees that overflow
+        (found OR late) and backs the scale off.  Growth therefore comes at most one update after GradScaler's."""
+        if self._held is None:
+            return
+        grown = self._scale * self._growth_factor
+        grow = self._held & (late_found.view(()) == 0) & torch.isfinite(grown)
+        self._scale.copy_(torch.where(grow, grown, self._scale))
+        self._held = None
 
     # ---- torch.amp.GradScaler's checkpoint format (nvsf/nerf/utils.py:622-648 stores scaler.state_dict()) ---------------------------
     def state_dict(self):
+        """GradScaler's dict.  A doubling still held for a deferred check (RenderTrainStep.sync settles that check first) is saved
+        as granted: GradScaler's own state after that clean step."""
         if not self._enabled:
             return {}
-        return {"scale": self.get_scale(), "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+        scale = self.get_scale()
+        if self._held is not None and bool(self._held) and math.isfinite(scale * self._growth_factor):
+            scale *= self._growth_factor
+        return {"scale": scale, "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
                 "growth_interval": self._growth_interval,
                 "_growth_tracker": self._init_growth_tracker if self._growth_tracker is None else int(self._growth_tracker)}
 
@@ -129,6 +150,7 @@ class LossScaler:
         self._growth_factor, self._backoff_factor = float(state["growth_factor"]), float(state["backoff_factor"])
         self._growth_interval = int(state["growth_interval"])
         self._init_growth_tracker = int(state["_growth_tracker"])
+        self._held = None
         if self._scale is not None:
             self._scale.fill_(self._init_scale)
             self._growth_tracker.fill_(self._init_growth_tracker)

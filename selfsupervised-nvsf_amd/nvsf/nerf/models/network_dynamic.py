@@ -333,7 +333,8 @@ class DensityTailFn(torch.autograd.Function):
         # as the static field's node does), else by a pass of its own
         parts = None
         if testing.get("density_grad") == "composed" and x16.is_cuda:
-            parts = ops.density_logit_gradient_parts(g_sigma, sigma, g_geo, None, spec.n_out - 1, (activation._LO, activation._HI))
+            parts = ops.density_logit_gradient_parts(g_sigma, sigma, g_geo, None, spec.n_out - 1, (activation._LO, activation._HI),
+                                                     n_hidden=spec.n_hidden)
         if parts is not None:
             grad_x, gw = ops.mlp_backward(x16[:, :spec.n_in], w16, spec, None, need_grad_x=need_x, density_grad=parts)
         else:

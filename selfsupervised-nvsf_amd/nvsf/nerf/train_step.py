@@ -446,6 +446,7 @@ class RenderTrainStep:
             ev_c, carry = self._late_carry
             self._late_carry = None
             ev_c.synchronize()
+            self.scaler.release_growth(carry)
             if float(carry) != 0.0:
                 self.scaler.update(carry)
         if self._pending is not None:
@@ -522,12 +523,12 @@ class RenderTrainStep:
                 main = torch.cuda.current_stream()
                 main.wait_event(prev[0])
                 prev[1].record_stream(main)  # allocated on the side stream, consumed here
+                self.scaler.release_growth(prev[1])  # the doubling the previous step earned, unless its late check found an overflow
                 found = torch.maximum(found, prev[1])
-            if self._late_carry is not None:
-                # this step's late check is still pending: its `found` may yet turn out to have been an overflow, so the step must not be
-                # the one that completes a growth interval (the scale would double now and halve one step later)
-                self.scaler.hold_growth()
-            self.scaler.update(found)
+            # this step's late check still pending: its `found` may yet turn out to have been an overflow, so a growth interval it
+            # completes doubles the scale only at the next step, once that check is known (else the scale would double now and halve
+            # one step later); the tracker itself advances as GradScaler's does
+            self.scaler.update(found, hold=self._late_carry is not None)
         if self.error_maps is not None:
             self.update_error_maps(batch)
         self.sched.step()

@@ -302,3 +302,10 @@ def test_density_logit_gradient_composed_in_the_kernel(dev, n_in, two_heads, blo
     # layouts the kernel does not read are refused by the helper (the caller then takes the matrix form)
     assert ops.density_logit_gradient_parts(g_sigma, sigma, geo_a[:, 1:16], None, 15, (lo, hi)) is None      # rows not 16-byte aligned
     assert ops.density_logit_gradient_parts(g_sigma, sigma, geo_a[:, :15].contiguous(), None, 15, (lo, hi)) is None  # 15-float rows
+    # a density network with two hidden layers (num_layers_sigma=3): nvsf_mlp_bwd_density is built for one and refuses the composed
+    # operand fetch, so the helper sends the caller to the matrix form (tests/test_static_grad_f64_gpu.py trains such a model)
+    assert ops.density_logit_gradient_parts(g_sigma, sigma, geo_a[:, :15], None, 15, (lo, hi), n_hidden=2) is None
+    spec2 = ops.MlpSpec(n_in, 16, 64, 2)
+    w2 = (torch.randn(spec2.n_params, generator=g) * 0.1).to(dev).half()
+    with pytest.raises(_hip.NvsfHipError):
+        ops.mlp_backward(x, w2, spec2, None, grad_x_blocks=blocks, density_grad=parts)

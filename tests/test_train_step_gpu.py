@@ -712,22 +712,117 @@ def test_density_gradient_composed_equals_the_matrix_form_in_the_step(dev, varia
         assert scale > 0 and float((a - b).abs().max()) <= 1e-5 * scale, n
 
 
-def test_loss_scaler_hold_growth_delays_the_doubling_by_one_update(dev):
-    """a step whose deferred overflow check is still pending must not be the one that completes a growth interval
-    (LossScaler.hold_growth: a device-side clamp of GradScaler's growth tracker before `update`)."""
+def test_loss_scaler_held_growth_is_granted_one_update_later_unless_the_late_check_overflows(dev):
+    """a step whose deferred overflow check is still pending must not double the scale before that check is known, and
+    must not lose the interval either (LossScaler.update(hold=True) completes GradScaler's tracker and holds the doubling on the device;
+    release_growth grants it when the late check is clean, drops it when it found an overflow)."""
     from nvsf.nerf.loss_scaler import LossScaler
-    clean = torch.zeros(1, device=dev)
+    clean, inf = torch.zeros(1, device=dev), torch.ones(1, device=dev)
     plain, held = LossScaler(device=dev, init_scale=4.0, growth_interval=3), LossScaler(device=dev, init_scale=4.0, growth_interval=3)
     for sc in (plain, held):
         sc.update(clean)
         sc.update(clean)
     plain.update(clean)
-    assert plain.get_scale() == 8.0             # third clean update in a row: doubled
-    held.hold_growth()
+    assert plain.get_scale() == 8.0                              # third clean update in a row: doubled
+    held.update(clean, hold=True)
+    assert held.get_scale() == 4.0                               # held: the interval is complete, its doubling waits ...
+    assert held.state_dict()["scale"] == 8.0 and held.state_dict()["_growth_tracker"] == 0  # (a checkpoint sees it granted)
+    held.release_growth(clean)
+    assert held.get_scale() == 8.0                               # ... and is granted once the late check is clean
+    assert held.state_dict() == plain.state_dict()
+    for sc in (plain, held):                                     # the tracker ran on: the next interval is not one update longer
+        sc.update(clean)
+        sc.update(clean)
+    plain.update(clean)
+    held.update(clean, hold=True)
+    held.release_growth(clean)
+    assert plain.get_scale() == held.get_scale() == 16.0
+    held.update(clean, hold=True)                                # a held update that does not complete an interval holds nothing
+    held.release_growth(clean)
+    assert held.get_scale() == 16.0 and held.state_dict()["_growth_tracker"] == 1
     held.update(clean)
-    assert held.get_scale() == 4.0              # held: this update cannot complete the interval ...
-    held.update(clean)
-    assert held.get_scale() == 8.0              # ... the next one does
-    held.hold_growth()
-    held.update(torch.ones(1, device=dev))
-    assert held.get_scale() == 4.0              # an overflow halves as always
+    held.update(clean, hold=True)
+    held.release_growth(inf)                                     # the late check found an overflow: no doubling ...
+    assert held.get_scale() == 16.0
+    held.update(inf)                                             # ... and the caller's next update (found OR late) backs off
+    assert held.get_scale() == 8.0 and held.state_dict()["_growth_tracker"] == 0
+    held.update(inf, hold=True)
+    held.release_growth(clean)
+    assert held.get_scale() == 4.0                               # an overflow halves as always, held or not
+    held.update(clean, hold=True)
+    with pytest.raises(RuntimeError):                            # a held doubling is never overwritten by the next update
+        held.update(clean)
+    held.release_growth(clean)
+    loaded = LossScaler(device=dev)
+    loaded.load_state_dict(held.state_dict())
+    assert loaded.state_dict() == held.state_dict()
+
+
+def _gradscaler_schedule(init_scale, flags, interval):
+    """torch.amp.GradScaler.update's rule (the same ATen kernel, on the host) fed one overflow flag per step -> scale after each step."""
+    scale, tracker, out = torch.full((), float(init_scale)), torch.zeros((), dtype=torch.int32), []
+    for f in flags:
+        torch._amp_update_scale_(scale, tracker, torch.full((1,), float(f)), 2.0, 0.5, interval)
+        out.append(float(scale))
+    return out, int(tracker)
+
+
+@pytest.mark.parametrize("mode", ["deferred", "not_deferred", "ray_chunks_2"])
+def test_loss_scale_schedule_follows_gradscaler(dev, mode):
+    """with the last table's update deferred (the default single-GPU step) every step leaves a late overflow check
+    pending, and the scale could halve but never double again.  Here a small RenderTrainStep runs a forced-overflow stretch (initial
+    scale 2^24: the fp16 gradients overflow until the scale has halved far enough) and then about four growth intervals of clean steps.
+    The overflow flag of every step is read from the gradients themselves (early OR late tables, after the step has finished), the
+    scale after every step from the scaler, and the sequence must be GradScaler's for those flags -- except that a doubling may come
+    one step late, and only while a late check was pending at the step that earned it.  The scale must grow back after the stretch,
+    and a checkpoint taken with a doubling still held must hold GradScaler's scale and tracker."""
+    from nvsf import synthetic as S
+    from nvsf.nerf.models.network_static import NeRFNetworkStatic
+    from nvsf.nerf.train_step import RenderTrainStep
+    kw = dict(bound=S.BOUND, min_near=S.MIN_NEAR, min_near_lidar=S.MIN_NEAR, lidar_max_depth=S.LIDAR_MAX_DEPTH, log2_hashmap_size=14)
+    torch.manual_seed(2)
+    teacher = NeRFNetworkStatic(**kw)
+    with torch.no_grad():
+        for enc in (teacher.hash_encoder_lidar, teacher.hash_encoder_camera):
+            enc.params.normal_(0.0, 0.2)
+    teacher = teacher.to(dev).eval()
+    batch = _batch(S, teacher, dev, n=512, T=32, seed=3)
+    torch.manual_seed(6)
+    m = NeRFNetworkStatic(**kw).to(dev)
+    step = RenderTrainStep(m, num_steps=32, scale=S.SCALE, ema_decay=None, ray_chunks=2 if mode == "ray_chunks_2" else 1)
+    step.defer_last_table = mode != "not_deferred"
+    interval, init = 4, 2.0 ** 20
+    step.scaler = _LossScaler()(init_scale=init, growth_interval=interval)
+    flags, scales, pending = [], [], []
+
+    def one_step():
+        torch.manual_seed(200 + len(flags))
+        step.step(batch)
+        pending.append(step._late_carry is not None)
+        torch.cuda.synchronize()  # the deferred table's pass included: every gradient of this step is final and still in .grad
+        flags.append(any(not bool(torch.isfinite(p.grad).all()) for p in m.parameters() if p.grad is not None))
+        scales.append(step.scaler.get_scale())
+    while len(flags) < 40 and (not flags or flags[-1]):  # the forced stretch: overflowing steps until the first clean one
+        one_step()
+    n0 = len(flags) - 1
+    for _ in range(4 * interval + 2):  # about four growth intervals after it
+        one_step()
+    assert n0 >= 2 and all(flags[:n0]) and not flags[n0], flags
+    assert all(pending) == (mode != "not_deferred") and any(pending) == all(pending)
+    ref, tracker = _gradscaler_schedule(init, flags, interval)
+    late = []
+    for k, (got, want) in enumerate(zip(scales, ref)):
+        if got != want:
+            # the one permitted difference: a doubling GradScaler makes at step k arrives at step k + 1, behind k's pending late check
+            grew = k > 0 and want == 2.0 * ref[k - 1] and not flags[k]
+            assert grew and pending[k] and got == ref[k - 1] and (k + 1 == len(ref) or scales[k + 1] == ref[k + 1]), (mode, k, scales, ref)
+            late.append(k)
+    grown = [k for k in range(n0 + 1, len(ref)) if ref[k] == 2.0 * ref[k - 1]]
+    assert len(grown) >= 2, (mode, ref)  # the run does cover growth intervals (GradScaler doubles in them) ...
+    assert sum(1 for k in range(n0 + 1, len(scales)) if scales[k] == 2.0 * scales[k - 1]) >= len(grown) - 1  # ... and so does the step
+    if mode == "not_deferred":
+        assert not late  # no check pending: GradScaler's sequence exactly
+    state = step.checkpoint_state()["scaler"]  # settles a doubling the last step may still hold
+    assert (state["scale"], state["_growth_tracker"]) == (ref[-1], tracker), (state, ref[-1], tracker)
+    assert step.scaler.get_scale() == ref[-1]
+    print(f"{mode}: {n0} overflow steps, scale {scales[n0]:g} -> {scales[-1]:g}, {len(grown)} doublings, {len(late)} of them one step late")
