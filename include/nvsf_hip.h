@@ -719,6 +719,23 @@ int nvsf_mse_sum_bwd(const float* a, const float* b, uint32_t n, float alpha, co
  * :1420-1421 one update per epoch): shadow -= one_minus_decay * (shadow - param), fp32 [n]. */
 int nvsf_ema_update(float* shadow, const float* param, uint64_t n, float one_minus_decay, nvsf_stream_t stream);
 
+/* ---- 8. mesh export of the density field ------------------------------------------------------------------------------ */
+
+/* ref: extract_geometry -> mcubes.marching_cubes, nvsf/nerf/utils.py:350-384 (called by export_mesh_density, :559-608).
+ * Marching cubes over u [nx, ny, nz] fp32, C-contiguous (z fastest), nx ny nz < 2^31; a point is inside iff u >= iso (NaN: outside).
+ * tables: the case tables of nvsf/nerf/mesh.py (4432 bytes, 4-byte aligned, device memory).  Two passes with one host read between:
+ * count writes totals (device uint64 [2]) = (vertices, triangles) and leaves per-point prefixes in the workspace (8 ceil(N / 4096)
+ * + 4 N bytes, 8-byte aligned, N = nx ny nz; ws_bytes is checked); emit reads the same workspace and writes vertices [n_vertices, 3]
+ * fp32 (index space) and triangles [n_triangles, 3] int32, where n_vertices / n_triangles are the totals read back (< 2^31) and
+ * v_capacity / t_capacity the rows the two buffers hold (NVSF_ERR_INVALID_ARG when smaller).  Vertex order: (point linear index,
+ * edge axis x < y < z); triangle order: (cube linear index, case-table order); (v1 - v0) x (v2 - v0) points from inside to outside.
+ * A grid with a dimension of 1 has no cube: count writes zero totals, emit writes nothing.  Deterministic (no atomics). */
+int nvsf_marching_cubes_count(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float iso, const void* tables, void* workspace,
+                              size_t ws_bytes, uint64_t* totals, nvsf_stream_t stream);
+int nvsf_marching_cubes_emit(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float iso, const void* tables, const void* workspace,
+                             size_t ws_bytes, uint32_t n_vertices, uint32_t n_triangles, float* vertices, uint32_t v_capacity,
+                             int32_t* triangles, uint32_t t_capacity, nvsf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,9 @@ SIGNATURES = {
                                       _P, _P, _P, _P, _P, _P, _P],
     "nvsf_render_occupancy_fwd": [_P, _P, _P, _P, _P, _F, _F, _U, _U, _U, _U, _P, _U, _U, _P, _P, _P, _P, _I, _P, _P, _F, _F, _P, _P, _P, _P],
     "nvsf_field_heads_uniform_fwd": [_P, _P, _P, _P, _I, _P, _P, _U, _U, _F, _P, _P],
+    # section 8: mesh export (marching cubes)
+    "nvsf_marching_cubes_count": [_P, _U, _U, _U, _F, _P, _P, ctypes.c_size_t, _P],
+    "nvsf_marching_cubes_emit": [_P, _U, _U, _U, _F, _P, _P, ctypes.c_size_t, _U, _U, _P, _U, _P, _U],
 }
 
 _lib = None

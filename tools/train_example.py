@@ -1,6 +1,7 @@
 """End-to-end example of the multimodal training loop around the hot path (BASELINE config 4), one process per GPU:
 
     python tools/train_example.py --root /path/to/kitti360_nvsf --sequence 1908 [--dynamic] [--epochs 6] [--plain]
+                                  [--export-mesh out.ply --mesh-res 256 256 256 --mesh-threshold 10]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 tools/train_example.py ...
 
 Data: the reference's on-disk formats (transforms_{seq}_{split}.json + range-image .npy + images; nvsf/nerf/dataset/formats.py).
@@ -10,6 +11,7 @@ all-reduce of the gradients, then Adam under the loss scaler (nvsf/nerf/train_st
 (configs/kitti360_1908.txt: grad_loss, use_error_map; trainer.py:1035-1062): epochs over the frames, every second epoch samples 2 x 8 LiDAR
 patches from the error map and adds the structural regularisation, every step writes its per-ray losses back into the frame's error maps,
 one EMA update per epoch; --plain = random pixels and the default losses only.  Reports loss terms, PSNR, range RMSE, CD / F-score.
+--export-mesh then writes the density field's marching-cubes mesh (nvsf/nerf/mesh.py) at the time of the first evaluation frame.
 """
 import argparse
 import os
@@ -56,6 +58,10 @@ def main():
     ap.add_argument("--num-rays", type=int, default=4096)
     ap.add_argument("--num-steps", type=int, default=768)
     ap.add_argument("--dynamic", action="store_true", help="the reference's space-time model instead of the static hash field")
+    ap.add_argument("--export-mesh", default=None, metavar="PATH", help="after training, write the density field's mesh as a binary PLY "
+                    "(marching cubes on the device, at the time of the first evaluation frame; nvsf/nerf/mesh.py)")
+    ap.add_argument("--mesh-res", type=int, nargs=3, default=[256, 256, 256], metavar=("NX", "NY", "NZ"))
+    ap.add_argument("--mesh-threshold", type=float, default=10.0, help="density at the surface (inside: sigma >= threshold)")
     args = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
@@ -116,6 +122,11 @@ def main():
     if rank == 0:
         print(f"evaluation over {res['frames']} frames: loss {res['loss']:.4f}, PSNR {res['psnr']:.2f} dB, range RMSE {res['depth_rmse_m']:.2f} m, "
               f"chamfer distance {res['chamfer_distance']:.3f}, F-score {res['f_score']:.3f}")
+    if args.export_mesh and rank == 0:
+        from nvsf.nerf.mesh import export_mesh_density
+        t_first = float(whole.collate([0])["time"].reshape(-1)[0])
+        v, f = export_mesh_density(model, args.export_mesh, xyz_res=args.mesh_res, threshold=args.mesh_threshold, time=t_first)
+        print(f"mesh at time {t_first:.4f}: {len(v)} vertices, {len(f)} triangles -> {args.export_mesh}")
     if world > 1:
         dist.destroy_process_group()
 
