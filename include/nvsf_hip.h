@@ -736,6 +736,26 @@ int nvsf_marching_cubes_emit(const float* u, uint32_t nx, uint32_t ny, uint32_t 
                              size_t ws_bytes, uint32_t n_vertices, uint32_t n_triangles, float* vertices, uint32_t v_capacity,
                              int32_t* triangles, uint32_t t_capacity, nvsf_stream_t stream);
 
+/* ---- 9. LiDAR cloud cleaning for the scene-flow loss --------------------------------------------------------------------- */
+
+/* ref: point_removal -> Open3D remove_statistical_outlier, nvsf/nerf/utils.py:231-268 (called by Trainer.process_pointcloud,
+ * trainer.py:1848-1912).  out_mean[i] = mean Euclidean distance from point i to its min(k, n) nearest points of the same cloud, the
+ * point itself included (distance 0): the statistic Open3D thresholds.  points [n, 3] fp32, 1 <= k <= 64, n <= 2^28; n = 0 is a
+ * no-op.  Brute force, squared distances from coordinate differences, ties broken arbitrarily (the mean does not depend on it);
+ * bit-identical between runs (no atomics, fixed-order reduction). */
+int nvsf_knn_mean_distance(const float* points, uint32_t n, uint32_t k, float* out_mean, nvsf_stream_t stream);
+
+/* ref: my_ransac's inlier test, nvsf/nerf/utils.py:151-205.  counts[h] += #{i : |a x_i + b y_i + c z_i + d| < threshold} for the K plane
+ * hypotheses planes [K, 4] = (a, b, c, d) fp32 with (a, b, c) a unit normal; the distance is evaluated in fp64.  counts [K] int32 is
+ * ZEROED BY THE CALLER; integer atomics, so the result does not depend on scheduling.  n <= 2^28, K <= 2^20, threshold >= 0. */
+int nvsf_plane_inlier_count(const float* points, uint32_t n, const float* planes, uint32_t K, float threshold, int32_t* counts,
+                            nvsf_stream_t stream);
+
+/* ref: the union of the six fits' inliers and `pc[:, 2] < -1`, nvsf/nerf/utils.py:246-254.  mask[i] = 1 where point i lies within
+ * threshold of ANY of the R planes [R, 4] and z_i < z_max, else 0 (every element of mask [n] uint8 is written; R = 0: all 0). */
+int nvsf_plane_inlier_mask(const float* points, uint32_t n, const float* planes, uint32_t R, float threshold, float z_max, uint8_t* mask,
+                           nvsf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,10 @@ SIGNATURES = {
     # section 8: mesh export (marching cubes)
     "nvsf_marching_cubes_count": [_P, _U, _U, _U, _F, _P, _P, ctypes.c_size_t, _P],
     "nvsf_marching_cubes_emit": [_P, _U, _U, _U, _F, _P, _P, ctypes.c_size_t, _U, _U, _P, _U, _P, _U],
+    # section 9: LiDAR cloud cleaning (outlier statistic, ground-plane inliers)
+    "nvsf_knn_mean_distance": [_P, _U, _U, _P],
+    "nvsf_plane_inlier_count": [_P, _U, _P, _U, _F, _P],
+    "nvsf_plane_inlier_mask": [_P, _U, _P, _U, _F, _F, _P],
 }
 
 _lib = None

@@ -89,3 +89,38 @@ def boxes_density_grid(rng, cascades=2, H=128, n_boxes=64, bound=BOUND):
             occ |= mx[:, None, None] & my[None, :, None] & mz[None, None, :]
         grid[c, morton] = occ.reshape(-1).astype(np.float32)
     return grid
+
+
+def street_range_image(rng, boxes=None, n_boxes=10, ground_z=-1.7, max_range=80.0, drop=0.1, isolated=0.002, isolated_range=(5.0, 60.0),
+                       hw=LIDAR_HW, fov=LIDAR_FOV):
+    """One LiDAR range image [H, W] float32 (metres, 0 = no return) of a street-like scene seen from the origin: the ground plane
+    z = ground_z and axis-aligned boxes standing on it, ray-cast along the sensor model above.  `boxes` [B, 6] = (x0, y0, z0, x1, y1, z1);
+    None draws `n_boxes` within +-35 m, none within 5 m of the origin.  Ranges above `max_range` and a random fraction `drop` of the
+    pixels are 0; a fraction `isolated` of the pixels is replaced by a uniform range in `isolated_range`: isolated returns in free
+    space (or below the ground).  Returns (range image, boxes, mask [H, W] of the isolated pixels)."""
+    H, W = hw
+    fov_up, fov_v, fov_hoz = fov
+    if boxes is None:
+        boxes = []
+        while len(boxes) < n_boxes:
+            c = rng.uniform(-35.0, 35.0, size=2)
+            half = rng.uniform(0.8, 3.0, size=2)
+            if np.all(np.abs(c) - half < 5.0):
+                continue
+            boxes.append([c[0] - half[0], c[1] - half[1], ground_z, c[0] + half[0], c[1] + half[1], ground_z + rng.uniform(1.5, 4.0)])
+    boxes = np.asarray(boxes, np.float64).reshape(-1, 6)
+    i, j = np.arange(W)[None, :], np.arange(H)[:, None]
+    beta = -(i - W / 2) / W * fov_hoz * np.pi / 180.0
+    alpha = (fov_up - j / H * fov_v) * np.pi / 180.0
+    d = np.stack([np.cos(alpha) * np.cos(beta), np.cos(alpha) * np.sin(beta), np.broadcast_to(np.sin(alpha), (H, W))], -1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(d[..., 2] < 0, ground_z / d[..., 2], np.inf)
+        for b in boxes:  # slab test from the origin
+            t0, t1 = b[:3] / d, b[3:] / d
+            near, far = np.minimum(t0, t1).max(-1), np.maximum(t0, t1).min(-1)
+            t = np.where((near <= far) & (near > 0), np.minimum(t, near), t)
+    t = np.where(np.isfinite(t) & (t <= max_range), t, 0.0)
+    t[rng.random((H, W)) < drop] = 0.0
+    iso = rng.random((H, W)) < isolated
+    t[iso] = rng.uniform(*isolated_range, size=int(iso.sum()))
+    return t.astype(np.float32), boxes, iso

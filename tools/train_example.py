@@ -1,7 +1,7 @@
 """End-to-end example of the multimodal training loop around the hot path (BASELINE config 4), one process per GPU:
 
     python tools/train_example.py --root /path/to/kitti360_nvsf --sequence 1908 [--dynamic] [--epochs 6] [--plain]
-                                  [--export-mesh out.ply --mesh-res 256 256 256 --mesh-threshold 10]
+                                  [--export-mesh out.ply --mesh-res 256 256 256 --mesh-threshold 10] [--dynamic --flow-loss]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 tools/train_example.py ...
 
 Data: the reference's on-disk formats (transforms_{seq}_{split}.json + range-image .npy + images; nvsf/nerf/dataset/formats.py).
@@ -12,6 +12,8 @@ all-reduce of the gradients, then Adam under the loss scaler (nvsf/nerf/train_st
 patches from the error map and adds the structural regularisation, every step writes its per-ray losses back into the frame's error maps,
 one EMA update per epoch; --plain = random pixels and the default losses only.  Reports loss terms, PSNR, range RMSE, CD / F-score.
 --export-mesh then writes the density field's marching-cubes mesh (nvsf/nerf/mesh.py) at the time of the first evaluation frame.
+--flow-loss (with --dynamic) builds the scene-flow point clouds from the range images before the first epoch (Trainer.process_pointcloud,
+trainer.py:1848-1912; here nvsf/nerf/pointcloud.py on the device) and switches the flow term of the loss on.
 """
 import argparse
 import os
@@ -25,10 +27,13 @@ import numpy as np
 import torch
 
 
-def synthetic_dataset(root, seq, n_frames=8, H=376, W=1408, Hl=66, Wl=1030, seed=0):  # KITTI-360's image / range-image sizes
-    """A box-shaped toy scene in the reference's formats: constant-colour images, a range image of a sphere of radius 30 m."""
+def synthetic_dataset(root, seq, n_frames=8, H=376, W=1408, Hl=66, Wl=1030, seed=0, street=False):  # KITTI-360's image / range-image sizes
+    """A box-shaped toy scene in the reference's formats: constant-colour images, a range image of a sphere of radius 30 m.
+    `street` (--flow-loss): the range images show a ground plane and boxes instead, one of which moves 1 m per frame."""
+    from nvsf import synthetic as S
     from nvsf.nerf.dataset import formats as F
     rng = np.random.default_rng(seed)
+    boxes = S.street_range_image(np.random.default_rng(seed), hw=(Hl, Wl))[1] if street else None
     d = os.path.join(root, "train", seq)
     os.makedirs(d, exist_ok=True)
     frames = []
@@ -40,6 +45,10 @@ def synthetic_dataset(root, seq, n_frames=8, H=376, W=1408, Hl=66, Wl=1030, seed
         pc[..., 1] = rng.random((Hl, Wl)) * 0.5
         pc[..., 2] = 30.0
         pc[rng.random((Hl, Wl)) < 0.1, 2] = 0.0
+        if street:
+            moved = boxes.copy()
+            moved[0, [0, 3]] += 1.0 * i
+            pc[..., 2] = S.street_range_image(rng, boxes=moved, hw=(Hl, Wl))[0]
         np.save(os.path.join(d, f"img_{i:04d}.npy"), img)
         np.save(os.path.join(d, f"pano_{i:04d}.npy"), pc)
         frames.append({"frame_id": 1908 + i, "file_path": f"train/{seq}/img_{i:04d}.npy", "transform_matrix": pose,
@@ -58,11 +67,15 @@ def main():
     ap.add_argument("--num-rays", type=int, default=4096)
     ap.add_argument("--num-steps", type=int, default=768)
     ap.add_argument("--dynamic", action="store_true", help="the reference's space-time model instead of the static hash field")
+    ap.add_argument("--flow-loss", action="store_true", help="scene-flow supervision of the space-time model (needs --dynamic): the frames' "
+                    "LiDAR clouds are cleaned on the device first (nvsf/nerf/pointcloud.py)")
     ap.add_argument("--export-mesh", default=None, metavar="PATH", help="after training, write the density field's mesh as a binary PLY "
                     "(marching cubes on the device, at the time of the first evaluation frame; nvsf/nerf/mesh.py)")
     ap.add_argument("--mesh-res", type=int, nargs=3, default=[256, 256, 256], metavar=("NX", "NY", "NZ"))
     ap.add_argument("--mesh-threshold", type=float, default=10.0, help="density at the surface (inside: sigma >= threshold)")
     args = ap.parse_args()
+    if args.flow_loss and not args.dynamic:
+        ap.error("--flow-loss supervises the flow head of the space-time model: add --dynamic")
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -74,9 +87,9 @@ def main():
     from nvsf.nerf.train_step import RenderTrainStep
     root = args.root
     if root is None:
-        root = os.path.join(tempfile.gettempdir(), "nvsf_synthetic_376x1408")
+        root = os.path.join(tempfile.gettempdir(), "nvsf_synthetic_street_376x1408" if args.flow_loss else "nvsf_synthetic_376x1408")
         if rank == 0:
-            synthetic_dataset(root, args.sequence)
+            synthetic_dataset(root, args.sequence, street=args.flow_loss)
         if world > 1:
             dist.barrier()
     scale = S.SCALE if hasattr(S, "SCALE") else 0.010851959895748291
@@ -92,8 +105,19 @@ def main():
                                   num_frames=data.meta["num_frames"]).to(dev)
     n = len(data)
     per_epoch = max(1, n // world)
+    pc_list = None
+    if args.flow_loss:  # every rank builds every frame's cloud: a step on frame k needs the clouds of k - 1 and k + 1
+        import time
+        from nvsf.nerf.pointcloud import process_pointcloud
+        t0 = time.perf_counter()
+        pc_list, pc_ground = process_pointcloud(FrameSet(root, args.sequence, "train", scale, device=dev, training=False), S.LIDAR_MAX_DEPTH)
+        torch.cuda.synchronize()
+        if rank == 0:
+            print(f"scene-flow point clouds of {len(pc_list)} frames in {time.perf_counter() - t0:.2f} s: "
+                  + "  ".join(f"{k}: {pc_list[k].shape[0]} points / {pc_ground[k].shape[0]} ground" for k in sorted(pc_list)), flush=True)
     trainer = RenderTrainStep(model, iters=args.epochs * per_epoch, num_steps=args.num_steps, scale=scale, grad_loss=not args.plain,
-                              use_error_map=not args.plain, change_patch_size_lidar=(1,) if args.plain else (2, 8))
+                              use_error_map=not args.plain, change_patch_size_lidar=(1,) if args.plain else (2, 8),
+                              flow_loss=args.flow_loss, pc_list=pc_list)
     if not args.plain:
         trainer.attach_error_maps(data)
     it = 0
