@@ -756,6 +756,49 @@ int nvsf_plane_inlier_count(const float* points, uint32_t n, const float* planes
 int nvsf_plane_inlier_mask(const float* points, uint32_t n, const float* planes, uint32_t R, float threshold, float z_max, uint8_t* mask,
                            nvsf_stream_t stream);
 
+/* ---- 10. evaluation meters ------------------------------------------------------------------------------------------------- */
+
+/* The arithmetic of the reference's meter classes over whole frames in device memory; every result stays in a caller-supplied DEVICE
+ * buffer, so a frame's table needs no device -> host copy until the meter is read.  No floating-point atomics: fp64 partial sums go to
+ * `workspace` (8-byte aligned; ws_bytes is checked) and one workgroup folds them in a fixed order -- two runs give the same bits.
+ * pred, truth: fp32, dense.  n = 0 is NVSF_ERR_INVALID_ARG (the reference's mean over nothing has no value to return), n <= 2^30.
+ * Workspace sizes, with g(n) = min(ceil(n / 1024), 2048): stats 64 g(n) bytes, confusion 48 g(n), median 16448, ssim
+ * 8 ceil((W - size + 1) / 32) ceil((H - size + 1) / 16)  (nvsf/nerf/meters.py computes them). */
+
+/* ref: compute_depth_errors / compute_intensity_errors, nvsf/lib/error_matrices.py:193-215, 263-285 (and the sums behind PSNRMeter,
+ * RMSEMeter, MAEMeter, :48-57, 90-103, 139-148).  Both inputs are clamped first as `x[x < lo] = lo; x[x > hi] = hi` (NaN passes
+ * through; lo = -inf, hi = +inf: no clamp), d = t - p is formed in fp32 as numpy does on fp32 arrays, and
+ * out fp64 [6] = sum d^2, sum |d|, min truth, max truth, min pred, max pred (of the clamped values; NaN if the image holds one, as
+ * numpy's), accumulated in fp64.  Two launches. */
+int nvsf_image_error_stats(const float* pred, const float* truth, uint32_t n, float lo, float hi, void* workspace, size_t ws_bytes,
+                           double* out, nvsf_stream_t stream);
+
+/* ref: `np.median(np.abs(gt - pred))`, error_matrices.py:204, 274.  out fp64 [1] = the exact median of the fp32 values |t - p| after
+ * the clamp above: for even n the fp32 mean (a + b) / 2 of the two middle values, NaN if any |t - p| is NaN -- bit for bit what
+ * np.median returns for that float32 array (the fp32 result widened to fp64).  Radix select over the bit patterns (11 + 10 + 10 bits:
+ * seven launches, three reads of the images), LDS histograms, integer atomics only. */
+int nvsf_median_abs_error(const float* pred, const float* truth, uint32_t n, float lo, float hi, void* workspace, size_t ws_bytes,
+                          double* out, nvsf_stream_t stream);
+
+/* ref: skimage.metrics.structural_similarity as called at error_matrices.py:209-211, 279-281 (window 0, size 7, sample_cov 1) and
+ * torchmetrics' structural_similarity_index_measure at :458 (window 1, size 11, sigma 1.5, sample_cov 0).  pred, truth [H, W, C] fp32,
+ * channels interleaved, C in {1, 3}; window 0 = uniform, 1 = Gaussian exp(-(d / sigma)^2 / 2) normalised to sum 1 (formed in double by
+ * this entry); size odd, 3 <= size <= 11 <= H, W <= 32768.  Per pixel and channel, from the windowed means E[.] in fp64:
+ *   vp = k (E[pp] - E[p]^2), vt, vpt likewise, k = size^2 / (size^2 - 1) if sample_cov else 1; C1 = (0.01 R)^2, C2 = (0.03 R)^2;
+ *   S = (2 E[p] E[t] + C1) (2 vpt + C2) / ((E[p]^2 + E[t]^2 + C1) (vp + vt + C2)),
+ * no clamp of the variances.  out fp64 [1] = mean of S over the (H - size + 1) x (W - size + 1) pixels whose whole window lies inside
+ * the image, all channels (the region both libraries crop to).  R is READ ON THE DEVICE from range_ptr (fp64 [1]) when the kernel
+ * runs: the caller derives it from the buffer nvsf_image_error_stats filled, on the same stream, without a host round trip.
+ * Two launches. */
+int nvsf_ssim_mean(const float* pred, const float* truth, uint32_t H, uint32_t W, uint32_t C, int window, uint32_t size, float sigma,
+                   int sample_cov, const double* range_ptr, void* workspace, size_t ws_bytes, double* out, nvsf_stream_t stream);
+
+/* ref: RaydropMeter.update, error_matrices.py:384-395.  With m = (pred > ratio):  out uint64 [5] = TP (truth == 1 and m), FP (truth == 0
+ * and m), TN (truth == 0 and not m), FN (truth == 1 and not m), equal (m == truth); out[5] holds the bits of the fp64 sum of d^2,
+ * d = t - p in fp32.  A truth value that is neither 0 nor 1 counts toward `equal` (never) and the sum only, as there.  Two launches. */
+int nvsf_raydrop_confusion(const float* pred, const float* truth, uint32_t n, float ratio, void* workspace, size_t ws_bytes,
+                           uint64_t* out, nvsf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,11 @@ SIGNATURES = {
     "nvsf_knn_mean_distance": [_P, _U, _U, _P],
     "nvsf_plane_inlier_count": [_P, _U, _P, _U, _F, _P],
     "nvsf_plane_inlier_mask": [_P, _U, _P, _U, _F, _F, _P],
+    # section 10: evaluation meters
+    "nvsf_image_error_stats": [_P, _P, _U, _F, _F, _P, ctypes.c_size_t, _P],
+    "nvsf_median_abs_error": [_P, _P, _U, _F, _F, _P, ctypes.c_size_t, _P],
+    "nvsf_ssim_mean": [_P, _P, _U, _U, _U, _I, _U, _F, _I, _P, _P, ctypes.c_size_t, _P],
+    "nvsf_raydrop_confusion": [_P, _P, _U, _F, _P, ctypes.c_size_t, _P],
 }
 
 _lib = None

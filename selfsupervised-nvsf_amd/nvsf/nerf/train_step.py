@@ -806,7 +806,7 @@ def eval_step(model, data, num_steps, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, al
     return out
 
 
-def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="rays", **eval_kwargs):
+def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="rays", meters=None, intensity_inv_scale=1, **eval_kwargs):
     """The metric half of the reference's evaluate_one_epoch (trainer.py:1458-1560) over a FrameSet opened with training=False:
     per frame eval_step, then the two quality metrics of the headline benchmark -- PSNR of the image (error_matrices.py:48-57), range
     RMSE in metres (:263-285) -- and chamfer distance / F-score of the range image's point cloud (PointsMeter, :299-356, on
@@ -819,11 +819,18 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
       "frames" the reference's scheme (trainer.py:1495-1524): rank r evaluates frames r, r + W, ... on its own and the per-rank SUMS
                of loss and metrics go through ONE all-reduce (frame_shard.allreduce_sums = the `dist.all_reduce(loss)` of
                trainer.py:1508, widened to the metrics); no per-pixel data crosses xGMI.
-    Every rank returns the same numbers.  The reference's other meters (ray-drop accuracy / F1, intensity MAE, SSIM, LPIPS: SURVEY 2
-    #18) are outside this package's scope; nvsf/nerf/meters_extra.py restates two of them for users who want them beside these."""
+    Every rank returns the same numbers.  `meters="table"` adds the rest of the reference's evaluation table, computed on
+    the device by nvsf/nerf/meters.py from the same eval_step tensors, fed as evaluate_one_epoch feeds its own (trainer.py:1537-1584):
+    "depth" and "intensity" = [RMSE, MedAE, LPIPS, SSIM, PSNR] (DepthMeter_L4D(frames.scale), IntensityMeter_L4D(intensity_inv_scale,
+    the reference's --intensity_inv_scale, default 1); the LPIPS slot is NaN: no weights here), "raydrop" = [RMSE, accuracy, F1]
+    (RaydropMeter at `raydrop_thres`), "rgb_ssim" (SSIMMeter) and "rgb_rmse" (RMSE of the rendered against the measured image);
+    frame means, the per-frame values riding in the same all-reduce under shard="frames".  The default (None) returns exactly the six
+    keys above from the same code path as before."""
     from nvsf import frame_shard
     if shard not in ("rays", "frames"):
         raise ValueError("shard: 'rays' or 'frames'")
+    if meters not in (None, "table"):
+        raise ValueError("meters: None or 'table'")
     rank, ws = frame_shard.world()
     was_training = model.training
     model.eval()
@@ -833,6 +840,10 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
     try:
         points = PointsMeter(frames.scale, frames.intrinsics_lidar, frames.intrinsics_hoz_lidar)
         ps, rm, ls = [], [], []
+        table = None
+        if meters == "table":
+            from nvsf.nerf import meters as M
+            table = M.table_meters(frames.scale, intensity_inv_scale, eval_kwargs.get("raydrop_thres", 0.5))
         todo = list(range(len(frames)) if indices is None else indices)
         if shard == "frames" and ws > 1:
             todo = todo[rank::ws]
@@ -841,6 +852,8 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
             ps.append(psnr(e["pred_rgb"], e["gt_rgb"]))
             rm.append(depth_rmse(e["pred_depth"], e["gt_depth"], frames.scale))
             points.update(e["pred_depth"], e["gt_depth"])
+            if table is not None:
+                M.update_table(table, e)  # launches only; read once, after the last frame
             ls.append(float(e["loss"]))
     finally:
         if ema is not None:
@@ -848,8 +861,17 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
         model.train(was_training)
     cdf = np.array(points.V, dtype=np.float64).reshape(-1, 2).sum(0)
     sums = [float(np.sum(ls)), float(np.sum(ps)), float(np.sum(rm)), float(cdf[0]), float(cdf[1]), float(len(ps))]
+    if table is not None:  # per-frame values -> sums over this rank's frames, behind the six sums above
+        cols = [table["depth"].frame_values().reshape(-1, 5), table["intensity"].frame_values().reshape(-1, 5),
+                table["raydrop"].frame_values().reshape(-1, 3), table["ssim"].frame_values().reshape(-1, 1),
+                table["rmse"].frame_values().reshape(-1, 1)]
+        sums += [float(v) for v in np.concatenate(cols, axis=1).sum(0)]
     if shard == "frames":
         sums = frame_shard.allreduce_sums(sums, device=next(model.parameters()).device)
     n = max(sums[5], 1.0)
-    return {"loss": sums[0] / n, "psnr": sums[1] / n, "depth_rmse_m": sums[2] / n, "chamfer_distance": sums[3] / n, "f_score": sums[4] / n,
-            "frames": int(sums[5])}
+    res = {"loss": sums[0] / n, "psnr": sums[1] / n, "depth_rmse_m": sums[2] / n, "chamfer_distance": sums[3] / n, "f_score": sums[4] / n,
+           "frames": int(sums[5])}
+    if table is not None:
+        t = [v / n for v in sums[6:]]
+        res.update(depth=t[0:5], intensity=t[5:10], raydrop=t[10:13], rgb_ssim=t[13], rgb_rmse=t[14])
+    return res

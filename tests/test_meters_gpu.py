@@ -1,0 +1,346 @@
+"""Device meters (csrc/metrics.hip through nvsf/nerf/meters.py) against the float64 oracles of tests/test_meters_cpu.py.
+
+Bars: the median is bit-equal to np.median of the float32 abs-error array; confusion counts are equal to numpy's; sums and SSIM means
+agree with the float64 oracle to 1e-9 relative -- fp64 sums of at most 4.5 M terms in a fixed tree and 121-term windows leave about
+1e-13, and the division by (v_p + v_t + C2) amplifies a moment's rounding by at most about 1 / C2 ~ 1e3 at R = 1; two runs of every
+entry give the same bits; degenerate frames (constant images: R = 0; a frame without a single return) return the oracle's IEEE
+results, NaN and inf included, without a fault; bad arguments are rejected before anything is launched."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "selfsupervised-nvsf_amd"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import test_meters_cpu as O  # noqa: E402  (oracles and seeded inputs)
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-9
+INF = float("inf")
+
+
+def _dev(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _bits32(x):
+    return np.asarray(x, dtype=np.float32).reshape(1).view(np.uint32)[0]
+
+
+def _rel(got, want):
+    return abs(got - want) / abs(want) if want != 0 else abs(got)
+
+
+def _median_cases():
+    rng = np.random.default_rng(11)
+    cases = []
+    p, t = O.lidar_pair(0)
+    cases.append(("lidar frame, clamp [1e-6, 80]", p, t, 1e-6, 80.0))
+    cases.append(("lidar frame, no clamp", p, t, -INF, INF))
+    p3, t3 = O.lidar_pair(0, drop=0.3)
+    cases.append(("lidar frame with 30 % of the rays dropped, clamp [1e-6, 80]", p3, t3, 1e-6, 80.0))
+    cp, ct = O.camera_pair(0)
+    cases.append(("camera frame (even n = 1588224)", cp, ct, -INF, INF))
+    cases.append(("camera frame minus one value (odd n)", cp.reshape(-1)[:-1], ct.reshape(-1)[:-1], -INF, INF))
+    for n in (1, 2, 3, 4, 255, 256, 1000, 1001, 4097):
+        a, b = rng.random(n).astype(np.float32), rng.random(n).astype(np.float32)
+        cases.append((f"n = {n}", a, b, -INF, INF))
+    ties = rng.integers(0, 4, 5000).astype(np.float32)
+    cases.append(("four distinct values", ties, np.zeros_like(ties), -INF, INF))
+    cases.append(("all equal", np.full(777, 0.3, np.float32), np.full(777, 0.1, np.float32), -INF, INF))
+    big = rng.random(1000).astype(np.float32)
+    big[:600] = np.inf
+    cases.append(("median at +inf", big, np.zeros_like(big), -INF, INF))
+    cases.append(("two values whose sum overflows", np.array([3e38, 3.2e38], np.float32), np.zeros(2, np.float32), -INF, INF))
+    nan = rng.random(1001).astype(np.float32)
+    nan[17] = np.nan
+    cases.append(("one NaN", nan, np.zeros_like(nan), -INF, INF))
+    cases.append(("denormals and zeros", (rng.integers(0, 3, 2000) * 1e-45).astype(np.float32), np.zeros(2000, np.float32), -INF, INF))
+    return cases
+
+
+def test_median_is_bit_equal_to_numpy(dev):
+    from nvsf.nerf import meters as M
+    for name, p, t, lo, hi in _median_cases():
+        with np.errstate(over="ignore", invalid="ignore"):
+            want = np.float32(O.median_oracle(p, t, lo, hi))
+        got = np.float32(M.median_abs_error(_dev(p, dev), _dev(t, dev), lo, hi).cpu().numpy()[0])
+        print(f"median {name}: {got!r} (numpy {want!r})")
+        if np.isnan(want):
+            assert np.isnan(got), name
+        else:
+            assert _bits32(got) == _bits32(want), (name, got, want)
+    for drop, least in ((0.1, 0.15), (0.3, 0.3)):  # the inputs do hold the long runs of ties they are there for
+        p, t = O.lidar_pair(0, drop=drop)
+        zeros = float((np.abs(O.clamp_ref(t, 1e-6, 80) - O.clamp_ref(p, 1e-6, 80)) == 0).mean())
+        print(f"exact zeros among the abs errors of the lidar frame at drop {drop}: {zeros:.3f}")
+        assert zeros > least
+
+
+def test_confusion_counts_equal_numpy(dev):
+    from nvsf.nerf import meters as M
+    rng = np.random.default_rng(12)
+    _, truth_range = O.lidar_pair(1)
+    truth = (truth_range > 0).astype(np.float32)
+    pred = np.clip(truth * 0.8 + rng.normal(0.1, 0.25, truth.shape), 0, 1).astype(np.float32)
+    odd = truth.copy().reshape(-1)
+    odd[::97] = 0.5   # neither 0 nor 1: counts toward `equal` (never equal) and the sum only
+    odd[5] = np.nan
+    worst = 0.0
+    for name, p, t, ratio in (("frame", pred, truth, 0.5), ("ratio 0.3", pred, truth, 0.3), ("soft truth", pred.reshape(-1), odd, 0.5),
+                              ("n = 1", pred.reshape(-1)[:1], truth.reshape(-1)[:1], 0.5), ("n = 1025", pred.reshape(-1)[:1025], truth.reshape(-1)[:1025], 0.5)):
+        out = M.raydrop_confusion(_dev(p, dev), _dev(t, dev), ratio)
+        counts, s2 = out[:5].view(torch.int64).cpu().tolist(), float(out[5].cpu())
+        want_counts, want_s2 = O.confusion_oracle(p, t, ratio)
+        assert counts == want_counts, (name, counts, want_counts)
+        if np.isnan(want_s2):
+            assert np.isnan(s2)
+        else:
+            worst = max(worst, _rel(s2, want_s2))
+    print(f"confusion: max rel error of sum d^2 = {worst:.3e}")
+    assert worst <= RTOL
+
+
+def _ssim_cases():
+    rng = np.random.default_rng(13)
+    cases = []
+    p, t = O.lidar_pair(0)
+    cases.append(("lidar 66 x 1030 x 1", O.clamp_ref(p, 1e-6, 80), O.clamp_ref(t, 1e-6, 80)))
+    cp, ct = O.camera_pair(0)
+    cases.append(("camera 376 x 1408 x 3", cp, ct))
+    for shape in ((7, 7), (11, 11), (11, 13, 3), (37, 45, 3), (50, 33), (16, 32), (17, 33, 3), (26, 42, 3), (43, 75)):
+        t2 = rng.random(shape).astype(np.float32)
+        cases.append((f"random {shape}", np.clip(t2 + rng.normal(0, 0.1, shape), 0, 1).astype(np.float32), t2))
+    return cases
+
+
+def test_sums_and_ssim_means_against_the_fp64_oracle(dev):
+    from nvsf.nerf import meters as M
+    worst_stats, worst_ssim = 0.0, 0.0
+    for name, p, t in _ssim_cases():
+        for lo, hi in ((-INF, INF), (0.25, 0.75)):
+            got = M.image_error_stats(_dev(p, dev), _dev(t, dev), lo, hi).cpu().numpy()
+            want = O.stats_oracle(p, t, lo, hi)
+            assert np.array_equal(got[2:], want[2:]), (name, got, want)  # extrema: exact
+            worst_stats = max(worst_stats, _rel(got[0], want[0]), _rel(got[1], want[1]))
+        s = O.stats_oracle(p, t)
+        for window, size, sample_cov, R in ((O.UNIFORM, 7, True, s[3] - s[2]), (O.GAUSSIAN, 11, False, max(s[5] - s[4], s[3] - s[2])),
+                                            (O.UNIFORM, 3, False, 1.0), (O.GAUSSIAN, 5, True, 1.0), (O.GAUSSIAN, 9, False, 255.0)):
+            if min(p.shape[:2]) < size:
+                continue
+            r = torch.tensor([R], dtype=torch.float64, device=dev)
+            got = float(M.ssim_mean(_dev(p, dev), _dev(t, dev), r, window, size, 1.5, sample_cov).cpu())
+            want = O.ssim_oracle(p, t, R, window, size, 1.5, sample_cov)
+            e = _rel(got, want)
+            print(f"ssim {name} window {window} size {size}: {got:.15f} oracle {want:.15f} rel {e:.2e}")
+            worst_ssim = max(worst_ssim, e)
+    print(f"max rel error: sums {worst_stats:.3e}, SSIM means {worst_ssim:.3e}")
+    assert worst_stats <= RTOL and worst_ssim <= RTOL
+
+
+def test_identical_images_give_exactly_one(dev):
+    from nvsf.nerf import meters as M
+    _, t = O.camera_pair(2, 64, 96)
+    one = torch.ones(1, dtype=torch.float64, device=dev)
+    assert float(M.ssim_mean(_dev(t, dev), _dev(t, dev), one, O.GAUSSIAN, 11, 1.5, False).cpu()) == 1.0
+    assert float(M.ssim_mean(_dev(t[..., 0], dev), _dev(t[..., 0], dev), one, O.UNIFORM, 7, 1.5, True).cpu()) == 1.0
+
+
+def test_two_runs_give_the_same_bits(dev):
+    from nvsf.nerf import meters as M
+    p, t = O.lidar_pair(3)
+    cp, ct = O.camera_pair(3)
+    dp, dt, dcp, dct = (_dev(a, dev) for a in (p, t, cp, ct))
+    one = torch.ones(1, dtype=torch.float64, device=dev)
+    entries = {
+        "stats lidar": lambda: M.image_error_stats(dp, dt, 1e-6, 80.0),
+        "stats camera": lambda: M.image_error_stats(dcp, dct),
+        "median lidar": lambda: M.median_abs_error(dp, dt, 1e-6, 80.0),
+        "median camera": lambda: M.median_abs_error(dcp, dct),
+        "ssim lidar": lambda: M.ssim_mean(dp, dt, one, O.UNIFORM, 7, 1.5, True),
+        "ssim camera": lambda: M.ssim_mean(dcp, dct, one, O.GAUSSIAN, 11, 1.5, False),
+        "confusion": lambda: M.raydrop_confusion((dp > 0).float() * 0.7, (dt > 0).float(), 0.5),
+    }
+    for name, fn in entries.items():
+        a, b = fn().view(torch.int64).cpu(), fn().view(torch.int64).cpu()
+        assert torch.equal(a, b), name
+
+
+def _l4d_oracle(p, t, hi):
+    """[RMSE, MedAE, LPIPS, SSIM, PSNR] of already scaled and clamped float32 images, in the oracle's IEEE arithmetic."""
+    s = O.stats_oracle(p, t)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mse = s[0] / p.size
+        ssim = O.ssim_oracle(p, t, s[3] - s[2], O.UNIFORM, 7, sample_cov=True)
+        return np.array([np.sqrt(mse), np.float32(O.median_oracle(p, t)), np.nan, ssim, 10 * np.log10(np.float64(hi) ** 2 / mse)])
+
+
+def test_meter_rows_of_real_and_degenerate_frames(dev):
+    from nvsf import synthetic as S
+    from nvsf.nerf import meters as M
+    scale = S.SCALE
+    p, t = O.lidar_pair(4)
+    frames = {
+        "street frame": (p * np.float32(scale), t * np.float32(scale)),
+        "constant pair (R = 0)": (np.full((66, 1030), 0.25, np.float32), np.full((66, 1030), 0.75, np.float32)),
+        "identical constants": (np.full((20, 40), 0.5, np.float32), np.full((20, 40), 0.5, np.float32)),
+        "no return in either image": (np.zeros((66, 1030), np.float32), np.zeros((66, 1030), np.float32)),
+    }
+    for name, (a, b) in frames.items():
+        for cls, sc, lo, hi in ((M.DepthMeter_L4D, scale, 1e-6, 80.0), (M.IntensityMeter_L4D, 1, 1e-6, 1.0)):
+            da, db = _dev(a, dev)[None], _dev(b, dev)[None]
+            meter = cls(sc)
+            meter.update(da, db)
+            got = meter.measure()
+            ha, hb = ((x[0] / sc).clamp(lo, hi).cpu().numpy() for x in (da, db))  # the meter's own torch preprocessing, then the oracle
+            want = _l4d_oracle(ha, hb, hi)
+            print(f"{cls.__name__} {name}: {got} oracle {want}")
+            assert got.shape == (5,) and np.isnan(got[2])
+            np.testing.assert_allclose(got, want, rtol=RTOL, atol=0, equal_nan=True, err_msg=f"{cls.__name__} {name}")
+            assert got[1] == want[1]  # the median: exact
+            if "street" not in name:
+                assert np.isnan(got[3]) and np.isnan(want[3])  # R = 0 and no variance: 0 / 0
+    # ray-drop: a frame without a single return
+    drop = M.RaydropMeter(0.5)
+    drop.update(torch.full((1, 66, 1030), 0.125, device=dev), torch.zeros(1, 66, 1030, device=dev))
+    got = drop.measure()
+    assert got[0] == pytest.approx(0.125, rel=RTOL) and got[1] == 1.0 and np.isnan(got[2])  # TP = FP = FN = 0: 0 / 0
+    drop.clear()
+    drop.update(torch.full((1, 66, 1030), 0.75, device=dev), torch.zeros(1, 66, 1030, device=dev))
+    got = drop.measure()
+    assert got[1] == 0.0 and np.isnan(got[2])  # precision 0, recall 0 / 0
+    # camera meters on a constant pair: the Gaussian window's weights sum to 1 only to rounding, so with R = 0 every implementation
+    # divides rounding noise by rounding noise; what is pinned is that the row comes back and NaN counts as 0
+    ssim = M.SSIMMeter()
+    ssim.update(torch.full((1, 32, 48, 3), 0.5, device=dev), torch.full((1, 32, 48, 3), 0.5, device=dev))
+    assert np.isfinite(ssim.measure())
+    # several frames: one read, frame means
+    cp, ct = O.camera_pair(5, 48, 80)
+    psnr, rmse, mae, ssim = M.PSNRMeter(), M.RMSEMeter(), M.MAEMeter(2.0), M.SSIMMeter()
+    want = {"psnr": [], "rmse": [], "mae": [], "ssim": []}
+    for k in range(3):
+        a, b = np.clip(cp + np.float32(0.01 * k), 0, 1), ct
+        for m in (psnr, rmse, mae, ssim):
+            m.update(_dev(a, dev)[None], _dev(b, dev)[None])
+        s = O.stats_oracle(a, b)
+        want["psnr"].append(-10 * np.log10(s[0] / a.size + 1e-8))
+        want["rmse"].append(np.sqrt(s[0] / a.size))
+        want["mae"].append(O.stats_oracle(a * np.float32(2), b * np.float32(2))[1] / a.size)
+        want["ssim"].append(O.ssim_oracle(a, b, max(s[5] - s[4], s[3] - s[2]), O.GAUSSIAN, 11, 1.5))
+    for m, key in ((psnr, "psnr"), (rmse, "rmse"), (mae, "mae"), (ssim, "ssim")):
+        assert m.N == 3 and m.measure() == pytest.approx(np.sum(want[key]) / (3 + 1e-8), rel=RTOL), key
+    capped = M.RMSEMeter(rgb_metric=True)
+    a = np.array([[0.0, 50.0, 100.0, 70.0]], np.float32)
+    b = np.array([[10.0, 0.0, 90.0, 60.0]], np.float32)
+    capped.update(_dev(b, dev), _dev(a, dev))  # preds b zeroed where the truth a is 0, both capped at 80
+    assert capped.measure() == pytest.approx(np.sqrt((0 + 50.0 ** 2 + 0 + 100.0) / 4) / (1 + 1e-8), rel=1e-9)
+    assert capped.report().startswith("RMSE = ")
+    # the LPIPS slot: a callable is called on the clamped images with normalize=True and its value lands in the row
+    seen = {}
+
+    def fake_lpips(x, y, normalize=False):
+        seen.update(shape=tuple(x.shape), normalize=normalize, lo=float(x.min()))
+        return (x - y).abs().mean()
+    withl = M.DepthMeter_L4D(scale, lpips_fn=fake_lpips)
+    withl.update(_dev(p * np.float32(scale), dev)[None], _dev(t * np.float32(scale), dev)[None])
+    assert seen["shape"] == (66, 1030) and seen["normalize"] is True and seen["lo"] >= 1e-6 * 0.999
+    assert withl.measure()[2] > 0
+
+
+def test_wrong_dtype_raises_before_any_launch(dev):
+    from nvsf.nerf import meters as M
+    a = torch.rand(1, 16, 24, device=dev)
+    for bad in (a.double(), a.half()):
+        with pytest.raises(ValueError, match="float32"):
+            M.DepthMeter_L4D(1.0).update(bad, bad)
+    with pytest.raises(ValueError):
+        M.PSNRMeter().update(a, a[:, :8])
+    with pytest.raises(ValueError):
+        M.ssim_mean(a[0, :5], a[0, :5], torch.ones(1, dtype=torch.float64, device=dev))  # H < size
+
+
+def test_invalid_arguments_are_rejected_without_a_launch(dev, hip_lib):
+    from nvsf.nerf import meters as M
+    H, W = 24, 40
+    img = torch.rand(H, W, 3, device=dev)
+    r = torch.ones(1, dtype=torch.float64, device=dev)
+    ws = torch.zeros(4096, dtype=torch.float64, device=dev)
+    out = torch.full((8,), -7.0, dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    P = lambda x: x.data_ptr()
+
+    def ssim(H=H, W=W, C=3, window=1, size=11, sigma=1.5, cov=0, ws_bytes=None):
+        nbytes = M.ssim_ws_bytes(H, W, size) if ws_bytes is None else ws_bytes
+        return hip_lib.nvsf_ssim_mean(P(img), P(img), H, W, C, window, size, sigma, cov, P(r), P(ws), nbytes, P(out), stream)
+    assert ssim() == 0
+    torch.cuda.synchronize()
+    assert float(out[0]) == 1.0
+    out.fill_(-7.0)
+    ws.fill_(-7.0)
+    assert ssim(size=8) == -1 and ssim(size=13) == -1 and ssim(size=1) == -1        # even, > 11, < 3
+    assert ssim(H=10, W=36) == -1 and ssim(H=36, W=10) == -1                        # H < size, W < size
+    assert ssim(C=2) == -1 and ssim(C=4) == -1 and ssim(window=2) == -1 and ssim(cov=2) == -1
+    assert ssim(ws_bytes=M.ssim_ws_bytes(H, W, 11) - 8) == -1 and ssim(sigma=0.0) == -1
+    n = img.numel()
+    assert hip_lib.nvsf_image_error_stats(P(img), P(img), n, 0.0, 1.0, P(ws), M.stats_ws_bytes(n) - 1, P(out), stream) == -1
+    assert hip_lib.nvsf_image_error_stats(P(img), P(img), 0, 0.0, 1.0, P(ws), 4096, P(out), stream) == -1
+    assert hip_lib.nvsf_image_error_stats(P(img), P(img), n, 1.0, 0.0, P(ws), 4096, P(out), stream) == -1  # lo > hi
+    assert hip_lib.nvsf_median_abs_error(P(img), P(img), 0, 0.0, 1.0, P(ws), M.MEDIAN_WS_BYTES, P(out), stream) == -1  # n = 0
+    assert hip_lib.nvsf_median_abs_error(P(img), P(img), n, 0.0, 1.0, P(ws), M.MEDIAN_WS_BYTES - 4, P(out), stream) == -1
+    assert hip_lib.nvsf_raydrop_confusion(P(img), P(img), n, 0.5, P(ws), M.confusion_ws_bytes(n) - 1, P(out), stream) == -1
+    assert hip_lib.nvsf_raydrop_confusion(P(img), None, n, 0.5, P(ws), 4096, P(out), stream) == -1
+    torch.cuda.synchronize()
+    assert bool((out == -7.0).all()) and bool((ws == -7.0).all())  # nothing ran
+
+
+def test_evaluate_frames_table(tmp_path):
+    """evaluate_frames(meters="table") on a small scene: the new keys are the meters fed by hand from eval_step's tensors, the old
+    keys are those of meters=None, and the reference's per-rank-frames scheme gives the same table."""
+    from test_formats_cpu import make_dataset
+    from nvsf.nerf.dataset import formats as F
+    from nvsf.nerf.models.network_static import NeRFNetworkStatic
+    from nvsf.nerf.train_step import eval_step, evaluate_frames
+    from nvsf.nerf import meters as M
+    dev = torch.device("cuda:0")
+    seq, frames, images, pcs, K = make_dataset(str(tmp_path), n_frames=2, H=24, W=32, Hl=16, Wl=64)
+    scale = 0.0108
+    fe = F.FrameSet(str(tmp_path), seq, "train", scale, device=dev, training=False)
+    torch.manual_seed(1)
+    m = NeRFNetworkStatic(bound=2.0, min_near=0.01, min_near_lidar=0.01, lidar_max_depth=0.9).to(dev)
+    with torch.no_grad():
+        for p in m.parameters():
+            if p.dim() == 1 and p.numel() > 10000:
+                p.normal_(0, 0.3)
+    thres = float(eval_step(m, fe.collate([1]), 48)["pred_raydrop"].median())
+    old = evaluate_frames(m, fe, 48, raydrop_thres=thres)
+    res = evaluate_frames(m, fe, 48, raydrop_thres=thres, meters="table", intensity_inv_scale=2)
+    assert set(old) == {"loss", "psnr", "depth_rmse_m", "chamfer_distance", "f_score", "frames"}
+    assert set(res) == set(old) | {"depth", "intensity", "raydrop", "rgb_ssim", "rgb_rmse"}
+    for k in old:
+        assert res[k] == old[k] or (np.isnan(res[k]) and np.isnan(old[k])), k  # the same code path: float equality
+    assert len(res["depth"]) == 5 and len(res["intensity"]) == 5 and len(res["raydrop"]) == 3
+    hand = M.table_meters(scale, 2, thres)
+    for i in range(2):
+        M.update_table(hand, eval_step(m, fe.collate([i]), 48, raydrop_thres=thres))
+    near = lambda a, b: np.testing.assert_allclose(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), rtol=1e-12, atol=0, equal_nan=True)
+    near(res["depth"], hand["depth"].measure())
+    near(res["intensity"], hand["intensity"].measure())
+    near(res["raydrop"], hand["raydrop"].measure())
+    near(res["rgb_ssim"], hand["ssim"].frame_values().mean())
+    near(res["rgb_rmse"], hand["rmse"].frame_values().mean())
+    assert hand["psnr"].measure() == pytest.approx(res["psnr"], rel=1e-6)  # the device PSNR meter against the host path's
+    assert hand["depth"].measure()[0] == pytest.approx(res["depth_rmse_m"], rel=1e-5)  # fp32 division by the scale vs float64
+    assert np.isnan(res["depth"][2]) and np.isfinite(res["depth"][0]) and 0 <= res["raydrop"][1] <= 1
+    by_frames = evaluate_frames(m, fe, 48, raydrop_thres=thres, meters="table", intensity_inv_scale=2, shard="frames")
+    assert by_frames.keys() == res.keys()
+    for k in res:
+        near(by_frames[k], res[k])
+    lines = M.table_report(res)
+    assert lines[1].startswith("Depth_error (RMSE, MedAE, LPIPS, SSIM, PNSR) = [") and len(lines) == 7
+    with pytest.raises(ValueError):
+        evaluate_frames(m, fe, 48, meters="all")

@@ -2,6 +2,7 @@
 
     python tools/train_example.py --root /path/to/kitti360_nvsf --sequence 1908 [--dynamic] [--epochs 6] [--plain]
                                   [--export-mesh out.ply --mesh-res 256 256 256 --mesh-threshold 10] [--dynamic --flow-loss]
+                                  [--eval-table]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 tools/train_example.py ...
 
 Data: the reference's on-disk formats (transforms_{seq}_{split}.json + range-image .npy + images; nvsf/nerf/dataset/formats.py).
@@ -14,6 +15,8 @@ one EMA update per epoch; --plain = random pixels and the default losses only.  
 --export-mesh then writes the density field's marching-cubes mesh (nvsf/nerf/mesh.py) at the time of the first evaluation frame.
 --flow-loss (with --dynamic) builds the scene-flow point clouds from the range images before the first epoch (Trainer.process_pointcloud,
 trainer.py:1848-1912; here nvsf/nerf/pointcloud.py on the device) and switches the flow term of the loss on.
+--eval-table also prints the report lines of the reference's evaluation table (trainer.py:1794-1827): range and intensity RMSE / MedAE /
+LPIPS / SSIM / PSNR, ray-drop RMSE / accuracy / F1, camera PSNR / RMSE / SSIM, computed on the device (nvsf/nerf/meters.py).
 """
 import argparse
 import os
@@ -73,6 +76,8 @@ def main():
                     "(marching cubes on the device, at the time of the first evaluation frame; nvsf/nerf/mesh.py)")
     ap.add_argument("--mesh-res", type=int, nargs=3, default=[256, 256, 256], metavar=("NX", "NY", "NZ"))
     ap.add_argument("--mesh-threshold", type=float, default=10.0, help="density at the surface (inside: sigma >= threshold)")
+    ap.add_argument("--eval-table", action="store_true", help="after training, print the report lines of the reference's evaluation table "
+                    "(device-side meters, nvsf/nerf/meters.py)")
     args = ap.parse_args()
     if args.flow_loss and not args.dynamic:
         ap.error("--flow-loss supervises the flow head of the space-time model: add --dynamic")
@@ -142,10 +147,14 @@ def main():
     # whole-frame evaluation (Trainer.eval_step / evaluate_one_epoch): every frame rendered with the staged loop, its rays split over the ranks
     from nvsf.nerf.train_step import evaluate_frames
     whole = FrameSet(root, args.sequence, "train", scale, device=dev, training=False)
-    res = evaluate_frames(model, whole, args.num_steps, indices=range(min(len(whole), 4)), ema=trainer.ema)
+    res = evaluate_frames(model, whole, args.num_steps, indices=range(min(len(whole), 4)), ema=trainer.ema,
+                          meters="table" if args.eval_table else None)
     if rank == 0:
         print(f"evaluation over {res['frames']} frames: loss {res['loss']:.4f}, PSNR {res['psnr']:.2f} dB, range RMSE {res['depth_rmse_m']:.2f} m, "
               f"chamfer distance {res['chamfer_distance']:.3f}, F-score {res['f_score']:.3f}")
+        if args.eval_table:
+            from nvsf.nerf.meters import table_report
+            print("\n".join(table_report(res)), flush=True)
     if args.export_mesh and rank == 0:
         from nvsf.nerf.mesh import export_mesh_density
         t_first = float(whole.collate([0])["time"].reshape(-1)[0])
