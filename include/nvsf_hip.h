@@ -715,6 +715,23 @@ int nvsf_mse_sum_fwd(const float* a, const float* b, uint32_t n, float alpha, fl
 int nvsf_mse_sum_bwd(const float* a, const float* b, uint32_t n, float alpha, const float* grad_loss, float* grad_a,
                      nvsf_stream_t stream);
 
+/* ref: the two camera terms of Trainer.train_step, trainer.py:491-518 (criteria of main_nvsf.py:205-212), one launch each way.
+ * image, gt_rgb [N, 3], depth [N] (scene units), gt_depth_m [N] (the LiDAR-projected depth map at the rays' pixels, metres; 0 = empty):
+ *   loss_rgb   = sum alpha_rgb (image - gt_rgb)^2
+ *   gt = min(gt_depth_m scale, max_depth), pred = min(depth, max_depth), mask = gt > 0        (the caller passes max_depth = 80 scale)
+ *   loss_depth = sum over ALL N rays of alpha_rd crit(pred mask, gt mask)
+ * criterion 0 L1, 1 MSE, 2 Huber(delta = criterion_param), 3 SmoothL1(beta = criterion_param), 4 BCE-with-logits (logits pred mask,
+ * targets gt mask: every masked ray adds log 2, as in the reference).  Per-ray terms fp32, summed in fp64 in a fixed order (one
+ * workgroup: thread-serial, wave butterfly, waves in order), rounded to fp32 on store; no atomics.
+ * bwd: grad_image = grad_loss_rgb 2 alpha_rgb (image - gt_rgb); grad_depth = grad_loss_depth alpha_rd crit'(pred mask, gt mask), and
+ * exactly 0 where the ray is masked or depth > max_depth (the reference assigns the cap into the tensor).  A null grad_loss_* is 0. */
+int nvsf_camera_loss_fwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N, float alpha_rgb,
+                         float alpha_rd, float scale, float max_depth, int criterion, float criterion_param, float* loss_rgb,
+                         float* loss_depth, nvsf_stream_t stream);
+int nvsf_camera_loss_bwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N, float alpha_rgb,
+                         float alpha_rd, float scale, float max_depth, int criterion, float criterion_param, const float* grad_loss_rgb,
+                         const float* grad_loss_depth, float* grad_image, float* grad_depth, nvsf_stream_t stream);
+
 /* ref: torch_ema.ExponentialMovingAverage.update as used by the Trainer (trainer.py:112-114 construction with decay 0.95,
  * :1420-1421 one update per epoch): shadow -= one_minus_decay * (shadow - param), fp32 [n]. */
 int nvsf_ema_update(float* shadow, const float* param, uint64_t n, float one_minus_decay, nvsf_stream_t stream);
@@ -773,6 +790,11 @@ int nvsf_plane_inlier_mask(const float* points, uint32_t n, const float* planes,
 int nvsf_image_error_stats(const float* pred, const float* truth, uint32_t n, float lo, float hi, void* workspace, size_t ws_bytes,
                            double* out, nvsf_stream_t stream);
 
+/* The same with d = t - p formed in fp64: what numpy computes in RMSEMeter's camera-depth form (error_matrices.py:92-99), where
+ * `preds * zero_mask` has already made the predictions a float64 array. */
+int nvsf_image_error_stats_wide(const float* pred, const float* truth, uint32_t n, float lo, float hi, void* workspace, size_t ws_bytes,
+                                double* out, nvsf_stream_t stream);
+
 /* ref: `np.median(np.abs(gt - pred))`, error_matrices.py:204, 274.  out fp64 [1] = the exact median of the fp32 values |t - p| after
  * the clamp above: for even n the fp32 mean (a + b) / 2 of the two middle values, NaN if any |t - p| is NaN -- bit for bit what
  * np.median returns for that float32 array (the fp32 result widened to fp64).  Radix select over the bit patterns (11 + 10 + 10 bits:
@@ -798,6 +820,30 @@ int nvsf_ssim_mean(const float* pred, const float* truth, uint32_t H, uint32_t W
  * d = t - p in fp32.  A truth value that is neither 0 nor 1 counts toward `equal` (never) and the sum only, as there.  Two launches. */
 int nvsf_raydrop_confusion(const float* pred, const float* truth, uint32_t n, float ratio, void* workspace, size_t ws_bytes,
                            uint64_t* out, nvsf_stream_t stream);
+
+/* ---- 11. LiDAR-projected camera depth maps ------------------------------------------------------------------------------------ */
+
+/* ref: the pseudo ground-truth camera depth image of every frame, nvsf/nerf/dataset/base_dataset.py:153-157 = convert.pano_to_lidar
+ * (nvsf/lib/convert.py:221-291) -> dataset_utils.lidar2points2d (:17-32) -> dataset_utils.get_lidar_depth_image (:69-96).
+ * range_m [F, Hl, Wl] fp32, metres (device); lidar2cam [F, 16] fp32, row-major 4 x 4, formed by the caller as inv(pose) @ pose_lidar in
+ * fp32 (device); K: HOST pointer to 9 doubles, row-major, read before the call returns; out [F, H, W] fp32 (device), every element
+ * written.  One thread per range pixel, the whole split in one call:
+ *   1. fp32, every operation rounded, true divisions (numpy on fp32 arrays): i = column, j = row,
+ *      beta = -(i - Wl / 2) / Wl * fov_hoz / 180 * pi, alpha = (fov_up - j / Hl * fov) / 180 * pi,
+ *      point = (cos alpha cos beta, cos alpha sin beta, sin alpha) * range.  A pixel whose range is exactly 0 gives no point.
+ *   2. fp64: c = [x, y, z, 1] @ lidar2cam^T, q = c @ K^T, z = clip(q2, 1e-5, 99999), u = q0 / z, v = q1 / z; the point is kept iff
+ *      0 <= u < W and 0 <= v < H (a NaN is never inside); its pixel is (int(v), int(u)).
+ *   3. out = the smallest z of the pixel, rounded to fp32; 0 where no point landed.
+ * The minimum is an integer one over the bit patterns of the (positive) fp32 depths: independent of arrival order, two runs give the
+ * same bits.  NaN and +-inf ranges land nowhere.  F, Hl, Wl, H, W >= 1, fov > 0, fov_hoz > 0, F Hl Wl < 2^31, F H W < 2^31.
+ * One memset and one launch. */
+int nvsf_lidar_depth_images(const float* range_m, uint32_t F, uint32_t Hl, uint32_t Wl, float fov_up, float fov, float fov_hoz,
+                            const float* lidar2cam, const double* K, uint32_t H, uint32_t W, float* out, nvsf_stream_t stream);
+
+/* Steps 2 and 3 for a raw cloud: points [P, 3] fp32 in the LiDAR frame (device), ONE lidar2cam (HOST pointer to 16 floats) and K (HOST
+ * pointer to 9 doubles), out [H, W] fp32 (device).  P = 0 gives the empty map. */
+int nvsf_points_depth_image(const float* points, uint32_t P, const float* lidar2cam, const double* K, uint32_t H, uint32_t W, float* out,
+                            nvsf_stream_t stream);
 
 #ifdef __cplusplus
 }

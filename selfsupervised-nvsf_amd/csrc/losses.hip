@@ -295,6 +295,78 @@ __global__ __launch_bounds__(256) void k_lidar_grad_loss_bwd(const float* __rest
     grad_pred[k] = *g_loss * sum / g.scale;
 }
 
+// ---- the two camera terms of a ray batch: trainer.py:491-518 ---------------------------------------------------------------------
+//   L_rgb = sum alpha_rgb (image - gt_rgb)^2 over rays and channels
+//   gt = min(gt_m scale, max_depth), pred = min(depth, max_depth) (a ray the cap changes gets no gradient: the reference assigns into the
+//   tensor), mask = gt > 0, L_depth = sum alpha_rd crit(pred mask, gt mask) over ALL rays (a masked ray gives crit(0, 0): log 2 under
+//   BCE-with-logits).  Per-ray terms are fp32; every thread adds its terms in index order into an fp64 partial, a wave folds its lanes in
+//   a fixed butterfly and thread 0 the 16 wave partials in wave order: no atomic, two runs give the same bits.
+__device__ __forceinline__ float cd_crit(float x, float y, int kind, float param) {
+    if (kind < 4) return sr_crit(x - y, kind, param);
+    return (fmaxf(x, 0.0f) - x * y) + log1pf(expf(-fabsf(x)));  // BCEWithLogitsLoss, logits x, targets y
+}
+__device__ __forceinline__ float cd_crit_grad(float x, float y, int kind, float param) {
+    if (kind < 4) return sr_crit_grad(x - y, kind, param);
+    return 1.0f / (1.0f + expf(-x)) - y;
+}
+struct CamDepth { float x, y, m; bool capped; };  // masked prediction, masked truth, mask, prediction above the cap
+__device__ __forceinline__ CamDepth cam_depth(float depth, float gt_m, float scale, float max_depth) {
+    CamDepth t;
+    float g = gt_m * scale;
+    g = g > max_depth ? max_depth : g;
+    t.capped = depth > max_depth;
+    const float p = t.capped ? max_depth : depth;
+    t.m = g > 0.0f ? 1.0f : 0.0f;
+    t.x = p * t.m;
+    t.y = g * t.m;
+    return t;
+}
+
+__global__ __launch_bounds__(kBlock) void k_camera_loss_fwd(const float* __restrict__ image, const float* __restrict__ gt_rgb,
+                                                            const float* __restrict__ depth, const float* __restrict__ gt_m, uint32_t N,
+                                                            float alpha_rgb, float alpha_rd, float scale, float max_depth, int kind, float param,
+                                                            float* __restrict__ l_rgb, float* __restrict__ l_depth) {
+    __shared__ double part[2][kBlock / kWave];
+    double acc[2] = {0.0, 0.0};
+    for (uint32_t i = threadIdx.x; i < 3 * N; i += kBlock) {
+        const float e = image[i] - gt_rgb[i];
+        acc[0] += (double)(alpha_rgb * (e * e));
+    }
+    for (uint32_t n = threadIdx.x; n < N; n += kBlock) {
+        const CamDepth t = cam_depth(depth[n], gt_m[n], scale, max_depth);
+        acc[1] += (double)(alpha_rd * cd_crit(t.x, t.y, kind, param));
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        acc[k] = wave_sum(acc[k]);
+        if (lane_id() == 0) part[k][threadIdx.x >> 6] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r[2] = {0.0, 0.0};
+        for (int w = 0; w < kBlock / kWave; ++w) { r[0] += part[0][w]; r[1] += part[1][w]; }
+        *l_rgb = (float)r[0];
+        *l_depth = (float)r[1];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_camera_loss_bwd(const float* __restrict__ image, const float* __restrict__ gt_rgb,
+                                                         const float* __restrict__ depth, const float* __restrict__ gt_m, uint32_t N,
+                                                         float alpha_rgb, float alpha_rd, float scale, float max_depth, int kind, float param,
+                                                         const float* __restrict__ g_rgb, const float* __restrict__ g_depth,
+                                                         float* __restrict__ grad_image, float* __restrict__ grad_depth) {
+    const uint32_t n = blockIdx.x * 256u + threadIdx.x;
+    if (n >= N) return;
+    const float gR = g_rgb ? *g_rgb : 0.0f, gD = g_depth ? *g_depth : 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const size_t i = 3 * (size_t)n + k;
+        grad_image[i] = gR * alpha_rgb * 2.0f * (image[i] - gt_rgb[i]);
+    }
+    const CamDepth t = cam_depth(depth[n], gt_m[n], scale, max_depth);
+    grad_depth[n] = (t.capped || t.m == 0.0f) ? 0.0f : gD * alpha_rd * cd_crit_grad(t.x, t.y, kind, param);
+}
+
 // ---- error map of the pixel sampler (trainer.py:552-630) -----------------------------------------------------------------------
 // per-ray LiDAR loss = alpha_d |.| + alpha_r (.)^2 + alpha_i (.)^2 (trainer.py:213-216, reduction "none") / per-ray camera loss =
 // sum over channels of alpha_rgb (.)^2 (trainer.py:598); stats[0 .. 1] = (min, max) over the rays as ordered unsigned bit patterns
@@ -404,6 +476,30 @@ NVSF_API int nvsf_mse_sum_bwd(const float* a, const float* b, uint32_t n, float 
     if (n == 0) return NVSF_OK;
     REQUIRE(a && b && grad_loss && grad_a);
     hipLaunchKernelGGL(k_mse_sum_bwd, dim3(cdiv(n, 256)), dim3(256), 0, stream, a, b, n, alpha, grad_loss, grad_a);
+    return nvsf_launch_status();
+}
+
+NVSF_API int nvsf_camera_loss_fwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N,
+                                  float alpha_rgb, float alpha_rd, float scale, float max_depth, int criterion, float criterion_param,
+                                  float* loss_rgb, float* loss_depth, hipStream_t stream) {
+    REQUIRE(loss_rgb && loss_depth && N <= (1u << 30));
+    REQUIRE(criterion >= 0 && criterion <= 4 && (criterion < 2 || criterion == 4 || criterion_param > 0.0f) && max_depth == max_depth);
+    REQUIRE(N == 0 || (image && gt_rgb && depth && gt_depth_m));
+    hipLaunchKernelGGL(k_camera_loss_fwd, dim3(1), dim3(kBlock), 0, stream, image, gt_rgb, depth, gt_depth_m, N, alpha_rgb, alpha_rd, scale,
+                       max_depth, criterion, criterion_param, loss_rgb, loss_depth);
+    return nvsf_launch_status();
+}
+
+NVSF_API int nvsf_camera_loss_bwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N,
+                                  float alpha_rgb, float alpha_rd, float scale, float max_depth, int criterion, float criterion_param,
+                                  const float* grad_loss_rgb, const float* grad_loss_depth, float* grad_image, float* grad_depth,
+                                  hipStream_t stream) {
+    REQUIRE(N <= (1u << 30));
+    REQUIRE(criterion >= 0 && criterion <= 4 && (criterion < 2 || criterion == 4 || criterion_param > 0.0f) && max_depth == max_depth);
+    if (N == 0) return NVSF_OK;
+    REQUIRE(image && gt_rgb && depth && gt_depth_m && grad_image && grad_depth);
+    hipLaunchKernelGGL(k_camera_loss_bwd, dim3(cdiv(N, 256)), dim3(256), 0, stream, image, gt_rgb, depth, gt_depth_m, N, alpha_rgb, alpha_rd, scale,
+                       max_depth, criterion, criterion_param, grad_loss_rgb, grad_loss_depth, grad_image, grad_depth);
     return nvsf_launch_status();
 }
 

@@ -47,6 +47,8 @@ __device__ __forceinline__ double block_fold(double v, double* sh) {
 }
 
 // ---- image_error_stats ---------------------------------------------------------------------------------------------------------
+// kWide: d = t - p formed in fp64 (numpy, once one operand of the difference is a float64 array: RMSEMeter's camera-depth form)
+template <bool kWide>
 __global__ __launch_bounds__(kBlock) void k_error_stats(const float* __restrict__ pred, const float* __restrict__ truth, uint32_t n, float lo,
                                                         float hi, double* __restrict__ partial) {
     __shared__ double sh[kStatCols][kWaves];
@@ -54,9 +56,9 @@ __global__ __launch_bounds__(kBlock) void k_error_stats(const float* __restrict_
     const uint32_t stride = gridDim.x * kBlock;
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         const float p = clamp_ref(pred[i], lo, hi), t = clamp_ref(truth[i], lo, hi);
-        const float d = t - p;  // fp32, as numpy forms it on the reference's fp32 arrays
-        s2 += (double)d * (double)d;
-        s1 += (double)fabsf(d);
+        const double d = kWide ? (double)t - (double)p : (double)(t - p);  // fp32 difference: as numpy forms it on the reference's fp32 arrays
+        s2 += d * d;
+        s1 += fabs(d);
         tmin = fmin(tmin, (double)t); tmax = fmax(tmax, (double)t);
         pmin = fmin(pmin, (double)p); pmax = fmax(pmax, (double)p);
         nt += t != t ? 1.0 : 0.0;
@@ -345,7 +347,17 @@ NVSF_API int nvsf_image_error_stats(const float* pred, const float* truth, uint3
     REQUIRE(pred && truth && workspace && out && n >= 1 && n <= kMaxElems && !(lo > hi));
     const uint32_t grid = host_streaming_grid(n);
     REQUIRE(ws_bytes >= (size_t)grid * kStatCols * sizeof(double) && ((uintptr_t)workspace & 7) == 0);
-    hipLaunchKernelGGL(k_error_stats, dim3(grid), dim3(kBlock), 0, stream, pred, truth, n, lo, hi, (double*)workspace);
+    hipLaunchKernelGGL(k_error_stats<false>, dim3(grid), dim3(kBlock), 0, stream, pred, truth, n, lo, hi, (double*)workspace);
+    hipLaunchKernelGGL(k_error_stats_fold, dim3(1), dim3(kBlock), 0, stream, (const double*)workspace, grid, out);
+    return nvsf_launch_status();
+}
+
+NVSF_API int nvsf_image_error_stats_wide(const float* pred, const float* truth, uint32_t n, float lo, float hi, void* workspace, size_t ws_bytes,
+                                         double* out, hipStream_t stream) {
+    REQUIRE(pred && truth && workspace && out && n >= 1 && n <= kMaxElems && !(lo > hi));
+    const uint32_t grid = host_streaming_grid(n);
+    REQUIRE(ws_bytes >= (size_t)grid * kStatCols * sizeof(double) && ((uintptr_t)workspace & 7) == 0);
+    hipLaunchKernelGGL(k_error_stats<true>, dim3(grid), dim3(kBlock), 0, stream, pred, truth, n, lo, hi, (double*)workspace);
     hipLaunchKernelGGL(k_error_stats_fold, dim3(1), dim3(kBlock), 0, stream, (const double*)workspace, grid, out);
     return nvsf_launch_status();
 }

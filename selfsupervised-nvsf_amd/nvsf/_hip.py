@@ -80,6 +80,8 @@ SIGNATURES = {
     "nvsf_error_map_update": [_P, _P, _U, _U, _P, _U, _U, _F, _F, _P, _P],
     "nvsf_mse_sum_fwd": [_P, _P, _U, _F, _P],
     "nvsf_mse_sum_bwd": [_P, _P, _U, _F, _P, _P],
+    "nvsf_camera_loss_fwd": [_P, _P, _P, _P, _U, _F, _F, _F, _F, _I, _F, _P, _P],
+    "nvsf_camera_loss_bwd": [_P, _P, _P, _P, _U, _F, _F, _F, _F, _I, _F, _P, _P, _P, _P],
     "nvsf_density_dynamic_f16planes_fwd": [_P, _P, _P, _P, _P, _I, _P, _I, _U, _P, _P, _P, _P, _P],
     "nvsf_density_dynamic_lm_fwd": [_P, _P, _P, _P, _P, _I, _P, _I, _U, _P, _P, _P, _P, _P],
     "nvsf_density_dynamic_lm32_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _U, _P, _P, _P, _P, _P],
@@ -108,9 +110,13 @@ SIGNATURES = {
     "nvsf_plane_inlier_mask": [_P, _U, _P, _U, _F, _F, _P],
     # section 10: evaluation meters
     "nvsf_image_error_stats": [_P, _P, _U, _F, _F, _P, ctypes.c_size_t, _P],
+    "nvsf_image_error_stats_wide": [_P, _P, _U, _F, _F, _P, ctypes.c_size_t, _P],
     "nvsf_median_abs_error": [_P, _P, _U, _F, _F, _P, ctypes.c_size_t, _P],
     "nvsf_ssim_mean": [_P, _P, _U, _U, _U, _I, _U, _F, _I, _P, _P, ctypes.c_size_t, _P],
     "nvsf_raydrop_confusion": [_P, _P, _U, _F, _P, ctypes.c_size_t, _P],
+    # section 11: LiDAR-projected camera depth maps
+    "nvsf_lidar_depth_images": [_P, _U, _U, _U, _F, _F, _F, _P, _P, _U, _U, _P],
+    "nvsf_points_depth_image": [_P, _U, _P, _P, _U, _U, _P],
 }
 
 _lib = None
@@ -196,6 +202,10 @@ def host_f32(values):
 
 def host_u32(values):
     return (ctypes.c_uint32 * len(values))(*[int(v) for v in values])
+
+
+def host_f64(values):
+    return (ctypes.c_double * len(values))(*[float(v) for v in values])
 
 
 def host_i32(values):

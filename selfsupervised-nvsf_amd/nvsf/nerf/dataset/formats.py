@@ -108,8 +108,10 @@ class FrameSet:
 
     def __init__(self, root_path, sequence_id, split, scale, intrinsics_lidar=(2.0, 26.9), intrinsics_hoz_lidar=(180.0, 360.0),
                  num_rays=4096, num_rays_lidar=4096, patch_size=1, patch_size_lidar=1, device="cuda", training=True,
-                 images=None, range_images=None):
-        """images / range_images: optional pre-decoded lists (skips file reads, e.g. synthetic data)."""
+                 images=None, range_images=None, camera_depth=False):
+        """images / range_images: optional pre-decoded lists (skips file reads, e.g. synthetic data).  camera_depth: build
+        `image_depths` [F, H, W], the LiDAR-projected camera depth map of every frame in metres (base_dataset.py:153-157), in one
+        launch (nvsf/nerf/dataset/depth_image.py); `collate` / `train_batch` then carry it."""
         t = load_transforms(transforms_path(root_path, sequence_id, split))
         self.meta, self.device, self.training, self.scale = t, torch.device(device), training, scale
         self.H, self.W, self.H_lidar, self.W_lidar = t["H"], t["W"], t["H_lidar"], t["W_lidar"]
@@ -132,6 +134,12 @@ class FrameSet:
         self.error_map = self.error_map_rgb = None
         self.use_error_map = False  # set per epoch by RenderTrainStep.set_epoch (trainer.py:1056-1059)
         self._em_stats, self._em_owner = {}, {}
+        self.image_depths = None
+        if camera_depth:
+            from nvsf.nerf.dataset import depth_image
+            ranges = torch.from_numpy(np.stack([np.asarray(pc)[:, :, 2] for pc in range_images], 0).astype(np.float32)).to(dev)
+            self.image_depths = depth_image.lidar_depth_images(ranges, self.poses, self.poses_lidar, self.intrinsics, self.H, self.W,
+                                                               self.intrinsics_lidar, self.intrinsics_hoz_lidar)
 
     def enable_error_maps(self):
         """The sampler's per-frame error maps as base_dataset.py:243-246 creates them: ones, [F, H_lidar / 2, W_lidar / 2] for the range
@@ -179,6 +187,9 @@ class FrameSet:
             images = gather_pixels(images, rays["inds"])
             images_lidar = gather_pixels(images_lidar, rl["inds"])
         res["images"], res["images_lidar"] = images, images_lidar
+        if self.image_depths is not None:  # base_dataset.py:373-388: [B, N, 1] at the camera rays' pixels in training, else [B, H, W]
+            depths = self.image_depths[idx]
+            res["image_depths"] = gather_pixels(depths.unsqueeze(-1), rays["inds"]) if self.training else depths
         res["pano_frame"] = self.images_lidar[idx]  # the whole ground-truth frame (base_dataset.py:403): the structural regulariser's masks
         return res
 
@@ -186,7 +197,10 @@ class FrameSet:
         """`collate` reshaped into the argument names of nvsf.nerf.train_step.RenderTrainStep.losses."""
         c = self.collate(index)
         gl = c["images_lidar"]  # [B, N, 3] = raydrop, intensity, range
-        return {"rays_o_lidar": c["rays_o_lidar"], "rays_d_lidar": c["rays_d_lidar"], "rays_o": c["rays_o"], "rays_d": c["rays_d"],
-                "time": c["time"], "gt_raydrop": gl[..., 0], "gt_intensity": gl[..., 1], "gt_depth": gl[..., 2], "gt_rgb": c["images"][..., :3],
-                # what the structural regulariser and the error-map update read (trainer.py:386-391, 552-556, 588-590)
-                "index": c["index"], "rays_pano_inds": c["rays_pano_inds"], "rays_rgb_inds": c["rays_rgb_inds"], "pano_frame": c["pano_frame"]}
+        b = {"rays_o_lidar": c["rays_o_lidar"], "rays_d_lidar": c["rays_d_lidar"], "rays_o": c["rays_o"], "rays_d": c["rays_d"],
+             "time": c["time"], "gt_raydrop": gl[..., 0], "gt_intensity": gl[..., 1], "gt_depth": gl[..., 2], "gt_rgb": c["images"][..., :3],
+             # what the structural regulariser and the error-map update read (trainer.py:386-391, 552-556, 588-590)
+             "index": c["index"], "rays_pano_inds": c["rays_pano_inds"], "rays_rgb_inds": c["rays_rgb_inds"], "pano_frame": c["pano_frame"]}
+        if "image_depths" in c:
+            b["gt_rgb_depth"] = c["image_depths"][..., 0]  # [B, N], metres (trainer.py:507)
+        return b

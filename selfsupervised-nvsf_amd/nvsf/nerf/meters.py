@@ -81,14 +81,15 @@ def _check_out(out, n, like):
     return out
 
 
-def image_error_stats(pred, truth, lo=-_INF, hi=_INF, out=None):
-    """fp64 [6] device tensor: sum d^2, sum |d|, min / max of truth, min / max of pred, after clamping both to [lo, hi]."""
+def image_error_stats(pred, truth, lo=-_INF, hi=_INF, out=None, wide=False):
+    """fp64 [6] device tensor: sum d^2, sum |d|, min / max of truth, min / max of pred, after clamping both to [lo, hi].  d = t - p is
+    an fp32 difference; `wide`: an fp64 one."""
     from nvsf import _hip
     _check_pair(pred, truth, "image_error_stats")
     pred, truth = pred.contiguous(), truth.contiguous()
     out = _check_out(out, 6, pred)
     nbytes = stats_ws_bytes(pred.numel())
-    _hip.call("nvsf_image_error_stats", _hip.ptr(pred), _hip.ptr(truth), pred.numel(), float(lo), float(hi),
+    _hip.call("nvsf_image_error_stats_wide" if wide else "nvsf_image_error_stats", _hip.ptr(pred), _hip.ptr(truth), pred.numel(), float(lo), float(hi),
               _hip.ptr(_workspace(pred.device, nbytes)), nbytes, _hip.ptr(out))
     return out
 
@@ -212,7 +213,8 @@ class PSNRMeter(_DeviceMeter):
 
 class RMSEMeter(_DeviceMeter):
     """Root mean square error per frame (error_matrices.py:68-115).  rgb_metric=True is the camera-depth form: predictions are zeroed
-    where the truth is 0 and both are capped at 80."""
+    where the truth is 0 and both are capped at 80; the differences are fp64 ones there, as numpy's are once `preds * zero_mask`
+    (error_matrices.py:93-94) has widened the predictions."""
 
     def __init__(self, rgb_metric=False):
         self.rgb_metric = rgb_metric
@@ -223,7 +225,7 @@ class RMSEMeter(_DeviceMeter):
         hi = _INF
         if self.rgb_metric:
             preds, hi = preds * (truths != 0).to(preds.dtype), 80.0
-        image_error_stats(preds, truths, hi=hi, out=self._next_row(preds.device, preds.numel()))
+        image_error_stats(preds, truths, hi=hi, out=self._next_row(preds.device, preds.numel()), wide=self.rgb_metric)
 
     def frame_values(self):
         r, n = self.rows()
@@ -391,14 +393,18 @@ class SSIMMeter(_DeviceMeter):
 def table_meters(scale, intensity_inv_scale=1, raydrop_ratio=0.5, lpips_fn=None):
     """The meters of the reference's evaluation table (main_nvsf.py:224-240) minus PointsMeter (train_step.PointsMeter) and
     LPIPSMeter (no weights here): {"depth", "intensity", "raydrop", "psnr", "rmse", "ssim"}.  "rmse" compares the rendered image
-    with the measured one: the reference feeds its camera RMSE meter a ground-truth camera DEPTH image (trainer.py:1540-1541),
-    which the datasets this package reads do not carry."""
+    with the measured one.  The reference feeds its camera RMSE meter the LiDAR-projected camera DEPTH image (trainer.py:1540-1541):
+    that is the further meter "rgb_depth" = RMSEMeter(rgb_metric=True), which evaluate_frames adds when the frames carry the map
+    (FrameSet(camera_depth=True))."""
     return {"depth": DepthMeter_L4D(scale, lpips_fn), "intensity": IntensityMeter_L4D(intensity_inv_scale, lpips_fn),
             "raydrop": RaydropMeter(raydrop_ratio), "psnr": PSNRMeter(), "rmse": RMSEMeter(), "ssim": SSIMMeter()}
 
 
-def update_table(meters, e):
-    """Feeds the meters of `table_meters` from eval_step's output, as evaluate_one_epoch feeds its own (trainer.py:1537-1584)."""
+def update_table(meters, e, scale=1.0):
+    """Feeds the meters of `table_meters` from eval_step's output, as evaluate_one_epoch feeds its own (trainer.py:1537-1584).  A
+    "rgb_depth" meter is fed pred_rgb_depth / scale against the depth map in metres (trainer.py:761-762)."""
+    if "rgb_depth" in meters:
+        meters["rgb_depth"].update(e["pred_rgb_depth"] / scale, e["gt_rgb_depth"])
     meters["depth"].update(e["pred_depth"], e["gt_depth"])
     meters["intensity"].update(e["pred_intensity"], e["gt_intensity"])
     meters["raydrop"].update(e["pred_raydrop"], e["gt_raydrop"])
@@ -408,7 +414,7 @@ def update_table(meters, e):
 
 def report_lines(meters):
     """The reference's report lines, LiDAR meters first (trainer.py:1794-1827)."""
-    return [meters[k].report() for k in ("depth", "intensity", "raydrop", "psnr", "rmse", "ssim") if k in meters]
+    return [meters[k].report() for k in ("depth", "intensity", "raydrop", "psnr", "rmse", "ssim", "rgb_depth") if k in meters]
 
 
 def table_report(res):
@@ -417,4 +423,5 @@ def table_report(res):
             f"Depth_error (RMSE, MedAE, LPIPS, SSIM, PNSR) = {np.array(res['depth'])}",
             f"Intensity_error (RMSE, MedAE, LPIPS, SSIM, PNSR) = {np.array(res['intensity'])}",
             f"Rdrop_error (RMSE, Accuracy, F_score) = {np.array(res['raydrop'])}",
-            f"RMSE_intensity = {res['rgb_rmse']:.3f}", f"PSNR = {res['psnr']:.3f}", f"SSIM = {res['rgb_ssim']:.3f}"]
+            f"RMSE_intensity = {res['rgb_rmse']:.3f}", f"PSNR = {res['psnr']:.3f}", f"SSIM = {res['rgb_ssim']:.3f}"] + \
+        ([f"RMSE = {res['rgb_depth_rmse']:.3f}"] if "rgb_depth_rmse" in res else [])

@@ -9,7 +9,8 @@ Only what sits directly around the hot path, restated from the reference's `Trai
     (trainer.py:229-233; it IS part of the total at :542), on csrc/chamfer.hip; optional scene-flow loss (`--flow_loss`,
     trainer.py:236-267: chamfer between the flow-warped point cloud of the frame and its neighbours' clouds + mean |flow|) and
     URF line-of-sight loss (trainer.py:276-294);
-  * camera: MSE RGB summed over rays and channels (alpha_rgb 1; trainer.py:491-503);
+  * camera: MSE RGB summed over rays and channels (alpha_rgb 1; trainer.py:491-503); optional depth term against the LiDAR-projected
+    camera depth map (`--use_rgbd_loss`, trainer.py:505-518: both capped at 80 m, masked where the map is empty, summed; `CameraLossFn`);
   * NaN -> 0, Inf -> 1e5 on the scalar (trainer.py:545-546);
   * optimiser: Adam(betas 0.9/0.99, eps 1e-15) on `model.get_params(lr)` and the 0.1^(iter/iters) decay
     (main_nvsf.py:350-362), under the GradScaler of the reference's fp16 run (trainer.py:119, 1332-1334);
@@ -112,6 +113,64 @@ class MseSumFn(torch.autograd.Function):
         return grad.view(ctx.shape), None, None
 
 
+class CameraLossFn(torch.autograd.Function):
+    """The two camera terms of Trainer.train_step with `--use_rgbd_loss` (trainer.py:491-518) as one launch each way
+    (nvsf_camera_loss_fwd / _bwd): sum alpha_rgb (image - gt_rgb)^2 and the depth term against the LiDAR-projected depth map --
+    gt = gt_depth_m * scale capped at 80 * scale, the rendered depth capped the same way (a capped ray gets no gradient), mask = gt > 0,
+    alpha_rd * sum criterion(depth * mask, gt * mask).  criterion: `--rgb_depth_loss` (main_nvsf.py:91, 205-212).
+    Returns (loss_rgb, loss_rgb_depth)."""
+    CRITERIA = {"l1": 0, "mse": 1, "huber": 2, "smoothl1": 3, "bce": 4}
+
+    @staticmethod
+    def criterion_code(criterion, scale):
+        if criterion not in CameraLossFn.CRITERIA:  # "cos": CosineSimilarity over dim 1 of a [B, N] pair is no per-ray loss
+            raise ValueError(f"rgb_depth_loss={criterion!r}: one of {sorted(CameraLossFn.CRITERIA)} (main_nvsf.py:91)")
+        param = 0.2 * float(scale) if criterion == "huber" else (0.1 if criterion == "smoothl1" else 0.0)  # main_nvsf.py:208-209
+        return CameraLossFn.CRITERIA[criterion], param
+
+    @staticmethod
+    def forward(ctx, image, depth, gt_rgb, gt_depth_m, alpha_rgb, alpha_rd, scale, criterion):
+        from nvsf import _hip
+        kind, param = CameraLossFn.criterion_code(criterion, scale)
+        c = lambda t: t.detach().float().contiguous()
+        img, dep, rgb, gtd = c(image), c(depth), c(gt_rgb), c(gt_depth_m)
+        N = dep.numel()
+        if img.numel() != 3 * N or rgb.numel() != 3 * N or gtd.numel() != N:
+            raise ValueError(f"CameraLossFn: image {tuple(image.shape)}, gt_rgb {tuple(gt_rgb.shape)}, depth {tuple(depth.shape)} and "
+                             f"gt_rgb_depth {tuple(gt_depth_m.shape)} do not describe one ray batch")
+        out = [torch.empty((), dtype=torch.float32, device=dep.device) for _ in range(2)]
+        args = (_hip.ptr(img), _hip.ptr(rgb), _hip.ptr(dep), _hip.ptr(gtd), N, float(alpha_rgb), float(alpha_rd), float(scale),
+                80 * float(scale), kind, float(param))
+        _hip.call("nvsf_camera_loss_fwd", *args, _hip.ptr(out[0]), _hip.ptr(out[1]))
+        ctx.save_for_backward(img, rgb, dep, gtd)
+        ctx.args, ctx.shapes = args, (image.shape, depth.shape)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth):
+        from nvsf import _hip
+        img, _, dep, _ = ctx.saved_tensors
+        c = lambda t: None if t is None else t.float().contiguous()
+        g_rgb, g_depth = c(g_rgb), c(g_depth)
+        grad_img, grad_dep = torch.empty_like(img), torch.empty_like(dep)
+        _hip.call("nvsf_camera_loss_bwd", *ctx.args, _hip.ptr(g_rgb), _hip.ptr(g_depth), _hip.ptr(grad_img), _hip.ptr(grad_dep))
+        return (grad_img.view(ctx.shapes[0]), grad_dep.view(ctx.shapes[1])) + (None,) * 6
+
+
+def rgb_depth_loss_host(depth, gt_depth_m, scale, criterion, alpha_rd):
+    """The depth term of CameraLossFn as torch expressions (trainer.py:506-518): the host branch of `losses` and the formulation the
+    device kernels are tested against."""
+    CameraLossFn.criterion_code(criterion, scale)
+    crit = {"l1": torch.nn.L1Loss(reduction="none"), "mse": torch.nn.MSELoss(reduction="none"),
+            "smoothl1": torch.nn.SmoothL1Loss(reduction="none", beta=0.1), "huber": torch.nn.HuberLoss(reduction="none", delta=0.2 * scale),
+            "bce": torch.nn.BCEWithLogitsLoss(reduction="none")}[criterion]
+    max_depth = 80 * scale
+    gt = (gt_depth_m * scale).clamp(max=max_depth)
+    pred = torch.where(depth > max_depth, torch.full_like(depth, max_depth), depth)  # assignment into the tensor: no gradient there
+    mask = (gt > 0).to(pred.dtype)
+    return (alpha_rd * crit(pred * mask, gt * mask)).sum()
+
+
 class LidarGradLossFn(torch.autograd.Function):
     """Structural regularisation of trainer.py:296-470 in its `grad_loss` form as one launch each way (nvsf_lidar_grad_loss_fwd / _bwd):
     pred_depth, gt_depth [1, N] the masked ranges (scene units), gt_raydrop [1, N], pano_inds int64 [1, N] pixel indices of the batch
@@ -160,7 +219,8 @@ class RenderTrainStep:
                  smooth_factor=0.0, use_urf_loss=False, bucket_bytes=64 << 20, fp16=True, scale=1.0, chamfer_loss=True,
                  flow_loss=False, pc_list=None, ema_decay=0.95, split_backward=True, ray_chunks=1, grad_loss=False, depth_grad_loss="l1",
                  alpha_grad=0.1, patch_size_lidar=1, change_patch_size_lidar=(2, 8), change_patch_size_epoch=2, use_error_map=False,
-                 sobel_grad=False, grad_norm_smooth=False, spatial_smooth=False, tv_loss=False):
+                 sobel_grad=False, grad_norm_smooth=False, spatial_smooth=False, tv_loss=False, use_rgbd_loss=False, rgb_depth_loss="l1",
+                 alpha_rd=1.0):
         """Defaults = the reference's CLI defaults (main_nvsf.py:60-97).  `scale`: the scene scale the chamfer loss divides by
         (opt.scale); `pc_list`: {frame index: [P, 3] tensor} world-frame point clouds for the scene-flow loss
         (Trainer.process_pointcloud, trainer.py:1848-1912, builds them from the range images); `ema_decay=None` disables EMA.
@@ -168,8 +228,13 @@ class RenderTrainStep:
         the step runs camera forward + backward, then LiDAR forward + backward, and the camera table scatter (the longest kernel
         of the step, on its side stream) overlaps the whole LiDAR pass instead of the tail of one joint backward.  Same
         gradients (test_train_step_gpu.py); the reference's `nan_to_num` of the total is applied per modality, which differs
-        only when a loss is not finite (then that modality contributes no gradient; GradScaler skips such a step anyway)."""
+        only when a loss is not finite (then that modality contributes no gradient; GradScaler skips such a step anyway).
+        `use_rgbd_loss`, `rgb_depth_loss`, `alpha_rd` (main_nvsf.py:84, 91, 97): the camera depth term against the LiDAR-projected
+        depth map batch["gt_rgb_depth"] (FrameSet(camera_depth=True)); switched on, both camera terms are one launch (CameraLossFn)."""
         self.model = model
+        self.use_rgbd_loss, self.rgb_depth_loss, self.alpha_rd = bool(use_rgbd_loss), str(rgb_depth_loss), float(alpha_rd)
+        if self.use_rgbd_loss:
+            CameraLossFn.criterion_code(self.rgb_depth_loss, scale)  # an unknown criterion (or "cos") fails here, not at the first step
         # loss scaling of the reference's mixed-precision run (trainer.py:119, 1332-1334: GradScaler(enabled=fp16) -> scale(loss)
         # .backward() -> step -> update; `-L` / `--fp16` in main_nvsf.py:17,43,159).  The encoders hand fp16 features to the
         # MLPs, so the gradients that travel back between them are fp16 tensors.
@@ -350,7 +415,18 @@ class RenderTrainStep:
         if "rays_o" in batch:
             gt_rgb = batch["gt_rgb"] if "gt_rgb" in batch else batch["images"][..., :3]
             r = self._render(batch["rays_o"], batch["rays_d"], batch["time"], perturb=True, num_steps=self.num_steps, bg_color=1)
-            out["rgb"] = MseSumFn.apply(r["image"], gt_rgb, self.alpha_rgb) if r["image"].is_cuda else (self.alpha_rgb * (r["image"] - gt_rgb) ** 2).sum()
+            if not self.use_rgbd_loss:
+                out["rgb"] = MseSumFn.apply(r["image"], gt_rgb, self.alpha_rgb) if r["image"].is_cuda else (self.alpha_rgb * (r["image"] - gt_rgb) ** 2).sum()
+            else:
+                if "gt_rgb_depth" not in batch:
+                    raise ValueError("use_rgbd_loss needs batch['gt_rgb_depth'] (FrameSet(camera_depth=True).train_batch)")
+                gt_m = batch["gt_rgb_depth"].reshape(r["depth"].shape)
+                if r["image"].is_cuda:  # both camera terms in one HIP launch each way
+                    out["rgb"], out["rgb_depth"] = CameraLossFn.apply(r["image"], r["depth"], gt_rgb, gt_m, self.alpha_rgb, self.alpha_rd, self.scale,
+                                                                      self.rgb_depth_loss)
+                else:  # host-side logic tests: the same terms as torch expressions
+                    out["rgb"] = (self.alpha_rgb * (r["image"] - gt_rgb) ** 2).sum()
+                    out["rgb_depth"] = rgb_depth_loss_host(r["depth"], gt_m, self.scale, self.rgb_depth_loss, self.alpha_rd)
             if self.error_maps is not None and r["image"].is_cuda:
                 self._for_error_map["camera"] = (r["image"].detach(), gt_rgb)
         total = sum(out.values())
@@ -413,7 +489,7 @@ class RenderTrainStep:
             _hip.call("nvsf_error_map_update", _hip.ptr(ray_loss), _hip.ptr(inds), N, int(W), emap[idx].data_ptr(), int(eH), int(eW), float(eH / H),
                       float(eW / W), _hip.ptr(stats), _hip.ptr(frames.error_map_owner(dev, eH * eW)))
 
-    CAMERA_KEYS = ("rays_o", "rays_d", "gt_rgb", "images", "rays_rgb_inds", "H", "W")
+    CAMERA_KEYS = ("rays_o", "rays_d", "gt_rgb", "images", "rays_rgb_inds", "H", "W", "gt_rgb_depth")
 
     def _backward(self, loss):
         overlap = loss.is_cuda and self.scatter_overlap
@@ -803,6 +879,8 @@ def eval_step(model, data, num_steps, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, al
         pred_rgb = c["image"].reshape(B, H, W, 3)
         loss = loss + alpha_rgb * ((pred_rgb - gt_rgb) ** 2).mean()
         out.update(pred_rgb=pred_rgb, pred_rgb_depth=c["depth"].reshape(B, H, W), gt_rgb=gt_rgb, loss=loss)
+        if "image_depths" in data:  # the LiDAR-projected camera depth map, metres (trainer.py:761-762)
+            out["gt_rgb_depth"] = data["image_depths"].reshape(B, H, W)
     return out
 
 
@@ -824,8 +902,9 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
     "depth" and "intensity" = [RMSE, MedAE, LPIPS, SSIM, PSNR] (DepthMeter_L4D(frames.scale), IntensityMeter_L4D(intensity_inv_scale,
     the reference's --intensity_inv_scale, default 1); the LPIPS slot is NaN: no weights here), "raydrop" = [RMSE, accuracy, F1]
     (RaydropMeter at `raydrop_thres`), "rgb_ssim" (SSIMMeter) and "rgb_rmse" (RMSE of the rendered against the measured image);
-    frame means, the per-frame values riding in the same all-reduce under shard="frames".  The default (None) returns exactly the six
-    keys above from the same code path as before."""
+    frame means, the per-frame values riding in the same all-reduce under shard="frames".  Over a FrameSet opened with camera_depth=True
+    the table also has "rgb_depth_rmse": RMSEMeter(rgb_metric=True) on pred_rgb_depth / scale against the LiDAR-projected depth map, as
+    trainer.py:761-762, 1540-1541 feed it.  The default (None) returns exactly the six keys above from the same code path as before."""
     from nvsf import frame_shard
     if shard not in ("rays", "frames"):
         raise ValueError("shard: 'rays' or 'frames'")
@@ -844,6 +923,8 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
         if meters == "table":
             from nvsf.nerf import meters as M
             table = M.table_meters(frames.scale, intensity_inv_scale, eval_kwargs.get("raydrop_thres", 0.5))
+            if getattr(frames, "image_depths", None) is not None:  # FrameSet(camera_depth=True): the reference's camera depth RMSE
+                table["rgb_depth"] = M.RMSEMeter(rgb_metric=True)
         todo = list(range(len(frames)) if indices is None else indices)
         if shard == "frames" and ws > 1:
             todo = todo[rank::ws]
@@ -853,7 +934,7 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
             rm.append(depth_rmse(e["pred_depth"], e["gt_depth"], frames.scale))
             points.update(e["pred_depth"], e["gt_depth"])
             if table is not None:
-                M.update_table(table, e)  # launches only; read once, after the last frame
+                M.update_table(table, e, frames.scale)  # launches only; read once, after the last frame
             ls.append(float(e["loss"]))
     finally:
         if ema is not None:
@@ -865,6 +946,8 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
         cols = [table["depth"].frame_values().reshape(-1, 5), table["intensity"].frame_values().reshape(-1, 5),
                 table["raydrop"].frame_values().reshape(-1, 3), table["ssim"].frame_values().reshape(-1, 1),
                 table["rmse"].frame_values().reshape(-1, 1)]
+        if "rgb_depth" in table:
+            cols.append(table["rgb_depth"].frame_values().reshape(-1, 1))
         sums += [float(v) for v in np.concatenate(cols, axis=1).sum(0)]
     if shard == "frames":
         sums = frame_shard.allreduce_sums(sums, device=next(model.parameters()).device)
@@ -874,4 +957,6 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
     if table is not None:
         t = [v / n for v in sums[6:]]
         res.update(depth=t[0:5], intensity=t[5:10], raydrop=t[10:13], rgb_ssim=t[13], rgb_rmse=t[14])
+        if len(t) > 15:
+            res["rgb_depth_rmse"] = t[15]
     return res

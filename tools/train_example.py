@@ -2,7 +2,7 @@
 
     python tools/train_example.py --root /path/to/kitti360_nvsf --sequence 1908 [--dynamic] [--epochs 6] [--plain]
                                   [--export-mesh out.ply --mesh-res 256 256 256 --mesh-threshold 10] [--dynamic --flow-loss]
-                                  [--eval-table]
+                                  [--eval-table] [--rgbd-loss]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 tools/train_example.py ...
 
 Data: the reference's on-disk formats (transforms_{seq}_{split}.json + range-image .npy + images; nvsf/nerf/dataset/formats.py).
@@ -17,6 +17,9 @@ one EMA update per epoch; --plain = random pixels and the default losses only.  
 trainer.py:1848-1912; here nvsf/nerf/pointcloud.py on the device) and switches the flow term of the loss on.
 --eval-table also prints the report lines of the reference's evaluation table (trainer.py:1794-1827): range and intensity RMSE / MedAE /
 LPIPS / SSIM / PSNR, ray-drop RMSE / accuracy / F1, camera PSNR / RMSE / SSIM, computed on the device (nvsf/nerf/meters.py).
+--rgbd-loss (the reference's --use_rgbd_loss, main_nvsf.py:84) projects every frame's range image into its camera once, on the device
+(nvsf/nerf/dataset/depth_image.py), and supervises the camera render's depth with that map; with --eval-table the table gets the camera
+depth RMSE line the reference prints as "RMSE = ".
 """
 import argparse
 import os
@@ -78,6 +81,8 @@ def main():
     ap.add_argument("--mesh-threshold", type=float, default=10.0, help="density at the surface (inside: sigma >= threshold)")
     ap.add_argument("--eval-table", action="store_true", help="after training, print the report lines of the reference's evaluation table "
                     "(device-side meters, nvsf/nerf/meters.py)")
+    ap.add_argument("--rgbd-loss", action="store_true", help="camera depth supervision from the LiDAR-projected depth map (FrameSet(camera_depth=True), "
+                    "RenderTrainStep(use_rgbd_loss=True)); adds the camera depth RMSE to --eval-table")
     args = ap.parse_args()
     if args.flow_loss and not args.dynamic:
         ap.error("--flow-loss supervises the flow head of the space-time model: add --dynamic")
@@ -98,7 +103,8 @@ def main():
         if world > 1:
             dist.barrier()
     scale = S.SCALE if hasattr(S, "SCALE") else 0.010851959895748291
-    data = FrameSet(root, args.sequence, "train", scale, num_rays=args.num_rays, num_rays_lidar=args.num_rays, device=dev)
+    data = FrameSet(root, args.sequence, "train", scale, num_rays=args.num_rays, num_rays_lidar=args.num_rays, device=dev,
+                    camera_depth=args.rgbd_loss)
     torch.manual_seed(0)  # identical initial replicas
     if args.dynamic:
         from nvsf.nerf.models.network_dynamic import NeRFNetwork
@@ -122,7 +128,7 @@ def main():
                   + "  ".join(f"{k}: {pc_list[k].shape[0]} points / {pc_ground[k].shape[0]} ground" for k in sorted(pc_list)), flush=True)
     trainer = RenderTrainStep(model, iters=args.epochs * per_epoch, num_steps=args.num_steps, scale=scale, grad_loss=not args.plain,
                               use_error_map=not args.plain, change_patch_size_lidar=(1,) if args.plain else (2, 8),
-                              flow_loss=args.flow_loss, pc_list=pc_list)
+                              flow_loss=args.flow_loss, pc_list=pc_list, use_rgbd_loss=args.rgbd_loss)
     if not args.plain:
         trainer.attach_error_maps(data)
     it = 0
@@ -146,7 +152,7 @@ def main():
             print(line, flush=True)
     # whole-frame evaluation (Trainer.eval_step / evaluate_one_epoch): every frame rendered with the staged loop, its rays split over the ranks
     from nvsf.nerf.train_step import evaluate_frames
-    whole = FrameSet(root, args.sequence, "train", scale, device=dev, training=False)
+    whole = FrameSet(root, args.sequence, "train", scale, device=dev, training=False, camera_depth=args.rgbd_loss)
     res = evaluate_frames(model, whole, args.num_steps, indices=range(min(len(whole), 4)), ema=trainer.ema,
                           meters="table" if args.eval_table else None)
     if rank == 0:
