@@ -98,8 +98,6 @@ __global__ __launch_bounds__(kBlock) void k_ema_update(float* __restrict__ shado
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 NVSF_API int nvsf_adam_prepare(float* state4, const float* found_inf, float beta1, float beta2, hipStream_t stream) {
     REQUIRE(state4 && beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f);
     hipLaunchKernelGGL(k_adam_prepare, dim3(1), dim3(64), 0, stream, state4, found_inf, beta1, beta2);

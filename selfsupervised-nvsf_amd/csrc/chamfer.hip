@@ -80,8 +80,6 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_grad(const float* __restrict
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 static int scan_one_direction(const float* q, uint32_t n, const float* t, uint32_t m, uint32_t B, unsigned long long* ws, float* dist,
                               int* idx, hipStream_t stream) {
     if (n == 0) return NVSF_OK;

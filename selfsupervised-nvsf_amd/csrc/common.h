@@ -12,6 +12,9 @@ enum : int {
     NVSF_ERR_UNSUPPORTED = -2,   // template instantiation not built for this shape
 };
 
+// Argument check of the entry points: a violated precondition returns NVSF_ERR_INVALID_ARG before anything is launched.
+#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
+
 constexpr int kWave = 64;  // CDNA4 wavefront width
 
 static inline int nvsf_launch_status() {

@@ -130,8 +130,6 @@ __global__ __launch_bounds__(kBlock) void k_density_dynamic(DynFeat f, uint32_t 
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 static int density_dynamic_impl(const float* plane_s, const float* plane_d, const float* plane_1, const float* plane_2, int planes_f16,
                                       int hash_s_lm, const void* hash_s_f16, const float* hash_d, const void* hash_1, int hash_1_is_f16, const void* hash_2,
                                       int hash_2_is_f16, uint32_t M, const void* sigma_weights_f16, float* out_h, float* sigmas,

@@ -56,8 +56,6 @@ __global__ __launch_bounds__(kBlock) void k_sh4(const float* __restrict__ d01, u
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 NVSF_API int nvsf_freq_encode(const float* x, uint32_t M, uint32_t n_dims, uint32_t n_freq, void* out_f16, uint32_t out_stride,
                               hipStream_t stream) {
     if (M == 0) return NVSF_OK;

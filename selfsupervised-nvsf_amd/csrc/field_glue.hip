@@ -246,8 +246,6 @@ __global__ __launch_bounds__(kBlock) void k_count_nonzero_u8(const uint8_t* __re
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 NVSF_API int nvsf_sigma_geo_bwd(const float* grad_sigma, const float* sigma, const float* grad_geo, uint32_t gg_stride, uint32_t n_geo,
                                 uint32_t M, float* grad_h, uint32_t gh_stride, float sigma_lo, float sigma_hi, hipStream_t stream) {
     if (M == 0) return NVSF_OK;

@@ -39,6 +39,41 @@ struct RayBatch {
     uint32_t N, T;
 };
 
+// Sample position (renderer_dynamic.py:155-169) and its normalisation to [0,1] (network_dynamic.py:217), the same expression trees in
+// every kernel that forms positions from the rays (their outputs are compared bit for bit).  `lin`: the sample's fraction of
+// [near, near + range]; `noise`: where its jitter in [0, 1) of one step lies -- in rb.noise or in a register that was loaded ahead --
+// dereferenced only when the batch carries noise.  `o`, `d`: the ray's origin and direction, in memory or loaded ahead.
+__device__ __forceinline__ float sample_z(const RayBatch& rb, float near, float range, float lin, const float* noise) {
+    float z = near + range * lin;
+    if (rb.noise) z = z + (*noise - 0.5f) * (range / (float)rb.T);
+    return z;
+}
+
+__device__ __forceinline__ void sample_x01(const RayBatch& rb, const float* o, const float* d, float z, float (&x)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float p = o[k] + d[k] * z;
+        p = fminf(fmaxf(p, rb.lo[k]), rb.hi[k]);
+        x[k] = (p + rb.bound) * rb.inv_extent;
+    }
+}
+
+__device__ __forceinline__ float sample_point(const RayBatch& rb, const float* o, const float* d, float near, float range, float lin,
+                                              const float* noise, float (&x)[3]) {
+    const float z = sample_z(rb, near, range, lin, noise);
+    sample_x01(rb, o, d, z, x);
+    return z;
+}
+
+// origin and direction of ray n
+__device__ __forceinline__ void load_ray(const RayBatch& rb, uint32_t n, float (&o)[3], float (&d)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        o[k] = rb.rays_o[3 * (size_t)n + k];
+        d[k] = rb.rays_d[3 * (size_t)n + k];
+    }
+}
+
 template <int F>
 __global__ __launch_bounds__(kBlock) void k_density_uniform(RayBatch rb, const _Float16* __restrict__ table, GridMeta meta,
                                                             const _Float16* __restrict__ w_sigma, float* __restrict__ z_vals,
@@ -63,17 +98,9 @@ __global__ __launch_bounds__(kBlock) void k_density_uniform(RayBatch rb, const _
         const bool in_range = s_raw < total;
         const unsigned long long s = in_range ? s_raw : total - 1;
         const uint32_t n = (uint32_t)(s / rb.T), i = (uint32_t)(s - (unsigned long long)n * rb.T);
-        // sample position (renderer_dynamic.py:155-169) and normalisation to [0,1] (network_dynamic.py:217)
         const float near = rb.nears[n], range = rb.fars[n] - near;
-        float z = near + range * rb.lin[i];
-        if (rb.noise) z = z + (rb.noise[s] - 0.5f) * (range / (float)rb.T);
         float x[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float p = rb.rays_o[3 * (size_t)n + k] + rb.rays_d[3 * (size_t)n + k] * z;
-            p = fminf(fmaxf(p, rb.lo[k]), rb.hi[k]);
-            x[k] = (p + rb.bound) * rb.inv_extent;
-        }
+        const float z = sample_point(rb, rb.rays_o + 3 * (size_t)n, rb.rays_d + 3 * (size_t)n, near, range, rb.lin[i], rb.noise + s, x);
         // hash-grid encode: this lane's 8 features = levels g*kLevelsPerGroup .. +kLevelsPerGroup-1
         half8_t xf;
 #pragma unroll
@@ -430,19 +457,14 @@ __global__ __launch_bounds__(kBlock) void k_density_uniform_v2(RayBatch rb, cons
             const uint32_t n = unit / segs_per_ray;
             const uint32_t seg = unit - n * segs_per_ray;
             const float near = rb.nears[n], range = rb.fars[n] - near;
-            const float ox = rb.rays_o[3 * (size_t)n], oy = rb.rays_o[3 * (size_t)n + 1], oz = rb.rays_o[3 * (size_t)n + 2];
-            const float dx = rb.rays_d[3 * (size_t)n], dy = rb.rays_d[3 * (size_t)n + 1], dz = rb.rays_d[3 * (size_t)n + 2];
-            const float sample_dist = range / (float)rb.T;
+            float ro[3], rd[3];
+            load_ray(rb, n, ro, rd);
             const uint32_t t_end = min(tiles_per_ray, (seg + 1) * seg_tiles);
             for (uint32_t tt = seg * seg_tiles + wave_in_block; tt < t_end; tt += kWavesPerBlock) {
                 const uint32_t i = tt * 16 + sl;
                 const unsigned long long s = (unsigned long long)n * rb.T + i;
-                float z = near + range * rb.lin[i];
-                if (rb.noise) z = z + (rb.noise[s] - 0.5f) * sample_dist;
                 float x[3];
-                x[0] = (fminf(fmaxf(ox + dx * z, rb.lo[0]), rb.hi[0]) + rb.bound) * rb.inv_extent;
-                x[1] = (fminf(fmaxf(oy + dy * z, rb.lo[1]), rb.hi[1]) + rb.bound) * rb.inv_extent;
-                x[2] = (fminf(fmaxf(oz + dz * z, rb.lo[2]), rb.hi[2]) + rb.bound) * rb.inv_extent;
+                const float z = sample_point(rb, ro, rd, near, range, rb.lin[i], rb.noise + s, x);
                 density_tile<F, QG, TRAIN>(cx, x, z, s, true, z_vals, sigmas, geo, &tr);
             }
         }
@@ -455,6 +477,8 @@ __global__ __launch_bounds__(kBlock) void k_density_uniform_v2(RayBatch rb, cons
             const unsigned long long s = in_range ? s_raw : total - 1;
             const uint32_t n = (uint32_t)(s / rb.T), i = (uint32_t)(s - (unsigned long long)n * rb.T);
             const float near = rb.nears[n], range = rb.fars[n] - near;
+            // sample_point, written out: through the helper this instance allocates one VGPR less (131 / 145 against 132 / 146), and
+            // the register figures of these kernels are pinned to their measured timings
             float z = near + range * rb.lin[i];
             if (rb.noise) z = z + (rb.noise[s] - 0.5f) * (range / (float)rb.T);
             float x[3];
@@ -590,6 +614,68 @@ struct SlicePlan {
     uint32_t slice[8][kPlanItems], begin[8][kPlanItems], end[8][kPlanItems];
 };
 
+// ---- unit walker of the encode passes (k_encode_sliced_pairs, k_encode_sliced_f4) ----
+// A unit = 32 consecutive samples, two lanes per sample (half_lane = lane >> 1 is the sample of the unit).  What a lane needs of
+// its sample before the position can be formed:
+struct EncodeUnit {
+    uint32_t s, n;
+    bool in_range;
+    float near, far, lin, noise, o[3], d[3];
+};
+
+// UNIFORM_RAY (T % 32 == 0, hence M % 32 == 0): the unit lies inside ray n_u and starts at its sample i_u (wave-uniform, from the
+// walker's cursor); otherwise (ray, sample) come from a division per lane.
+template <bool UNIFORM_RAY>
+__device__ __forceinline__ EncodeUnit fetch_unit(const RayBatch& rb, uint32_t M, uint32_t half_lane, uint32_t unit, uint32_t n_u, uint32_t i_u) {
+    EncodeUnit u;
+    const uint32_t s_raw = unit * 32u + half_lane;
+    uint32_t i;
+    if constexpr (UNIFORM_RAY) {
+        u.in_range = true;  // M % 32 == 0
+        u.s = s_raw;
+        u.n = n_u;
+        i = i_u + half_lane;
+    } else {
+        u.in_range = s_raw < M;
+        u.s = u.in_range ? s_raw : M - 1u;
+        u.n = u.s / rb.T;
+        i = u.s - u.n * rb.T;
+    }
+    u.near = rb.nears[u.n];
+    u.far = rb.fars[u.n];
+    u.lin = rb.lin[i];
+    u.noise = rb.noise ? rb.noise[u.s] : 0.5f;
+    load_ray(rb, u.n, u.o, u.d);
+    return u;
+}
+
+// The wave-uniform (ray, first sample) of the unit a wave works on.  It stays in SGPRs: the encode passes are bound by VALU issue as
+// much as by the L1 look-ups (rocprofv3: VALU active 81 % of the SIMD cycles), so the unit / ray cursor must not cost vector
+// instructions.  UNIFORM_RAY (T % 32 == 0): a unit lies inside one ray and the cursor advances by a fixed stride without a
+// division; otherwise it is unused (fetch_unit divides per lane).
+template <bool UNIFORM_RAY>
+struct UnitCursor {
+    uint32_t ray = 0, first = 0, d_ray = 0, d_first = 0;
+    __device__ __forceinline__ UnitCursor(uint32_t wave, uint32_t wave_count, uint32_t T) {
+        if constexpr (UNIFORM_RAY) {
+            ray = (wave * 32u) / T;
+            first = wave * 32u - ray * T;
+            d_ray = (wave_count * 32u) / T;
+            d_first = wave_count * 32u - d_ray * T;
+        }
+    }
+    __device__ __forceinline__ void advance(uint32_t T) {  // by wave_count units
+        if constexpr (UNIFORM_RAY) {
+            ray += d_ray;
+            first += d_first;
+            if (first >= T) {
+                first -= T;
+                ray += 1u;
+            }
+        }
+    }
+};
+
 template <int F, bool UNIFORM_RAY>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_encode_sliced_pairs(RayBatch rb, const _Float16* __restrict__ table, uint32_t table_bytes,
                                                                 GridMeta meta, uint32_t L, uint32_t first_hashed, uint32_t M,
@@ -616,77 +702,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     const int lane = lane_id();
     const uint32_t xb = (uint32_t)(lane & 1), half_lane = (uint32_t)(lane >> 1);
     const uint32_t n_units = unit_end;
-    // wave-uniform bookkeeping in SGPRs: the pass is bound by VALU issue as much as by the L1 look-ups (rocprofv3: VALU active
-    // 81 % of the SIMD cycles), so the unit / ray cursor must not cost vector instructions
     const uint32_t wave = __builtin_amdgcn_readfirstlane(unit_begin + sb * kWavesPerBlock + (threadIdx.x >> 6)), wave_count = n_sb * kWavesPerBlock;
     if (wave >= n_units) continue;
-    const uint32_t T = rb.T;
-    struct Unit {
-        uint32_t s, n;
-        bool in_range;
-        float near, far, lin, noise, o[3], d[3];
-    };
-    // UNIFORM_RAY (T % 32 == 0): a unit lies inside one ray; (ray, first sample) advance by a fixed stride without a division
-    uint32_t ray = 0, first = 0, d_ray = 0, d_first = 0;
-    if constexpr (UNIFORM_RAY) {
-        ray = (wave * 32u) / T;
-        first = wave * 32u - ray * T;
-        d_ray = (wave_count * 32u) / T;
-        d_first = wave_count * 32u - d_ray * T;
-    }
-    auto fetch = [&](uint32_t unit, uint32_t n_u, uint32_t i_u) {
-        Unit u;
-        const uint32_t s_raw = unit * 32u + half_lane;
-        uint32_t i;
-        if constexpr (UNIFORM_RAY) {
-            u.in_range = true;  // M % 32 == 0
-            u.s = s_raw;
-            u.n = n_u;
-            i = i_u + half_lane;
-        } else {
-            u.in_range = s_raw < M;
-            u.s = u.in_range ? s_raw : M - 1u;
-            u.n = u.s / T;
-            i = u.s - u.n * T;
-        }
-        u.near = rb.nears[u.n];
-        u.far = rb.fars[u.n];
-        u.lin = rb.lin[i];
-        u.noise = rb.noise ? rb.noise[u.s] : 0.5f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            u.o[k] = rb.rays_o[3 * (size_t)u.n + k];
-            u.d[k] = rb.rays_d[3 * (size_t)u.n + k];
-        }
-        return u;
-    };
-    Unit cur = fetch(wave, ray, first);
+    // units wave, wave + wave_count, ...; the next unit's inputs are fetched one unit ahead
+    UnitCursor<UNIFORM_RAY> at(wave, wave_count, rb.T);
+    EncodeUnit cur = fetch_unit<UNIFORM_RAY>(rb, M, half_lane, wave, at.ray, at.first);
     for (uint32_t unit = wave; unit < n_units; unit += wave_count) {
         const bool more = unit + wave_count < n_units;
-        uint32_t ray_n = ray, first_n = first;
-        if constexpr (UNIFORM_RAY) {
-            if (more) {
-                ray_n = ray + d_ray;
-                first_n = first + d_first;
-                if (first_n >= T) {
-                    first_n -= T;
-                    ray_n += 1u;
-                }
-            }
-        }
-        const Unit nxt = fetch(more ? unit + wave_count : unit, ray_n, first_n);
-        ray = ray_n;
-        first = first_n;
-        const float range = cur.far - cur.near;
-        float z = cur.near + range * cur.lin;
-        if (rb.noise) z = z + (cur.noise - 0.5f) * (range / (float)T);
+        if (more) at.advance(rb.T);
+        const EncodeUnit nxt = fetch_unit<UNIFORM_RAY>(rb, M, half_lane, more ? unit + wave_count : unit, at.ray, at.first);
         float x[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float p = cur.o[k] + cur.d[k] * z;
-            p = fminf(fmaxf(p, rb.lo[k]), rb.hi[k]);
-            x[k] = (p + rb.bound) * rb.inv_extent;
-        }
+        const float z = sample_point(rb, cur.o, cur.d, cur.near, cur.far - cur.near, cur.lin, &cur.noise, x);
         float frac[2][3];
         uint32_t half_raw[2][4];
         slice_issue_half<F>(lv[0], rsrc, x, xb, frac[0], half_raw[0]);
@@ -759,72 +785,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     const uint32_t n_units = unit_end;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(unit_begin + sb * kWavesPerBlock + (threadIdx.x >> 6)), wave_count = n_sb * kWavesPerBlock;
     if (wave >= n_units) continue;
-    const uint32_t T = rb.T;
-    struct Unit {
-        uint32_t s, n;
-        bool in_range;
-        float near, far, lin, noise, o[3], d[3];
-    };
-    uint32_t ray = 0, first = 0, d_ray = 0, d_first = 0;
-    if constexpr (UNIFORM_RAY) {  // T % 32 == 0: a unit lies inside one ray; the cursor advances without a division
-        ray = (wave * 32u) / T;
-        first = wave * 32u - ray * T;
-        d_ray = (wave_count * 32u) / T;
-        d_first = wave_count * 32u - d_ray * T;
-    }
-    auto fetch = [&](uint32_t unit, uint32_t n_u, uint32_t i_u) {
-        Unit u;
-        const uint32_t s_raw = unit * 32u + half_lane;
-        uint32_t i;
-        if constexpr (UNIFORM_RAY) {
-            u.in_range = true;
-            u.s = s_raw;
-            u.n = n_u;
-            i = i_u + half_lane;
-        } else {
-            u.in_range = s_raw < M;
-            u.s = u.in_range ? s_raw : M - 1u;
-            u.n = u.s / T;
-            i = u.s - u.n * T;
-        }
-        u.near = rb.nears[u.n];
-        u.far = rb.fars[u.n];
-        u.lin = rb.lin[i];
-        u.noise = rb.noise ? rb.noise[u.s] : 0.5f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            u.o[k] = rb.rays_o[3 * (size_t)u.n + k];
-            u.d[k] = rb.rays_d[3 * (size_t)u.n + k];
-        }
-        return u;
-    };
-    Unit cur = fetch(wave, ray, first);
+    // units wave, wave + wave_count, ...; the next unit's inputs are fetched one unit ahead
+    UnitCursor<UNIFORM_RAY> at(wave, wave_count, rb.T);
+    EncodeUnit cur = fetch_unit<UNIFORM_RAY>(rb, M, half_lane, wave, at.ray, at.first);
     for (uint32_t unit = wave; unit < n_units; unit += wave_count) {
         const bool more = unit + wave_count < n_units;
-        uint32_t ray_n = ray, first_n = first;
-        if constexpr (UNIFORM_RAY) {
-            if (more) {
-                ray_n = ray + d_ray;
-                first_n = first + d_first;
-                if (first_n >= T) {
-                    first_n -= T;
-                    ray_n += 1u;
-                }
-            }
-        }
-        const Unit nxt = fetch(more ? unit + wave_count : unit, ray_n, first_n);
-        ray = ray_n;
-        first = first_n;
-        const float range = cur.far - cur.near;
-        float z = cur.near + range * cur.lin;
-        if (rb.noise) z = z + (cur.noise - 0.5f) * (range / (float)T);
+        if (more) at.advance(rb.T);
+        const EncodeUnit nxt = fetch_unit<UNIFORM_RAY>(rb, M, half_lane, more ? unit + wave_count : unit, at.ray, at.first);
         float x[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float p = cur.o[k] + cur.d[k] * z;
-            p = fminf(fmaxf(p, rb.lo[k]), rb.hi[k]);
-            x[k] = (p + rb.bound) * rb.inv_extent;
-        }
+        const float z = sample_point(rb, cur.o, cur.d, cur.near, cur.far - cur.near, cur.lin, &cur.noise, x);
         float frac[3];
         uint32_t c[3];
 #pragma unroll
@@ -1042,6 +1011,33 @@ struct HeadW {
 // sigmoid with the hardware exp2 / reciprocal (each ~1 ulp): well inside the 1e-4 budget of the composited image
 __device__ __forceinline__ float sigmoid_f32(float logit) { return __builtin_amdgcn_rcpf(1.0f + __expf(-logit)); }
 
+// Per-ray direction encoding -> the ray-constant part of the heads' B fragments: lane group g's 8 features of every k-step.
+// d0, d1, d2: the direction mapped to [0, 1] (network_dynamic.py:310,319).  Camera: SH16 (groups 0, 1; groups 2, 3 are overwritten
+// per tile).  LiDAR: feature k = i*24 + 2*f + (0: sin, 1: cos) for k < 72, 1.0 beyond (placeholder: geo / ones filled per tile).
+template <bool LIDAR>
+__device__ __forceinline__ void encode_ray_direction(float d0, float d1, float d2, int g, half8_t (&xf)[LIDAR ? 3 : 1]) {
+    if constexpr (!LIDAR) {
+        float sh[16];
+        sh4_basis(d0, d1, d2, sh);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) xf[0][j] = (_Float16)(g == 0 ? sh[j] : sh[8 + j]);
+    } else {
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+#pragma unroll
+            for (int j = 0; j < 8; j += 2) {
+                const int k = 32 * s + 8 * g + j;
+                float sn = 1.0f, cs = 1.0f;
+                if (k < 72) {
+                    const int i = k / 24, f = (k - 24 * i) >> 1;
+                    freq_pair(i == 0 ? d0 : (i == 1 ? d1 : d2), f, sn, cs);
+                }
+                xf[s][j] = (_Float16)sn;
+                xf[s][j + 1] = (_Float16)cs;
+            }
+    }
+}
+
 // Two 16-sample tiles per iteration (independent MFMA chains for the scheduler to interleave); the weights and
 // geometry rows of the next iteration are fetched before the current one is evaluated.
 template <bool LIDAR>
@@ -1061,27 +1057,7 @@ __global__ __launch_bounds__(kBlock) void k_heads_uniform(const float* __restric
     const float d0 = (rays_d[3 * (size_t)n] + 1.0f) / 2.0f, d1 = (rays_d[3 * (size_t)n + 1] + 1.0f) / 2.0f,
                 d2 = (rays_d[3 * (size_t)n + 2] + 1.0f) / 2.0f;  // network_dynamic.py:310,319
     half8_t xf[IN_STEPS];
-    if constexpr (!LIDAR) {
-        float sh[16];
-        sh4_basis(d0, d1, d2, sh);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xf[0][j] = (_Float16)(g == 0 ? sh[j] : sh[8 + j]);  // groups 2,3 are overwritten per tile
-    } else {
-        // feature k = i*24 + 2*f + (0: sin, 1: cos), k < 72
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                const int k = 32 * s + 8 * g + j;
-                float sn = 1.0f, cs = 1.0f;  // k >= 72: placeholder (geo / ones filled per tile)
-                if (k < 72) {
-                    const int i = k / 24, f = (k - 24 * i) >> 1;
-                    freq_pair(i == 0 ? d0 : (i == 1 ? d1 : d2), f, sn, cs);
-                }
-                xf[s][j] = (_Float16)sn;
-                xf[s][j + 1] = (_Float16)cs;
-            }
-    }
+    encode_ray_direction<LIDAR>(d0, d1, d2, g, xf);
     // LiDAR: the two heads run as separate waves (blockIdx.y selects raydrop / intensity -> image channel 0 / 1):
     // half the weight registers per wave (twice the resident waves) and twice as many waves to fill the chip.
     const int head = LIDAR ? (int)blockIdx.y : 0;
@@ -1245,6 +1221,114 @@ __device__ __forceinline__ void ray_head_constants(const half8_t* xf, const _Flo
     }
 }
 
+// The LDS level table the LDS_LV form of density_encode reads: {scale, res, byte offset, rows} of level l at [l].  Every thread of the
+// workgroup calls it, before the barrier.
+template <int F>
+__device__ __forceinline__ void fill_level_table(uint4* s_lv, const GridMeta& meta) {
+    if (threadIdx.x < kMaxLevels) {
+        const uint32_t l = threadIdx.x;
+        s_lv[l] = make_uint4(__builtin_bit_cast(uint32_t, meta.scale[l]), meta.res[l], meta.offset[l] * (uint32_t)(F * sizeof(_Float16)),
+                             meta.offset[l + 1] - meta.offset[l]);
+    }
+}
+
+// Sigma MLP on a tile from the LDS fragments (frag = s_frag + lane): 32 encoded features -> 64 -> 16.  Returns the rotated output
+// rows 4g..4g+3 of sample (lane & 15): rows 0..14 = h1..h15, row 15 = density logit h0 (as density_eval).
+template <bool LIDAR>
+__device__ __forceinline__ float4_t sigma_tile(const half8_t* frag, const half8_t& feat) {
+    using FR = OccFrags<LIDAR>;
+    float4_t acc1[kHidTiles];
+#pragma unroll
+    for (int t = 0; t < kHidTiles; ++t) acc1[t] = mfma16(frag[(FR::kSigma + t) * kWave], feat, float4_t{0, 0, 0, 0});
+    half8_t h[kHidSteps];
+    pack_hidden(acc1, h);
+    float4_t c = {0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < kHidSteps; ++s) c = mfma16(frag[(FR::kSigma + 4 + s) * kWave], h[s], c);
+    return c;
+}
+
+// Geometry row of a tile -> the last k-step of the heads' input.  The lane groups that carry geometry features in the varying
+// k-step (LiDAR: 1, 2; camera: 2, 3) collect their 8 columns (h1 .. h15, 1.0) from two source groups, the others keep the
+// ray-constant `x_const`.  Set up once per ray, applied per tile.
+template <bool LIDAR>
+struct GeoRoute {
+    bool takes_geo;
+    int src_a, src_b;
+    __device__ __forceinline__ GeoRoute(int g, int c) {  // lane group, sample column of this lane
+        takes_geo = LIDAR ? (g == 1 || g == 2) : (g >= 2);
+        src_a = (c + 16 * (LIDAR ? 2 * (g - 1) : 2 * (g - 2))) & 63;
+        src_b = (src_a + 16) & 63;
+    }
+    // `o`: the sigma net's rotated output rows of this lane (lane group g holds rows 4g .. 4g+3 of sample lane & 15, the density logit
+    // in the last row of group 3).  `shift` = 1: the output layer ran with its rows rotated by 5 instead of 1 (tile 2j + 1 of
+    // k_render_tail2), so every row sits one lane group lower.  Every lane of the wave must call it (cross-lane reads).
+    __device__ __forceinline__ half8_t apply(const float4_t& o, int g, int shift, const half8_t& x_const) const {
+        const int a = shift ? (src_a + 48) & 63 : src_a, b = shift ? (src_b + 48) & 63 : src_b;
+        const uint32_t p0 = pack_h2(o[0], o[1]), p1 = pack_h2(o[2], g == (shift ? 2 : 3) ? 1.0f : o[3]);
+        typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
+        u4_t gv;
+        gv[0] = (uint32_t)__shfl((int)p0, a);
+        gv[1] = (uint32_t)__shfl((int)p1, a);
+        gv[2] = (uint32_t)__shfl((int)p0, b);
+        gv[3] = (uint32_t)__shfl((int)p1, b);
+        return takes_geo ? __builtin_bit_cast(half8_t, gv) : x_const;
+    }
+};
+
+// One head on NT tiles from the LDS fragments: the last k-step of the first layer on top of the ray's constants (`pre`,
+// ray_head_constants), two more layers.  Every fragment is read once and feeds the MFMAs of all NT tiles.
+template <bool LIDAR, int NT>
+__device__ __forceinline__ void head_tiles(const half8_t* frag, const float4_t* pre, int g, int hd, const half8_t (&x_last)[NT], float4_t (&out)[NT]) {
+    using FR = OccFrags<LIDAR>;
+    const int base = FR::kHead + hd * FR::kPerHead;
+    float4_t acc[NT][kHidTiles];
+#pragma unroll
+    for (int t = 0; t < kHidTiles; ++t) {
+        float4_t c = {0, 0, 0, 0};
+        if constexpr (FR::IN_STEPS > 1) c = pre[(hd * 4 + t) * 4 + g];
+        const half8_t w = frag[(base + t) * kWave];
+#pragma unroll
+        for (int u = 0; u < NT; ++u) acc[u][t] = mfma16(w, x_last[u], c);
+    }
+    half8_t h[NT][kHidSteps];
+#pragma unroll
+    for (int u = 0; u < NT; ++u) pack_hidden(acc[u], h[u]);
+#pragma unroll
+    for (int t = 0; t < kHidTiles; ++t) {
+        float4_t a[NT];
+#pragma unroll
+        for (int u = 0; u < NT; ++u) a[u] = float4_t{0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < kHidSteps; ++s) {
+            const half8_t w = frag[(base + 4 + 2 * t + s) * kWave];
+#pragma unroll
+            for (int u = 0; u < NT; ++u) a[u] = mfma16(w, h[u][s], a[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < NT; ++u) acc[u][t] = a[u];
+    }
+#pragma unroll
+    for (int u = 0; u < NT; ++u) pack_hidden(acc[u], h[u]);
+#pragma unroll
+    for (int u = 0; u < NT; ++u) out[u] = float4_t{0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < kHidSteps; ++s) {
+        const half8_t w = frag[(base + 4 + 8 + s) * kWave];
+#pragma unroll
+        for (int u = 0; u < NT; ++u) out[u] = mfma16(w, h[u][s], out[u]);
+    }
+}
+
+// the one-tile kernels' form
+template <bool LIDAR>
+__device__ __forceinline__ float4_t head_tile(const half8_t* frag, const float4_t* pre, int g, int hd, const half8_t& x_last) {
+    const half8_t x[1] = {x_last};
+    float4_t out[1];
+    head_tiles<LIDAR, 1>(frag, pre, g, hd, x, out);
+    return out[0];
+}
+
 template <bool LIDAR, int F = 2, int FH = -1>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_render_occupancy_lds(OccRays rr, const _Float16* __restrict__ table, uint32_t table_bytes,
                                                                  GridMeta meta, uint32_t first_hashed, const _Float16* __restrict__ w_sigma,
@@ -1259,11 +1343,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 4))) 
     __shared__ float4_t s_pre[kWavesPerBlock * FR::kPre];
     constexpr uint32_t kLutH = 128;  // Morton bit-spread table for grids up to 128^3 (the reference's size); larger: computed
     __shared__ uint32_t s_lut[kLutH];
-    if (threadIdx.x < kMaxLevels) {
-        const uint32_t l = threadIdx.x;
-        s_lv[l] = make_uint4(__builtin_bit_cast(uint32_t, meta.scale[l]), meta.res[l], meta.offset[l] * (uint32_t)(F * sizeof(_Float16)),
-                             meta.offset[l + 1] - meta.offset[l]);
-    }
+    fill_level_table<F>(s_lv, meta);
     if (threadIdx.x < kLutH) s_lut[threadIdx.x] = spread3(threadIdx.x);
     const int lane = lane_id(), g = lane >> 4, sl = lane & 15;
     for (int f = (int)(threadIdx.x >> 6); f < FR::kCount; f += kWavesPerBlock) s_frag[f * kWave + lane] = occ_fragment<LIDAR, F>(f, lane, w_sigma, w_a, w_b);
@@ -1281,56 +1361,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 4))) 
     const float rd0 = rr.rays_d[3 * (size_t)n], rd1 = rr.rays_d[3 * (size_t)n + 1], rd2 = rr.rays_d[3 * (size_t)n + 2];
     const float d0 = (rd0 + 1.0f) / 2.0f, d1 = (rd1 + 1.0f) / 2.0f, d2 = (rd2 + 1.0f) / 2.0f;
     half8_t xf[IN_STEPS];
-    if constexpr (!LIDAR) {
-        float sh[16];
-        sh4_basis(d0, d1, d2, sh);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xf[0][j] = (_Float16)(g == 0 ? sh[j] : sh[8 + j]);
-    } else {
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                const int k = 32 * s + 8 * g + j;
-                float sn = 1.0f, cs = 1.0f;
-                if (k < 72) {
-                    const int i = k / 24, f = (k - 24 * i) >> 1;
-                    freq_pair(i == 0 ? d0 : (i == 1 ? d1 : d2), f, sn, cs);
-                }
-                xf[s][j] = (_Float16)sn;
-                xf[s][j + 1] = (_Float16)cs;
-            }
-    }
-    const bool takes_geo = LIDAR ? (g == 1 || g == 2) : (g >= 2);
-    const int src_a = (sl + 16 * (LIDAR ? 2 * (g - 1) : 2 * (g - 2))) & 63, src_b = (src_a + 16) & 63;
+    encode_ray_direction<LIDAR>(d0, d1, d2, g, xf);
 
+    const GeoRoute<LIDAR> route(g, lane & 15);
     float4_t* pre = s_pre + (threadIdx.x >> 6) * FR::kPre;
     ray_head_constants<LIDAR>(xf, w_a, w_b, lane, pre);
-    // one head on a tile: last k-step of the first layer on top of the ray's constants, two more layers
-    auto head = [&](int hd, const half8_t& x_last) {
-        const int base = FR::kHead + hd * FR::kPerHead;
-        float4_t acc[kHidTiles];
-#pragma unroll
-        for (int t = 0; t < kHidTiles; ++t) {
-            float4_t c = {0, 0, 0, 0};
-            if constexpr (IN_STEPS > 1) c = pre[(hd * 4 + t) * 4 + g];
-            acc[t] = mfma16(frag[(base + t) * kWave], x_last, c);
-        }
-        half8_t h[kHidSteps];
-        pack_hidden(acc, h);
-#pragma unroll
-        for (int t = 0; t < kHidTiles; ++t) {
-            float4_t c = {0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < kHidSteps; ++s) c = mfma16(frag[(base + 4 + 2 * t + s) * kWave], h[s], c);
-            acc[t] = c;
-        }
-        pack_hidden(acc, h);
-        float4_t c = {0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < kHidSteps; ++s) c = mfma16(frag[(base + 4 + 8 + s) * kWave], h[s], c);
-        return c;
-    };
 
     const float o3[3] = {rr.rays_o[3 * (size_t)n], rr.rays_o[3 * (size_t)n + 1], rr.rays_o[3 * (size_t)n + 2]};
     const float dd[3] = {rd0, rd1, rd2};
@@ -1378,34 +1413,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 4))) 
         if (cnt == 0u) break;
         const float x01[3] = {(sx + rr.bound) / extent, (sy + rr.bound) / extent, (sz + rr.bound) / extent};
         const half8_t feat = density_encode<F, 8 / F, true, FH>(cx, x01);
-        float4_t o;
-        {
-            float4_t acc1[kHidTiles];
-#pragma unroll
-            for (int tt = 0; tt < kHidTiles; ++tt) {
-                const float4_t zero = {0, 0, 0, 0};
-                acc1[tt] = mfma16(frag[(FR::kSigma + tt) * kWave], feat, zero);
-            }
-            half8_t h[kHidSteps];
-            pack_hidden(acc1, h);
-            float4_t c = {0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < kHidSteps; ++s) c = mfma16(frag[(FR::kSigma + 4 + s) * kWave], h[s], c);
-            o = c;
-        }
+        const float4_t o = sigma_tile<LIDAR>(frag, feat);
         const float sigma = expf(o[3]) * density_scale;  // meaningful in lanes g == 3
-        const uint32_t p0 = pack_h2(o[0], o[1]), p1 = pack_h2(o[2], g == 3 ? 1.0f : o[3]);
-        typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
-        u4_t gv;
-        gv[0] = (uint32_t)__shfl((int)p0, src_a);
-        gv[1] = (uint32_t)__shfl((int)p1, src_a);
-        gv[2] = (uint32_t)__shfl((int)p0, src_b);
-        gv[3] = (uint32_t)__shfl((int)p1, src_b);
-        const half8_t x_last = takes_geo ? __builtin_bit_cast(half8_t, gv) : xf[IN_STEPS - 1];
+        const half8_t x_last = route.apply(o, g, 0, xf[IN_STEPS - 1]);
         float c[3] = {0.0f, 0.0f, 0.0f};  // colour of sample sl, meaningful in lanes g == 0
-        const float4_t oa = head(0, x_last);
+        const float4_t oa = head_tile<LIDAR>(frag, pre, g, 0, x_last);
         if constexpr (LIDAR) {
-            const float4_t ob = head(1, x_last);
+            const float4_t ob = head_tile<LIDAR>(frag, pre, g, 1, x_last);
             c[0] = sigmoid_f32(oa[0]);
             c[1] = sigmoid_f32(ob[0]);
         } else {
@@ -1478,6 +1492,24 @@ __device__ __forceinline__ float row16_scan_mul(float v) {  // inclusive product
     return v;
 }
 
+// Per-ray epilogue of the uniform render kernels: the lanes' partial sums -> weights_sum, depth, image (+ (1 - ws) * bg with use_bg).
+template <int C>
+__device__ __forceinline__ void store_ray(int lane, float ws, float dp, float (&img)[C], float bg0, float bg1, float bg2, int use_bg,
+                                          float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image) {
+    ws = wave_sum(ws);
+    dp = wave_sum(dp);
+#pragma unroll
+    for (int k = 0; k < C; ++k) img[k] = wave_sum(img[k]);
+    if (lane == 0) {
+        *weights_sum = ws;
+        *depth = dp;
+        const float bg[3] = {bg0, bg1, bg2};
+        const float rest = use_bg ? 1.0f - ws : 0.0f;
+#pragma unroll
+        for (int k = 0; k < C; ++k) image[k] = use_bg ? img[k] + rest * bg[k] : img[k];
+    }
+}
+
 // What the TRAINING form of the render kernels keeps beside z_vals / weights (ops.RenderRaysFn): everything the backward of the
 // whole render reads -- unit-cube positions (table scatter), the 32 encoded features as fp16 rows in level order (the density MLP's
 // backward recomputes its hidden layer from them), sigma (compositor backward), the geometry rows (h1 .. h15, 1.0) the heads'
@@ -1504,11 +1536,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     __shared__ uint4 s_lv[kMaxLevels];
     __shared__ half8_t s_frag[FR::kCount * kWave];
     __shared__ float4_t s_pre[kWavesPerBlock * FR::kPre];
-    if (threadIdx.x < kMaxLevels) {
-        const uint32_t l = threadIdx.x;
-        s_lv[l] = make_uint4(__builtin_bit_cast(uint32_t, meta.scale[l]), meta.res[l], meta.offset[l] * (uint32_t)(F * sizeof(_Float16)),
-                             meta.offset[l + 1] - meta.offset[l]);
-    }
+    fill_level_table<F>(s_lv, meta);
     const int lane = lane_id(), g = lane >> 4, c = lane & 15;
     for (int f = (int)(threadIdx.x >> 6); f < FR::kCount; f += kWavesPerBlock) s_frag[f * kWave + lane] = occ_fragment<LIDAR>(f, lane, w_sigma, w_a, w_b);
     __syncthreads();
@@ -1528,58 +1556,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     const float rd0 = rb.rays_d[3 * (size_t)n], rd1 = rb.rays_d[3 * (size_t)n + 1], rd2 = rb.rays_d[3 * (size_t)n + 2];
     const float d0 = (rd0 + 1.0f) / 2.0f, d1 = (rd1 + 1.0f) / 2.0f, d2 = (rd2 + 1.0f) / 2.0f;
     half8_t xf[IN_STEPS];
-    if constexpr (!LIDAR) {
-        float sh[16];
-        sh4_basis(d0, d1, d2, sh);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xf[0][j] = (_Float16)(g == 0 ? sh[j] : sh[8 + j]);
-    } else {
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                const int k = 32 * s + 8 * g + j;
-                float sn = 1.0f, cs = 1.0f;
-                if (k < 72) {
-                    const int i = k / 24, f = (k - 24 * i) >> 1;
-                    freq_pair(i == 0 ? d0 : (i == 1 ? d1 : d2), f, sn, cs);
-                }
-                xf[s][j] = (_Float16)sn;
-                xf[s][j + 1] = (_Float16)cs;
-            }
-    }
-    const bool takes_geo = LIDAR ? (g == 1 || g == 2) : (g >= 2);
-    const int src_a = (c + 16 * (LIDAR ? 2 * (g - 1) : 2 * (g - 2))) & 63, src_b = (src_a + 16) & 63;
+    encode_ray_direction<LIDAR>(d0, d1, d2, g, xf);
+    const GeoRoute<LIDAR> route(g, lane & 15);
     float4_t* pre = s_pre + (threadIdx.x >> 6) * FR::kPre;
     ray_head_constants<LIDAR>(xf, w_a, w_b, lane, pre);
-    auto head = [&](int hd, const half8_t& x_last) {
-        const int base = FR::kHead + hd * FR::kPerHead;
-        float4_t acc[kHidTiles];
-#pragma unroll
-        for (int t = 0; t < kHidTiles; ++t) {
-            float4_t c = {0, 0, 0, 0};
-            if constexpr (IN_STEPS > 1) c = pre[(hd * 4 + t) * 4 + g];
-            acc[t] = mfma16(frag[(base + t) * kWave], x_last, c);
-        }
-        half8_t h[kHidSteps];
-        pack_hidden(acc, h);
-#pragma unroll
-        for (int t = 0; t < kHidTiles; ++t) {
-            float4_t c = {0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < kHidSteps; ++s) c = mfma16(frag[(base + 4 + 2 * t + s) * kWave], h[s], c);
-            acc[t] = c;
-        }
-        pack_hidden(acc, h);
-        float4_t c = {0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < kHidSteps; ++s) c = mfma16(frag[(base + 4 + 8 + s) * kWave], h[s], c);
-        return c;
-    };
 
     const float near = rb.nears[n], range = rb.fars[n] - near;
     const float sample_dist = range / (float)T;
-    const float ox = rb.rays_o[3 * (size_t)n], oy = rb.rays_o[3 * (size_t)n + 1], oz = rb.rays_o[3 * (size_t)n + 2];
+    const float ro[3] = {rb.rays_o[3 * (size_t)n], rb.rays_o[3 * (size_t)n + 1], rb.rays_o[3 * (size_t)n + 2]}, rd[3] = {rd0, rd1, rd2};
     const size_t row0 = (size_t)n * T;
     float carry = 1.0f, ws = 0.0f, dp = 0.0f, img[C];
 #pragma unroll
@@ -1614,17 +1598,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             const u4_t packed = {p0.x, p1.x, p1.y, p0.y};
             feat8 = __builtin_bit_cast(half8_t, packed);
         } else {
-            z = near + range * lin_cur;
-            z_next = near + range * lin_nxt;
-            if (rb.noise) {
-                z = z + (nz_cur - 0.5f) * sample_dist;
-                z_next = z_next + (nz_nxt - 0.5f) * sample_dist;
-            }
+            z = sample_z(rb, near, range, lin_cur, &nz_cur);
+            z_next = sample_z(rb, near, range, lin_nxt, &nz_nxt);
             if (i0 + 16u < T) request(i0 + 16u);
             float x[3];
-            x[0] = (fminf(fmaxf(ox + rd0 * z, rb.lo[0]), rb.hi[0]) + rb.bound) * rb.inv_extent;
-            x[1] = (fminf(fmaxf(oy + rd1 * z, rb.lo[1]), rb.hi[1]) + rb.bound) * rb.inv_extent;
-            x[2] = (fminf(fmaxf(oz + rd2 * z, rb.lo[2]), rb.hi[2]) + rb.bound) * rb.inv_extent;
+            sample_x01(rb, ro, rd, z, x);
             feat8 = density_encode<F, 4, true, FH>(cx, x);
             if constexpr (TRAIN) {
                 if (g == 0 && valid) { rt.x01[3 * s] = x[0]; rt.x01[3 * s + 1] = x[1]; rt.x01[3 * s + 2] = x[2]; }
@@ -1632,18 +1610,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         }
         if constexpr (TRAIN) store_feat_row_swap(rt.feat, s, g, __builtin_bit_cast(uint4, feat8), valid);
         // ---- sigma MLP
-        float4_t o;
-        {
-            float4_t acc1[kHidTiles];
-#pragma unroll
-            for (int tt = 0; tt < kHidTiles; ++tt) acc1[tt] = mfma16(frag[(FR::kSigma + tt) * kWave], feat8, float4_t{0, 0, 0, 0});
-            half8_t h[kHidSteps];
-            pack_hidden(acc1, h);
-            float4_t a = {0, 0, 0, 0};
-#pragma unroll
-            for (int sx = 0; sx < kHidSteps; ++sx) a = mfma16(frag[(FR::kSigma + 4 + sx) * kWave], h[sx], a);
-            o = a;
-        }
+        const float4_t o = sigma_tile<LIDAR>(frag, feat8);
         // ---- alpha compositing of the tile (renderer_dynamic.py:176-194); lanes g == 3 hold sigma of sample c
         const float delta = (i + 1u < T) ? z_next - z : sample_dist;
         float alpha = 0.0f;
@@ -1670,17 +1637,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             if (valid) *reinterpret_cast<uint2*>(rt.geo + s * 16 + 4 * g) = make_uint2(pack_h2(o[0], o[1]), pack_h2(o[2], g == 3 ? 1.0f : o[3]));
         }
         if (__ballot(w > w_thresh)) {  // w is zero outside lane group 3: the same set of samples
-            const uint32_t p0 = pack_h2(o[0], o[1]), p1 = pack_h2(o[2], g == 3 ? 1.0f : o[3]);
-            typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
-            u4_t gv;
-            gv[0] = (uint32_t)__shfl((int)p0, src_a);
-            gv[1] = (uint32_t)__shfl((int)p1, src_a);
-            gv[2] = (uint32_t)__shfl((int)p0, src_b);
-            gv[3] = (uint32_t)__shfl((int)p1, src_b);
-            const half8_t x_last = takes_geo ? __builtin_bit_cast(half8_t, gv) : xf[IN_STEPS - 1];
-            const float4_t oa = head(0, x_last);
+            const half8_t x_last = route.apply(o, g, 0, xf[IN_STEPS - 1]);
+            const float4_t oa = head_tile<LIDAR>(frag, pre, g, 0, x_last);
             if constexpr (LIDAR) {
-                const float4_t ob = head(1, x_last);
+                const float4_t ob = head_tile<LIDAR>(frag, pre, g, 1, x_last);
                 if (g == 0 && on) {
                     cr[0] = sigmoid_f32(oa[0]);
                     cr[1] = sigmoid_f32(ob[0]);
@@ -1704,18 +1664,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             }
         }
     }
-    ws = wave_sum(ws);
-    dp = wave_sum(dp);
-#pragma unroll
-    for (int k = 0; k < C; ++k) img[k] = wave_sum(img[k]);
-    if (lane == 0) {
-        weights_sum[n] = ws;
-        depth[n] = dp;
-        const float bg[3] = {bg0, bg1, bg2};
-        const float rest = use_bg ? 1.0f - ws : 0.0f;
-#pragma unroll
-        for (int k = 0; k < C; ++k) image[(size_t)n * C + k] = use_bg ? img[k] + rest * bg[k] : img[k];
-    }
+    store_ray<C>(lane, ws, dp, img, bg0, bg1, bg2, use_bg, weights_sum + n, depth + n, image + (size_t)n * C);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1753,70 +1702,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     const float rd0 = rb.rays_d[3 * (size_t)n], rd1 = rb.rays_d[3 * (size_t)n + 1], rd2 = rb.rays_d[3 * (size_t)n + 2];
     const float d0 = (rd0 + 1.0f) / 2.0f, d1 = (rd1 + 1.0f) / 2.0f, d2 = (rd2 + 1.0f) / 2.0f;
     half8_t xf[IN_STEPS];
-    if constexpr (!LIDAR) {
-        float sh[16];
-        sh4_basis(d0, d1, d2, sh);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xf[0][j] = (_Float16)(g == 0 ? sh[j] : sh[8 + j]);
-    } else {
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                const int k = 32 * s + 8 * g + j;
-                float sn = 1.0f, cs = 1.0f;
-                if (k < 72) {
-                    const int i = k / 24, f = (k - 24 * i) >> 1;
-                    freq_pair(i == 0 ? d0 : (i == 1 ? d1 : d2), f, sn, cs);
-                }
-                xf[s][j] = (_Float16)sn;
-                xf[s][j + 1] = (_Float16)cs;
-            }
-    }
-    const bool takes_geo = LIDAR ? (g == 1 || g == 2) : (g >= 2);
-    const int src_a = (c + 16 * (LIDAR ? 2 * (g - 1) : 2 * (g - 2))) & 63, src_b = (src_a + 16) & 63;
-    const int src_a1 = (src_a + 48) & 63, src_b1 = (src_b + 48) & 63;  // tile 2j + 1: its output rows sit one lane group lower
+    encode_ray_direction<LIDAR>(d0, d1, d2, g, xf);
+    const GeoRoute<LIDAR> route(g, lane & 15);
     float4_t* pre = s_pre + (threadIdx.x >> 6) * FR::kPre;
     ray_head_constants<LIDAR>(xf, w_a, w_b, lane, pre);
-    // one head on both tiles: every fragment read feeds two MFMAs
-    auto head2 = [&](int hd, const half8_t (&x_last)[2], float4_t (&out)[2]) {
-        const int base = FR::kHead + hd * FR::kPerHead;
-        float4_t acc[2][kHidTiles];
-#pragma unroll
-        for (int t = 0; t < kHidTiles; ++t) {
-            float4_t c = {0, 0, 0, 0};
-            if constexpr (IN_STEPS > 1) c = pre[(hd * 4 + t) * 4 + g];
-            const half8_t w = frag[(base + t) * kWave];
-            acc[0][t] = mfma16(w, x_last[0], c);
-            acc[1][t] = mfma16(w, x_last[1], c);
-        }
-        half8_t h[2][kHidSteps];
-        pack_hidden(acc[0], h[0]);
-        pack_hidden(acc[1], h[1]);
-#pragma unroll
-        for (int t = 0; t < kHidTiles; ++t) {
-            float4_t a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < kHidSteps; ++s) {
-                const half8_t w = frag[(base + 4 + 2 * t + s) * kWave];
-                a0 = mfma16(w, h[0][s], a0);
-                a1 = mfma16(w, h[1][s], a1);
-            }
-            acc[0][t] = a0;
-            acc[1][t] = a1;
-        }
-        pack_hidden(acc[0], h[0]);
-        pack_hidden(acc[1], h[1]);
-        float4_t a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < kHidSteps; ++s) {
-            const half8_t w = frag[(base + 4 + 8 + s) * kWave];
-            a0 = mfma16(w, h[0][s], a0);
-            a1 = mfma16(w, h[1][s], a1);
-        }
-        out[0] = a0;
-        out[1] = a1;
-    };
 
     const float sample_dist = (rb.fars[n] - rb.nears[n]) / (float)T;
     const size_t row0 = (size_t)n * T;
@@ -1942,21 +1831,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         // ---- heads on the samples that carry weight (the test reads the weights where they are: zero outside lane groups 2, 3)
         if (__ballot(w > w_thresh)) {
             half8_t x_last[2];
+            // tile 2j + 1: its output rows sit one lane group lower
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const uint32_t p0 = pack_h2(o[u][0], o[u][1]), p1 = pack_h2(o[u][2], g == 3 - u ? 1.0f : o[u][3]);
-                u4_t gv;
-                gv[0] = (uint32_t)__shfl((int)p0, u ? src_a1 : src_a);
-                gv[1] = (uint32_t)__shfl((int)p1, u ? src_a1 : src_a);
-                gv[2] = (uint32_t)__shfl((int)p0, u ? src_b1 : src_b);
-                gv[3] = (uint32_t)__shfl((int)p1, u ? src_b1 : src_b);
-                x_last[u] = takes_geo ? __builtin_bit_cast(half8_t, gv) : xf[IN_STEPS - 1];
-            }
+            for (int u = 0; u < 2; ++u) x_last[u] = route.apply(o[u], g, u, xf[IN_STEPS - 1]);
             float4_t oa[2];
-            head2(0, x_last, oa);
+            head_tiles<LIDAR, 2>(frag, pre, g, 0, x_last, oa);
             if constexpr (LIDAR) {
                 float4_t ob[2];
-                head2(1, x_last, ob);
+                head_tiles<LIDAR, 2>(frag, pre, g, 1, x_last, ob);
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
                     if (g == 0 && on[u]) {
@@ -1988,18 +1870,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         cur[0] = nxt[0];
         cur[1] = nxt[1];
     }
-    ws = wave_sum(ws);
-    dp = wave_sum(dp);
-#pragma unroll
-    for (int k = 0; k < C; ++k) img[k] = wave_sum(img[k]);
-    if (lane == 0) {
-        weights_sum[n] = ws;
-        depth[n] = dp;
-        const float bg[3] = {bg0, bg1, bg2};
-        const float rest = use_bg ? 1.0f - ws : 0.0f;
-#pragma unroll
-        for (int k = 0; k < C; ++k) image[(size_t)n * C + k] = use_bg ? img[k] + rest * bg[k] : img[k];
-    }
+    store_ray<C>(lane, ws, dp, img, bg0, bg1, bg2, use_bg, weights_sum + n, depth + n, image + (size_t)n * C);
 }
 
 int fill_meta(GridMeta& meta, uint32_t L, const float* scales, const uint32_t* res, const uint32_t* offsets) {
@@ -2013,9 +1884,55 @@ int fill_meta(GridMeta& meta, uint32_t L, const float* scales, const uint32_t* r
     meta.offset[L] = offsets[L];
     return NVSF_OK;
 }
-}  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
+// What the launchers ask about a grid.  `dense_first`: dense levels first, hashed levels after (true for any per_level_scale >= 1)
+// and every hashed level with a power-of-two number of rows -- what every kernel here except k_density_uniform is built for.
+struct GridInfo {
+    GridMeta meta;
+    uint32_t first_hashed;  // L: no hashed level
+    bool dense_first;
+    unsigned long long table_bytes;
+};
+
+int classify_grid(GridInfo& gi, uint32_t L, uint32_t F, const float* h_scales, const uint32_t* h_res, const uint32_t* h_offsets) {
+    const int st = fill_meta(gi.meta, L, h_scales, h_res, h_offsets);
+    if (st != NVSF_OK) return st;
+    gi.first_hashed = L;
+    gi.dense_first = true;
+    for (uint32_t l = 0; l < L; ++l) {
+        const unsigned long long cells = (unsigned long long)h_res[l] * h_res[l] * h_res[l];
+        const uint32_t rows = h_offsets[l + 1] - h_offsets[l];
+        const bool hashed = cells > (unsigned long long)rows;
+        if (hashed && gi.first_hashed == L) gi.first_hashed = l;
+        if (!hashed && gi.first_hashed != L) gi.dense_first = false;
+        if (hashed && (rows & (rows - 1u)) != 0u) gi.dense_first = false;
+    }
+    gi.table_bytes = (unsigned long long)h_offsets[L] * F * sizeof(_Float16);
+    return NVSF_OK;
+}
+
+RayBatch make_ray_batch(const float* rays_o, const float* rays_d, const float* nears, const float* fars, const float* lin, const float* noise,
+                        const float* h_aabb, float bound, uint32_t N, uint32_t T) {
+    RayBatch rb;
+    rb.rays_o = rays_o; rb.rays_d = rays_d; rb.nears = nears; rb.fars = fars; rb.lin = lin; rb.noise = noise;
+    for (int k = 0; k < 3; ++k) { rb.lo[k] = h_aabb[k]; rb.hi[k] = h_aabb[3 + k]; }
+    rb.bound = bound;
+    rb.inv_extent = 1.0f / (2.0f * bound);
+    rb.N = N; rb.T = T;
+    return rb;
+}
+
+// The fp16 parameter blocks of a field as the kernels take them, and the background colour (zeros without one).
+struct FieldParams {
+    const _Float16 *table, *sigma, *head_a, *head_b;
+    float bg[3];
+    FieldParams(const void* table_f16, const void* sigma_f16, const void* head_a_f16, const void* head_b_f16, const float* h_bg_color)
+        : table(reinterpret_cast<const _Float16*>(table_f16)), sigma(reinterpret_cast<const _Float16*>(sigma_f16)),
+          head_a(reinterpret_cast<const _Float16*>(head_a_f16)), head_b(reinterpret_cast<const _Float16*>(head_b_f16)) {
+        for (int k = 0; k < 3; ++k) bg[k] = h_bg_color ? h_bg_color[k] : 0.0f;
+    }
+};
+}  // namespace
 
 static int density_uniform_impl(const float* rays_o, const float* rays_d, const float* nears, const float* fars,
                                 const float* lin, const float* noise, const float* h_aabb, float bound, uint32_t N,
@@ -2029,103 +1946,69 @@ static int density_uniform_impl(const float* rays_o, const float* rays_d, const 
     REQUIRE((reinterpret_cast<uintptr_t>(table_f16) & 15u) == 0 && (reinterpret_cast<uintptr_t>(sigma_weights_f16) & 15u) == 0 &&
             (reinterpret_cast<uintptr_t>(geo_f16) & 15u) == 0);
     if (L * F != 32 || (F != 2 && F != 4)) return NVSF_ERR_UNSUPPORTED;
-    GridMeta meta;
-    const int st = fill_meta(meta, L, h_scales, h_res, h_offsets);
+    GridInfo gi;
+    const int st = classify_grid(gi, L, F, h_scales, h_res, h_offsets);
     if (st != NVSF_OK) return st;
-    RayBatch rb;
-    rb.rays_o = rays_o; rb.rays_d = rays_d; rb.nears = nears; rb.fars = fars; rb.lin = lin; rb.noise = noise;
-    for (int k = 0; k < 3; ++k) { rb.lo[k] = h_aabb[k]; rb.hi[k] = h_aabb[3 + k]; }
-    rb.bound = bound;
-    rb.inv_extent = 1.0f / (2.0f * bound);
-    rb.N = N; rb.T = T;
+    const RayBatch rb = make_ray_batch(rays_o, rays_d, nears, fars, lin, noise, h_aabb, bound, N, T);
     const unsigned long long n_tiles = ((unsigned long long)N * T + 15) / 16;
     const unsigned long long want = (n_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
     const uint32_t blocks = (uint32_t)(want < 4096ull ? want : 4096ull);
-    const _Float16* tb = reinterpret_cast<const _Float16*>(table_f16);
-    const _Float16* ws = reinterpret_cast<const _Float16*>(sigma_weights_f16);
+    const FieldParams w(table_f16, sigma_weights_f16, nullptr, nullptr, nullptr);
     _Float16* gp = reinterpret_cast<_Float16*>(geo_f16);
-    // v2 needs "dense levels first, hashed levels after" (true for any per_level_scale >= 1) and a table < 2 GiB
-    uint32_t first_hashed = L;
-    bool monotone = true;
-    for (uint32_t l = 0; l < L; ++l) {
-        const unsigned long long cells = (unsigned long long)h_res[l] * h_res[l] * h_res[l];
-        const bool hashed = cells > (unsigned long long)(h_offsets[l + 1] - h_offsets[l]);
-        if (hashed && first_hashed == L) first_hashed = l;
-        if (!hashed && first_hashed != L) monotone = false;
-        if (hashed && ((h_offsets[l + 1] - h_offsets[l]) & (h_offsets[l + 1] - h_offsets[l] - 1u)) != 0u) monotone = false;
-    }
-    const unsigned long long table_bytes = (unsigned long long)h_offsets[L] * F * sizeof(_Float16);
+    const TrainOut tr = train ? *train : TrainOut();
+    const bool small_table = gi.table_bytes < (1ull << 31);  // gathers are buffer loads with 32-bit byte offsets
     if (sliced_passes) {
         const unsigned long long total = (unsigned long long)N * T;
         const bool f4 = F == 4 && L == 8;  // the reference-default shape: one level per XCD group (k_encode_sliced_f4), same planes
-        if (!(((F == 2 && L == 16) || f4) && monotone && table_bytes < (1ull << 31) && total < (f4 ? (1ull << 28) : (1ull << 32)))) return NVSF_ERR_UNSUPPORTED;
+        if (!(((F == 2 && L == 16) || f4) && gi.dense_first && small_table && total < (f4 ? (1ull << 28) : (1ull << 32)))) return NVSF_ERR_UNSUPPORTED;
         REQUIRE(feat_scratch && (reinterpret_cast<uintptr_t>(feat_scratch) & 15u) == 0);
         const uint32_t M = (uint32_t)total;
         uint2* fp = reinterpret_cast<uint2*>(feat_scratch);
-        if ((sliced_passes & 1u) && f4) {
-            const uint32_t units32 = (M + 31u) / 32u;
-            uint32_t ps = (units32 + kWavesPerBlock - 1) / kWavesPerBlock;
-            if (ps > 512u) ps = 512u;
-            const SlicePlan plan = slice_plan(units32, T, h_res, first_hashed, false);  // every group its own level
-            float* x01 = train ? train->x01 : nullptr;
-            if (T % 32u == 0u)
-                hipLaunchKernelGGL((k_encode_sliced_f4<true>), dim3(8u * ps), dim3(kBlock), 0, stream, rb, tb, (uint32_t)table_bytes, meta,
-                                   first_hashed, M, z_vals, reinterpret_cast<uint32_t*>(fp), plan, x01);
-            else
-                hipLaunchKernelGGL((k_encode_sliced_f4<false>), dim3(8u * ps), dim3(kBlock), 0, stream, rb, tb, (uint32_t)table_bytes, meta,
-                                   first_hashed, M, z_vals, reinterpret_cast<uint32_t*>(fp), plan, x01);
-        } else if (sliced_passes & 1u) {
+        if (sliced_passes & 1u) {
             const uint32_t units32 = (M + 31u) / 32u;
             uint32_t ps = (units32 + kWavesPerBlock - 1) / kWavesPerBlock;
             if (ps > 512u) ps = 512u;  // 32 CUs per XCD x 8 resident workgroups x 2 (measured: 256 -> 512 gains 1.5 %)
-            const SlicePlan plan = slice_plan(units32, T, h_res, first_hashed, nvsf_variant(kVarSlicePlan) == 0);  // 1 (tests): every group its own slice only
-            float* x01 = train ? train->x01 : nullptr;
-            if (T % 32u == 0u)
-                hipLaunchKernelGGL((k_encode_sliced_pairs<2, true>), dim3(8u * ps), dim3(kBlock), 0, stream, rb, tb, (uint32_t)table_bytes, meta, L,
-                                   first_hashed, M, z_vals, fp, plan, x01);
-            else
-                hipLaunchKernelGGL((k_encode_sliced_pairs<2, false>), dim3(8u * ps), dim3(kBlock), 0, stream, rb, tb, (uint32_t)table_bytes, meta,
-                                   L, first_hashed, M, z_vals, fp, plan, x01);
+            // L16 F2: balanced slices (kVarSlicePlan 1 (tests): every group its own slice only); L8 F4: every group its own level
+            const SlicePlan plan = slice_plan(units32, T, h_res, gi.first_hashed, !f4 && nvsf_variant(kVarSlicePlan) == 0);
+            const dim3 grid(8u * ps), block(kBlock);
+            const bool uniform_ray = T % 32u == 0u;
+#define LAUNCH_ENCODE(KERNEL, ...) \
+    hipLaunchKernelGGL((KERNEL), grid, block, 0, stream, rb, w.table, (uint32_t)gi.table_bytes, gi.meta, __VA_ARGS__, plan, tr.x01)
+            if (f4) {
+                if (uniform_ray) LAUNCH_ENCODE(k_encode_sliced_f4<true>, gi.first_hashed, M, z_vals, reinterpret_cast<uint32_t*>(fp));
+                else LAUNCH_ENCODE(k_encode_sliced_f4<false>, gi.first_hashed, M, z_vals, reinterpret_cast<uint32_t*>(fp));
+            } else {
+                if (uniform_ray) LAUNCH_ENCODE((k_encode_sliced_pairs<2, true>), L, gi.first_hashed, M, z_vals, fp);
+                else LAUNCH_ENCODE((k_encode_sliced_pairs<2, false>), L, gi.first_hashed, M, z_vals, fp);
+            }
+#undef LAUNCH_ENCODE
         }
         const uint32_t tiles = (M + 15u) / 16u;
         uint32_t bb = (tiles + 4u * kWavesPerBlock - 1u) / (4u * kWavesPerBlock);
         if (bb > 4096u) bb = 4096u;
         if (sliced_passes & 2u) {
-            if (train) hipLaunchKernelGGL((k_density_from_features<2, true>), dim3(bb), dim3(kBlock), 0, stream, fp, M, L, ws, sigmas, gp, *train);
-            else hipLaunchKernelGGL((k_density_from_features<2, false>), dim3(bb), dim3(kBlock), 0, stream, fp, M, L, ws, sigmas, gp, TrainOut());
+            if (train) hipLaunchKernelGGL((k_density_from_features<2, true>), dim3(bb), dim3(kBlock), 0, stream, fp, M, L, w.sigma, sigmas, gp, tr);
+            else hipLaunchKernelGGL((k_density_from_features<2, false>), dim3(bb), dim3(kBlock), 0, stream, fp, M, L, w.sigma, sigmas, gp, tr);
         }
         return nvsf_launch_status();
     }
-    const bool use_v2 = F == 2 && monotone && table_bytes < (1ull << 31);  // else: the generic first formulation (any F with L F = 32)
-    if (train) {
-        if (!use_v2) return NVSF_ERR_UNSUPPORTED;
-        if (T % 16u == 0u) {
-            const uint32_t seg_tiles = 4u;
-            const unsigned long long units = (unsigned long long)N * ((T / 16 + seg_tiles - 1) / seg_tiles);
-            const uint32_t segb = (uint32_t)(units < 3072ull ? units : 3072ull);
-            hipLaunchKernelGGL((k_density_uniform_v2<2, true, 4, true>), dim3(segb), dim3(kBlock), 0, stream, rb, tb, (uint32_t)table_bytes, meta,
-                               first_hashed, seg_tiles, ws, z_vals, sigmas, gp, *train);
-        } else {
-            hipLaunchKernelGGL((k_density_uniform_v2<2, false, 4, true>), dim3(blocks), dim3(kBlock), 0, stream, rb, tb, (uint32_t)table_bytes, meta,
-                               first_hashed, 0u, ws, z_vals, sigmas, gp, *train);
-        }
-        return nvsf_launch_status();
-    }
+    const bool use_v2 = F == 2 && gi.dense_first && small_table;  // else: the generic first formulation (any F with L F = 32)
+    if (train && !use_v2) return NVSF_ERR_UNSUPPORTED;
     if (use_v2) {
-        const bool seg = T % 16u == 0u;
-        if (seg) {
-            const uint32_t seg_tiles = 4u;  // 4 tiles = one round of the 4 waves (measured best)
-            const unsigned long long units = (unsigned long long)N * ((T / 16 + seg_tiles - 1) / seg_tiles);
-            const uint32_t segb = (uint32_t)(units < 3072ull ? units : 3072ull);  // 256 CUs x 3 workgroups (VGPR-limited residency) x 4
-            hipLaunchKernelGGL((k_density_uniform_v2<2, true, 4, false>), dim3(segb), dim3(kBlock), 0, stream, rb, tb, (uint32_t)table_bytes, meta,
-                               first_hashed, seg_tiles, ws, z_vals, sigmas, gp, TrainOut());
-        } else {
-            hipLaunchKernelGGL((k_density_uniform_v2<2, false, 4, false>), dim3(blocks), dim3(kBlock), 0, stream, rb, tb, (uint32_t)table_bytes, meta,
-                               first_hashed, 0u, ws, z_vals, sigmas, gp, TrainOut());
-        }
+        const bool seg = T % 16u == 0u;  // whole tiles per ray: ray segments owned by a workgroup, else the generic tile loop
+        const uint32_t seg_tiles = 4u;   // 4 tiles = one round of the 4 waves (measured best)
+        const unsigned long long units = (unsigned long long)N * ((T / 16 + seg_tiles - 1) / seg_tiles);
+        const uint32_t segb = (uint32_t)(units < 3072ull ? units : 3072ull);  // 256 CUs x 3 workgroups (VGPR-limited residency) x 4
+        const dim3 grid(seg ? segb : blocks);
+#define LAUNCH_V2(SEG, TRAIN)                                                                                                          \
+    hipLaunchKernelGGL((k_density_uniform_v2<2, SEG, 4, TRAIN>), grid, dim3(kBlock), 0, stream, rb, w.table, (uint32_t)gi.table_bytes, \
+                       gi.meta, gi.first_hashed, SEG ? seg_tiles : 0u, w.sigma, z_vals, sigmas, gp, tr)
+        if (seg) { if (train) LAUNCH_V2(true, true); else LAUNCH_V2(true, false); }
+        else { if (train) LAUNCH_V2(false, true); else LAUNCH_V2(false, false); }
+#undef LAUNCH_V2
     }
-    else if (F == 2) hipLaunchKernelGGL(k_density_uniform<2>, dim3(blocks), dim3(kBlock), 0, stream, rb, tb, meta, ws, z_vals, sigmas, gp);
-    else hipLaunchKernelGGL(k_density_uniform<4>, dim3(blocks), dim3(kBlock), 0, stream, rb, tb, meta, ws, z_vals, sigmas, gp);
+    else if (F == 2) hipLaunchKernelGGL(k_density_uniform<2>, dim3(blocks), dim3(kBlock), 0, stream, rb, w.table, gi.meta, w.sigma, z_vals, sigmas, gp);
+    else hipLaunchKernelGGL(k_density_uniform<4>, dim3(blocks), dim3(kBlock), 0, stream, rb, w.table, gi.meta, w.sigma, z_vals, sigmas, gp);
     return nvsf_launch_status();
 }
 
@@ -2202,33 +2085,20 @@ NVSF_API int nvsf_render_occupancy_fwd(const float* rays_o, const float* rays_d,
     REQUIRE((reinterpret_cast<uintptr_t>(table_f16) & 15u) == 0 && (reinterpret_cast<uintptr_t>(sigma_weights_f16) & 15u) == 0 &&
             (reinterpret_cast<uintptr_t>(head_a_weights_f16) & 15u) == 0 && (reinterpret_cast<uintptr_t>(head_b_weights_f16) & 15u) == 0);
     if ((F != 2 && F != 4) || L * F != 32) return NVSF_ERR_UNSUPPORTED;  // 16 levels x 2 (BASELINE config 2) or 8 x 4 (the reference default)
-    GridMeta meta;
-    const int st = fill_meta(meta, L, h_scales, h_res, h_offsets);
+    GridInfo gi;
+    const int st = classify_grid(gi, L, F, h_scales, h_res, h_offsets);
     if (st != NVSF_OK) return st;
-    uint32_t first_hashed = L;
-    for (uint32_t l = 0; l < L; ++l) {
-        const unsigned long long cells = (unsigned long long)h_res[l] * h_res[l] * h_res[l];
-        const uint32_t rows = h_offsets[l + 1] - h_offsets[l];
-        const bool hashed = cells > (unsigned long long)rows;
-        if (hashed && first_hashed == L) first_hashed = l;
-        if (!hashed && first_hashed != L) return NVSF_ERR_UNSUPPORTED;         // dense levels must come first
-        if (hashed && (rows & (rows - 1u)) != 0u) return NVSF_ERR_UNSUPPORTED;  // hashed levels: power-of-two rows
-    }
-    const unsigned long long table_bytes = (unsigned long long)h_offsets[L] * F * sizeof(_Float16);
-    if (table_bytes >= (1ull << 31)) return NVSF_ERR_UNSUPPORTED;
+    if (!gi.dense_first || gi.table_bytes >= (1ull << 31)) return NVSF_ERR_UNSUPPORTED;
     OccRays rr;
     rr.rays_o = rays_o; rr.rays_d = rays_d; rr.nears = nears; rr.fars = fars; rr.grid = grid;
     rr.bound = bound; rr.dt_gamma = dt_gamma; rr.max_steps = max_steps; rr.C = C; rr.H = H; rr.N = N;
-    const _Float16* tb = reinterpret_cast<const _Float16*>(table_f16);
-    const _Float16* ws = reinterpret_cast<const _Float16*>(sigma_weights_f16);
-    const _Float16* wa = reinterpret_cast<const _Float16*>(head_a_weights_f16);
-    const _Float16* wb = reinterpret_cast<const _Float16*>(head_b_weights_f16);
-    const float b0 = h_bg_color ? h_bg_color[0] : 0.0f, b1 = h_bg_color ? h_bg_color[1] : 0.0f, b2 = h_bg_color ? h_bg_color[2] : 0.0f;
+    const FieldParams w(table_f16, sigma_weights_f16, head_a_weights_f16, head_b_weights_f16, h_bg_color);
     const dim3 grid_dim(cdiv(N, kWavesPerBlock)), block(kBlock);
 #define LAUNCH_OCC(LD, FF, FH)                                                                                                            \
-    hipLaunchKernelGGL((k_render_occupancy_lds<LD, FF, FH>), grid_dim, block, 0, stream, rr, tb, (uint32_t)table_bytes, meta, first_hashed, ws, \
-                       wa, wb, density_scale, T_thresh, b0, b1, b2, weights_sum, depth, image)
-    const bool c2_grid = F == 2 && first_hashed == kFirstHashedC2 && nvsf_variant(kVarLevelKinds) == 0;  // the instance with the level kinds compiled in (density_encode)
+    hipLaunchKernelGGL((k_render_occupancy_lds<LD, FF, FH>), grid_dim, block, 0, stream, rr, w.table, (uint32_t)gi.table_bytes, gi.meta,       \
+                       gi.first_hashed, w.sigma, w.head_a, w.head_b, density_scale, T_thresh, w.bg[0], w.bg[1], w.bg[2], weights_sum, depth, \
+                       image)
+    const bool c2_grid = F == 2 && gi.first_hashed == kFirstHashedC2 && nvsf_variant(kVarLevelKinds) == 0;  // the instance with the level kinds compiled in (density_encode)
     if (lidar) { if (c2_grid) LAUNCH_OCC(true, 2, (int)kFirstHashedC2); else if (F == 2) LAUNCH_OCC(true, 2, -1); else LAUNCH_OCC(true, 4, -1); }
     else { if (c2_grid) LAUNCH_OCC(false, 2, (int)kFirstHashedC2); else if (F == 2) LAUNCH_OCC(false, 2, -1); else LAUNCH_OCC(false, 4, -1); }
 #undef LAUNCH_OCC
@@ -2253,59 +2123,41 @@ static int render_uniform_impl(const float* rays_o, const float* rays_d, const f
     // L16 F2 (BASELINE config 2): gathers in the render kernel or feature planes; L8 F4 (the reference-default grid): feature planes
     // only -- the streaming tails read column pairs and do not know which shape produced them (k_encode_sliced_f4)
     if (!((F == 2 && L == 16) || (F == 4 && L == 8 && feat_scratch))) return NVSF_ERR_UNSUPPORTED;
-    GridMeta meta;
-    const int st = fill_meta(meta, L, h_scales, h_res, h_offsets);
+    GridInfo gi;
+    const int st = classify_grid(gi, L, F, h_scales, h_res, h_offsets);
     if (st != NVSF_OK) return st;
-    uint32_t first_hashed = L;
-    for (uint32_t l = 0; l < L; ++l) {
-        const unsigned long long cells = (unsigned long long)h_res[l] * h_res[l] * h_res[l];
-        const uint32_t rows = h_offsets[l + 1] - h_offsets[l];
-        const bool hashed = cells > (unsigned long long)rows;
-        if (hashed && first_hashed == L) first_hashed = l;
-        if (!hashed && first_hashed != L) return NVSF_ERR_UNSUPPORTED;
-        if (hashed && (rows & (rows - 1u)) != 0u) return NVSF_ERR_UNSUPPORTED;
-    }
-    const unsigned long long table_bytes = (unsigned long long)h_offsets[L] * F * sizeof(_Float16);
-    if (table_bytes >= (1ull << 31)) return NVSF_ERR_UNSUPPORTED;
-    RayBatch rb;
-    rb.rays_o = rays_o; rb.rays_d = rays_d; rb.nears = nears; rb.fars = fars; rb.lin = lin; rb.noise = noise;
-    for (int k = 0; k < 3; ++k) { rb.lo[k] = h_aabb[k]; rb.hi[k] = h_aabb[3 + k]; }
-    rb.bound = bound;
-    rb.inv_extent = 1.0f / (2.0f * bound);
-    rb.N = N; rb.T = T;
-    const _Float16* tb = reinterpret_cast<const _Float16*>(table_f16);
-    const _Float16* ws = reinterpret_cast<const _Float16*>(sigma_weights_f16);
-    const _Float16* wa = reinterpret_cast<const _Float16*>(head_a_weights_f16);
-    const _Float16* wb = reinterpret_cast<const _Float16*>(head_b_weights_f16);
+    if (!gi.dense_first || gi.table_bytes >= (1ull << 31)) return NVSF_ERR_UNSUPPORTED;
+    const RayBatch rb = make_ray_batch(rays_o, rays_d, nears, fars, lin, noise, h_aabb, bound, N, T);
+    const FieldParams w(table_f16, sigma_weights_f16, head_a_weights_f16, head_b_weights_f16, h_bg_color);
     const uint2* fp = reinterpret_cast<const uint2*>(feat_scratch);
-    const float b0 = h_bg_color ? h_bg_color[0] : 0.0f, b1 = h_bg_color ? h_bg_color[1] : 0.0f, b2 = h_bg_color ? h_bg_color[2] : 0.0f;
+    const RenderTrainOut rt = train ? *train : RenderTrainOut();
     const int use_bg = (h_bg_color && !lidar) ? 1 : 0;
     const dim3 grid_dim(cdiv(N, kWavesPerBlock)), block(kBlock);
 #define LAUNCH_RU_FH(LD, FF, FH)                                                                                                      \
     do {                                                                                                                              \
         if (train)                                                                                                                    \
-            hipLaunchKernelGGL((k_render_uniform<LD, FF, true, FH>), grid_dim, block, 0, stream, rb, tb, (uint32_t)table_bytes, meta, \
-                               first_hashed, fp, ws, wa, wb, k_scale, w_thresh, b0, b1, b2, use_bg, z_vals, weights, weights_sum,     \
-                               depth, image, *train);                                                                                \
+            hipLaunchKernelGGL((k_render_uniform<LD, FF, true, FH>), grid_dim, block, 0, stream, rb, w.table, (uint32_t)gi.table_bytes, gi.meta, \
+                               gi.first_hashed, fp, w.sigma, w.head_a, w.head_b, k_scale, w_thresh, w.bg[0], w.bg[1], w.bg[2], use_bg, z_vals,   \
+                               weights, weights_sum, depth, image, rt);                                                               \
         else                                                                                                                          \
-            hipLaunchKernelGGL((k_render_uniform<LD, FF, false, FH>), grid_dim, block, 0, stream, rb, tb, (uint32_t)table_bytes,      \
-                               meta, first_hashed, fp, ws, wa, wb, k_scale, w_thresh, b0, b1, b2, use_bg, z_vals, weights,            \
-                               weights_sum, depth, image, RenderTrainOut());                                                         \
+            hipLaunchKernelGGL((k_render_uniform<LD, FF, false, FH>), grid_dim, block, 0, stream, rb, w.table, (uint32_t)gi.table_bytes, gi.meta, \
+                               gi.first_hashed, fp, w.sigma, w.head_a, w.head_b, k_scale, w_thresh, w.bg[0], w.bg[1], w.bg[2], use_bg, z_vals,    \
+                               weights, weights_sum, depth, image, rt);                                                               \
     } while (0)
     // the gathering form has an instance for the grid of BASELINE config 2 (levels 0-4 dense, 5-15 hashed) beside the general one
 #define LAUNCH_RU(LD, FF)                                                                                                             \
     do {                                                                                                                              \
-        if (!FF && first_hashed == kFirstHashedC2 && nvsf_variant(kVarLevelKinds) == 0) LAUNCH_RU_FH(LD, FF, (FF ? -1 : (int)kFirstHashedC2)); \
+        if (!FF && gi.first_hashed == kFirstHashedC2 && nvsf_variant(kVarLevelKinds) == 0) LAUNCH_RU_FH(LD, FF, (FF ? -1 : (int)kFirstHashedC2)); \
         else LAUNCH_RU_FH(LD, FF, -1);                                                                                                \
     } while (0)
 #define LAUNCH_TAIL(LD)                                                                                                               \
     do {                                                                                                                              \
         if (train)                                                                                                                    \
-            hipLaunchKernelGGL((k_render_tail2<LD, true>), grid_dim, block, 0, stream, rb, fp, ws, wa, wb, k_scale, w_thresh, b0, b1, \
-                               b2, use_bg, z_vals, weights, weights_sum, depth, image, *train);                                      \
+            hipLaunchKernelGGL((k_render_tail2<LD, true>), grid_dim, block, 0, stream, rb, fp, w.sigma, w.head_a, w.head_b, k_scale, w_thresh, \
+                               w.bg[0], w.bg[1], w.bg[2], use_bg, z_vals, weights, weights_sum, depth, image, rt);                    \
         else                                                                                                                          \
-            hipLaunchKernelGGL((k_render_tail2<LD, false>), grid_dim, block, 0, stream, rb, fp, ws, wa, wb, k_scale, w_thresh, b0,    \
-                               b1, b2, use_bg, z_vals, weights, weights_sum, depth, image, RenderTrainOut());                        \
+            hipLaunchKernelGGL((k_render_tail2<LD, false>), grid_dim, block, 0, stream, rb, fp, w.sigma, w.head_a, w.head_b, k_scale, w_thresh, \
+                               w.bg[0], w.bg[1], w.bg[2], use_bg, z_vals, weights, weights_sum, depth, image, rt);                    \
     } while (0)
     const bool tail2 = nvsf_variant(kVarRenderTail) == 0;  // 1 (tests): one tile per iteration (k_render_uniform<*, true>)
     if (lidar) { if (fp) { if (tail2) LAUNCH_TAIL(true); else LAUNCH_RU(true, true); } else LAUNCH_RU(true, false); }

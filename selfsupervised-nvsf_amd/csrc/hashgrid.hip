@@ -625,8 +625,6 @@ int fill_meta(GridMeta& meta, uint32_t L, const float* scales, const uint32_t* r
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 #define DISPATCH_DF(D, F, CALL)                                         \
     do {                                                                \
         if (D == 2 && F == 2) { CALL(2, 2); }                           \

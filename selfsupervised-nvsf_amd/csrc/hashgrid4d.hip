@@ -541,8 +541,6 @@ int fill_meta(GridMeta& meta, uint32_t L, const float* scales, const uint32_t* r
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 // tables: 6 device pointers (lo slice of pair 0,1,2 then hi slice of pair 0,1,2); h_scales / h_res: [3][8];
 // h_offsets: [3][9]; h_time: {blend_lo, blend_hi, w0, w1, w2, w3}
 NVSF_API int nvsf_hashgrid4d_dynamic_fwd(const float* x, uint32_t x_stride, const float* offset, uint32_t off_stride, uint32_t off_col,

@@ -430,8 +430,6 @@ __global__ __launch_bounds__(256) void k_error_map_write(const float* __restrict
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 NVSF_API int nvsf_lidar_losses_fwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
                                    const float* gt_range, const float* rays_d, uint32_t N, float alpha_d, float alpha_r, float alpha_i,
                                    float smooth_factor, float scale, float* loss_depth, float* loss_raydrop, float* loss_intensity,

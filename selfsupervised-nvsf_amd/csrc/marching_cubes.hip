@@ -277,8 +277,6 @@ bool make_grid(uint32_t nx, uint32_t ny, uint32_t nz, Grid& g) {
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 static inline size_t mc_ws_need(const Grid& g) {
     const size_t tiles = cdiv(g.n, kTile);
     return tiles * 8 + (size_t)g.n * 4;

@@ -340,8 +340,6 @@ static inline uint32_t host_streaming_grid(uint32_t n) {
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 NVSF_API int nvsf_image_error_stats(const float* pred, const float* truth, uint32_t n, float lo, float hi, void* workspace, size_t ws_bytes,
                                     double* out, hipStream_t stream) {
     REQUIRE(pred && truth && workspace && out && n >= 1 && n <= kMaxElems && !(lo > hi));

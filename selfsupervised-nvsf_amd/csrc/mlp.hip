@@ -72,8 +72,6 @@ __global__ __launch_bounds__(kBlock) void k_mlp_fwd(const void* __restrict__ x, 
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 // weights: fp16 [64][in_cols] ++ (n_hidden-1) x [64][64] ++ [16][64]; out fp32 [M, out_stride]: all 16 columns (out_cols = 16) or the leading 1 ... 4
 static int mlp_fwd_impl(const void* x, int x_is_f16, uint32_t M, uint32_t n_in, uint32_t x_stride, const void* weights_f16,
                         uint32_t in_cols, uint32_t hidden, uint32_t n_hidden, uint32_t out_cols, float* out_f32,

@@ -885,8 +885,6 @@ int fill_plane_meta(PlaneMeta& meta, uint32_t n_scales, const uint32_t* h_res) {
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 NVSF_API int nvsf_planes_fwd(const float* xt, uint32_t M, const float* planes_cl, uint32_t n_scales, uint32_t C, const uint32_t* h_res,
                              int want, float* out_static, float* out_dynamic, hipStream_t stream) {
     if (M == 0) return NVSF_OK;

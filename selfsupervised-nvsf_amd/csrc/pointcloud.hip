@@ -127,7 +127,6 @@ __global__ __launch_bounds__(kBlock) void k_plane_mask(const float* __restrict__
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
 constexpr uint32_t kMaxPoints = 1u << 28;  // 3 n and the grid sizes stay far inside 32 bits
 
 NVSF_API int nvsf_knn_mean_distance(const float* points, uint32_t n, uint32_t k, float* out_mean, hipStream_t stream) {

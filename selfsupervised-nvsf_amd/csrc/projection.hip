@@ -78,8 +78,6 @@ __global__ __launch_bounds__(kBlock) void k_points_depth_image(const float* __re
 constexpr uint64_t kMaxImage = 1ull << 31;  // elements of the output and of the input: 32-bit thread indices
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 NVSF_API int nvsf_lidar_depth_images(const float* range_m, uint32_t F, uint32_t Hl, uint32_t Wl, float fov_up, float fov, float fov_hoz,
                                      const float* lidar2cam, const double* K, uint32_t H, uint32_t W, float* out, hipStream_t stream) {
     REQUIRE(range_m && lidar2cam && K && out && F >= 1 && Hl >= 1 && Wl >= 1 && H >= 1 && W >= 1);

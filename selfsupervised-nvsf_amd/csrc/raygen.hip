@@ -64,8 +64,6 @@ __global__ __launch_bounds__(kBlock) void k_camera_rays(const float* __restrict_
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 NVSF_API int nvsf_lidar_rays(const float* pose44, const int64_t* inds, uint32_t N, uint32_t H, uint32_t W, float fov_up, float fov,
                              float fov_hoz, float* rays_o, float* rays_d, hipStream_t stream) {
     if (N == 0) return NVSF_OK;

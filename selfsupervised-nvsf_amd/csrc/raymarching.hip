@@ -968,7 +968,6 @@ __global__ __launch_bounds__(kBlock) void k_composite_rays_g8(uint32_t n_alive, 
 // ================================================================================================
 // C-ABI (declared and documented in include/nvsf_hip.h)
 // ================================================================================================
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
 
 NVSF_API int nvsf_near_far_from_aabb(const float* rays_o, const float* rays_d, const float* aabb, uint32_t N,
                                      float min_near, float* nears, float* fars, hipStream_t stream) {

@@ -177,8 +177,6 @@ __global__ __launch_bounds__(kBlock) void k_image_bwd(const float* __restrict__ 
 }
 }  // namespace
 
-#define REQUIRE(cond) do { if (!(cond)) return NVSF_ERR_INVALID_ARG; } while (0)
-
 NVSF_API int nvsf_uniform_samples(const float* rays_o, const float* rays_d, const float* nears, const float* fars,
                                   const float* lin, const float* noise, const float* aabb, uint32_t N, uint32_t T,
                                   float* z_vals, float* xyzs, hipStream_t stream) {

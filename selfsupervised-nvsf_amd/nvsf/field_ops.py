@@ -827,6 +827,13 @@ def _density_backward(ctx, g_sigma, g_geo):
     return grad_table, None, None, (grad_w if need_w else None), None, None, None, None
 
 
+def _uniform_ray_args(rays_o, rays_d, nears, fars, T, noise, aabb_host, bound, table_f16, spec):
+    """The 16 leading arguments of the uniform-sampling entry points (include/nvsf_hip.h): rays_o ... h_offsets."""
+    N, dev = rays_o.shape[0], rays_o.device
+    return (_hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars), _hip.ptr(linspace01(T, dev)), _hip.ptr(noise),
+            _hip.host_f32(aabb_host), float(bound), N, T, _hip.ptr(table_f16), spec.L, spec.F, spec.h_scales, spec.h_res, spec.h_offsets)
+
+
 def density_uniform_train_forward(rays_o, rays_d, nears, fars, T, aabb_host, bound, noise, table_f16, grid_spec, mlp_w16, sliced):
     """nvsf_field_density_uniform_train_fwd: rays -> z_vals [N, T], sigma [N T], geo16 [N T, 16] fp16 and what the backward reads:
     normalised positions x01 [N T, 3], feature rows [N T, 32] fp16, MLP outputs h32 [N T, 16] fp32.  `sliced`: the level-sliced
@@ -840,10 +847,8 @@ def density_uniform_train_forward(rays_o, rays_d, nears, fars, T, aabb_host, bou
     feat = torch.empty(M, 32, dtype=torch.float16, device=dev)
     h32 = torch.empty(M, 16, dtype=torch.float32, device=dev)
     planes = torch.empty(16, M, dtype=torch.int32, device=dev) if sliced else None  # 8 planes of 8 bytes per sample
-    _hip.call("nvsf_field_density_uniform_train_fwd", _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars),
-              _hip.ptr(linspace01(T, dev)), _hip.ptr(noise), _hip.host_f32(aabb_host), float(bound), N, T, _hip.ptr(table_f16),
-              grid_spec.L, grid_spec.F, grid_spec.h_scales, grid_spec.h_res, grid_spec.h_offsets, _hip.ptr(mlp_w16), _hip.ptr(z_vals),
-              _hip.ptr(sigma), _hip.ptr(geo16), _hip.ptr(x01), _hip.ptr(feat), _hip.ptr(h32), _hip.ptr(planes))
+    _hip.call("nvsf_field_density_uniform_train_fwd", *_uniform_ray_args(rays_o, rays_d, nears, fars, T, noise, aabb_host, bound, table_f16, grid_spec),
+              _hip.ptr(mlp_w16), _hip.ptr(z_vals), _hip.ptr(sigma), _hip.ptr(geo16), _hip.ptr(x01), _hip.ptr(feat), _hip.ptr(h32), _hip.ptr(planes))
     return z_vals, sigma, geo16, x01, feat, h32
 
 
@@ -889,12 +894,10 @@ def render_uniform_train_forward(rays_o, rays_d, nears, fars, T, aabb_host, boun
     feat = torch.empty(M, 32, dtype=torch.float16, device=dev)
     geo16 = torch.empty(M, 16, dtype=torch.float16, device=dev)
     planes = torch.empty(16, M, dtype=torch.int32, device=dev) if sliced else None  # 8 planes of 8 bytes per sample
-    _hip.call("nvsf_render_uniform_train_fwd", _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars), _hip.ptr(linspace01(T, dev)),
-              _hip.ptr(noise), _hip.host_f32(aabb_host), float(bound), N, T, _hip.ptr(table_f16), grid_spec.L, grid_spec.F, grid_spec.h_scales,
-              grid_spec.h_res, grid_spec.h_offsets, _hip.ptr(sigma_w16), 1 if lidar else 0, _hip.ptr(head_a_w16), _hip.ptr(head_b_w16),
-              float(k_scale), float(w_thresh), _hip.host_f32(bg_host) if bg_host is not None else None, _hip.ptr(planes), _hip.ptr(z_vals),
-              _hip.ptr(weights), _hip.ptr(ws), _hip.ptr(depth), _hip.ptr(image), _hip.ptr(x01), _hip.ptr(feat), _hip.ptr(geo16), _hip.ptr(sigma),
-              _hip.ptr(rgbs))
+    _hip.call("nvsf_render_uniform_train_fwd", *_uniform_ray_args(rays_o, rays_d, nears, fars, T, noise, aabb_host, bound, table_f16, grid_spec),
+              _hip.ptr(sigma_w16), 1 if lidar else 0, _hip.ptr(head_a_w16), _hip.ptr(head_b_w16), float(k_scale), float(w_thresh),
+              _hip.host_f32(bg_host) if bg_host is not None else None, _hip.ptr(planes), _hip.ptr(z_vals), _hip.ptr(weights), _hip.ptr(ws),
+              _hip.ptr(depth), _hip.ptr(image), _hip.ptr(x01), _hip.ptr(feat), _hip.ptr(geo16), _hip.ptr(sigma), _hip.ptr(rgbs))
     return z_vals, weights, ws, depth, image, x01, feat, geo16, sigma, rgbs
 
 
@@ -1314,10 +1317,8 @@ def density_uniform(rays_o, rays_d, nears, fars, T, aabb_host, bound, table_f16,
         sigmas = torch.empty(N, T, dtype=torch.float32, device=dev)
         geo = torch.empty(N, T, 16, dtype=torch.float16, device=dev)
         feat = torch.empty(16, N * T, dtype=torch.int32, device=dev) if sliced else None  # 8 planes of 8 bytes per sample
-    args = (_hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars),
-            _hip.ptr(linspace01(T, dev)), _hip.ptr(noise), _hip.host_f32(aabb_host), float(bound), N, T, _hip.ptr(table_f16),
-            spec.L, spec.F, spec.h_scales, spec.h_res, spec.h_offsets, _hip.ptr(sigma_weights_f16), _hip.ptr(z_vals),
-            _hip.ptr(sigmas), _hip.ptr(geo))
+    args = (*_uniform_ray_args(rays_o, rays_d, nears, fars, T, noise, aabb_host, bound, table_f16, spec), _hip.ptr(sigma_weights_f16),
+            _hip.ptr(z_vals), _hip.ptr(sigmas), _hip.ptr(geo))
     if sliced:
         _hip.call("nvsf_field_density_uniform_sliced_fwd", *args, _hip.ptr(feat), int(_passes))
     else:
@@ -1346,7 +1347,7 @@ def render_uniform(rays_o, rays_d, nears, fars, T, aabb_host, bound, table_f16, 
     returned by an earlier call lets bench.py time the two launches of the sliced form separately."""
     N = rays_o.shape[0]
     dev = rays_o.device
-    lin = linspace01(T, dev)
+    lead = _uniform_ray_args(rays_o, rays_d, nears, fars, T, noise, aabb_host, bound, table_f16, spec)
     if _buffers is not None:
         z_vals, weights, ws, depth, image, feat = _buffers
     else:
@@ -1357,17 +1358,13 @@ def render_uniform(rays_o, rays_d, nears, fars, T, aabb_host, bound, table_f16, 
         image = torch.empty(N, 2 if lidar else 3, dtype=torch.float32, device=dev)
         feat = torch.empty(16, N * T, dtype=torch.int32, device=dev) if sliced else None  # 8 planes of 8 bytes per sample
     if sliced and _stage != "tail":
-        _hip.call("nvsf_field_density_uniform_sliced_fwd", _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars), _hip.ptr(lin),
-                  _hip.ptr(noise), _hip.host_f32(aabb_host), float(bound), N, T, _hip.ptr(table_f16), spec.L, spec.F, spec.h_scales,
-                  spec.h_res, spec.h_offsets, _hip.ptr(sigma_weights_f16), _hip.ptr(z_vals), _hip.ptr(weights), _hip.ptr(weights),
-                  _hip.ptr(feat), 1)  # passes = 1: encode only (the sigma / geo arguments are not touched)
+        _hip.call("nvsf_field_density_uniform_sliced_fwd", *lead, _hip.ptr(sigma_weights_f16), _hip.ptr(z_vals), _hip.ptr(weights),
+                  _hip.ptr(weights), _hip.ptr(feat), 1)  # passes = 1: encode only (the sigma / geo arguments are not touched)
     if _stage == "encode":
         return z_vals, weights, ws, depth, image, feat
-    _hip.call("nvsf_render_uniform_fwd", _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars), _hip.ptr(lin), _hip.ptr(noise),
-              _hip.host_f32(aabb_host), float(bound), N, T, _hip.ptr(table_f16), spec.L, spec.F, spec.h_scales, spec.h_res, spec.h_offsets,
-              _hip.ptr(sigma_weights_f16), 1 if lidar else 0, _hip.ptr(head_a_f16), _hip.ptr(head_b_f16), float(k_scale), float(w_thresh),
-              _hip.host_f32(bg_host) if bg_host is not None else None, _hip.ptr(feat), _hip.ptr(z_vals), _hip.ptr(weights), _hip.ptr(ws),
-              _hip.ptr(depth), _hip.ptr(image))
+    _hip.call("nvsf_render_uniform_fwd", *lead, _hip.ptr(sigma_weights_f16), 1 if lidar else 0, _hip.ptr(head_a_f16), _hip.ptr(head_b_f16),
+              float(k_scale), float(w_thresh), _hip.host_f32(bg_host) if bg_host is not None else None, _hip.ptr(feat), _hip.ptr(z_vals),
+              _hip.ptr(weights), _hip.ptr(ws), _hip.ptr(depth), _hip.ptr(image))
     if _stage is not None:
         return z_vals, weights, ws, depth, image, feat
     return z_vals, weights, ws, depth, image
