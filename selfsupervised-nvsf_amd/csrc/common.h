@@ -47,6 +47,13 @@ int nvsf_cu_count();  // compute units of the current device (256 on MI355X)
 // ---- wave-level primitives (64 lanes) -------------------------------------------------
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
+// value of the neighbouring lane (lane ^ 1): one DPP move, every lane has a source.  The two-lanes-per-sample encoders (lane = 2 * sample +
+// x-bit) exchange the halves of their gathers with it.
+__device__ __forceinline__ uint32_t lane_swap(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
+}
+__device__ __forceinline__ float lane_swap_f(float v) { return __builtin_bit_cast(float, lane_swap(__builtin_bit_cast(uint32_t, v))); }
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll

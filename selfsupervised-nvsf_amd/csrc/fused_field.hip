@@ -599,10 +599,6 @@ __device__ __forceinline__ void slice_issue_half(const SliceLevel<F>& lv, __amdg
     for (int p = 0; p < 4; ++p) raw[p] = gather_raw<F>(rsrc, lv.boff + idx[p] * (uint32_t)(F * sizeof(_Float16)));
 }
 
-__device__ __forceinline__ uint32_t quad_swap(uint32_t v) {  // value of the neighbouring lane (lane ^ 1); every lane has a source
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
-}
-
 // Which workgroups encode which units of which slice.  Workgroup b belongs to group b % 8 (workgroups are dealt to the XCDs
 // round-robin: a group = the workgroups of one XCD); a group works through up to kPlanItems items = (slice, range of units), its own
 // slice first.  The default plan gives every group exactly its slice; slice_plan() moves the tail of the heavy slices to the
@@ -724,14 +720,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         for (int p = 0; p < 4; ++p) {
             const uint32_t own = xb ? half_raw[1][p] : half_raw[0][p];
             const uint32_t send = xb ? half_raw[0][p] : half_raw[1][p];
-            const uint32_t recv = quad_swap(send);
+            const uint32_t recv = lane_swap(send);
             raw[2 * p] = xb ? recv : own;
             raw[2 * p + 1] = xb ? own : recv;
         }
 #pragma unroll
         for (int d = 0; d < 3; ++d) fr[d] = xb ? frac[1][d] : frac[0][d];
         const uint32_t mine = slice_blend(fr, raw);
-        const uint32_t other = quad_swap(mine);
+        const uint32_t other = lane_swap(mine);
         if (cur.in_range && xb == 0u) {
             feat[(size_t)slice * M + cur.s] = make_uint2(mine, other);
             if (slice == 0u) {
@@ -829,7 +825,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const uint32_t own = xb ? raw[p][1] : raw[p][0], send = xb ? raw[p][0] : raw[p][1];
-            const uint32_t recv = quad_swap(send);
+            const uint32_t recv = lane_swap(send);
             mine[2 * p] = xb ? recv : own;
             mine[2 * p + 1] = xb ? own : recv;
         }
@@ -1871,18 +1867,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         cur[1] = nxt[1];
     }
     store_ray<C>(lane, ws, dp, img, bg0, bg1, bg2, use_bg, weights_sum + n, depth + n, image + (size_t)n * C);
-}
-
-int fill_meta(GridMeta& meta, uint32_t L, const float* scales, const uint32_t* res, const uint32_t* offsets) {
-    if (L == 0 || L > (uint32_t)kMaxLevels || !scales || !res || !offsets) return NVSF_ERR_INVALID_ARG;
-    for (uint32_t l = 0; l < L; ++l) {
-        meta.scale[l] = scales[l];
-        meta.res[l] = res[l];
-        meta.offset[l] = offsets[l];
-        if (offsets[l + 1] <= offsets[l] || res[l] == 0) return NVSF_ERR_INVALID_ARG;
-    }
-    meta.offset[L] = offsets[L];
-    return NVSF_OK;
 }
 
 // What the launchers ask about a grid.  `dense_first`: dense levels first, hashed levels after (true for any per_level_scale >= 1)

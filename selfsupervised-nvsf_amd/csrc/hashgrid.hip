@@ -7,6 +7,7 @@
 // one wave instruction fall into few cache lines); the four waves split the levels (wave w takes levels
 // w, w+4, ...).  Features are staged as fp16 in LDS in output order and leave the workgroup as 16-byte
 // stores of whole rows, instead of 4..16-byte stores at a stride of L*F*2 bytes.
+#include <type_traits>
 #include "hashgrid_device.h"
 
 namespace {
@@ -60,10 +61,6 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_fwd(const float* __restrict
 // cells).  The even lane blends features 0, 1, the odd lane features 2, 3, each over all eight corners in the specification's
 // order (the partner's half of every entry arrives by a quad swap): the same fma chain as encode_level<3, 4>, bit-identical
 // features.  If the dispatcher placed workgroups differently the result is the same, only slower.
-__device__ __forceinline__ uint32_t lane_swap(uint32_t v) {  // value of lane ^ 1
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
-}
-
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_hashgrid_fwd_levels8(
     const float* __restrict__ x, uint32_t M, uint32_t x_stride, const _Float16* __restrict__ table, uint32_t table_bytes, GridMeta meta,
     _Float16* __restrict__ out, uint32_t out_stride, uint32_t planes = 0) {
@@ -90,13 +87,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         fetch(unit + wave_count < n_units ? unit + wave_count : unit, nxt);
         float frac[3];
         uint32_t c[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float pos = fmaf(scale, xs[d], 0.5f);
-            const float fl = floorf(pos);
-            frac[d] = pos - fl;
-            c[d] = (uint32_t)(int32_t)fl;
-        }
+        grid_cell<3>(xs, scale, c, frac);
         const uint32_t hy0 = c[1] * 2654435761u, hy1 = hy0 + 2654435761u;
         const uint32_t hz0 = c[2] * 805459861u, hz1 = hz0 + 805459861u;
         const uint32_t yz[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
@@ -152,10 +143,7 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_bwd(const float* __restrict
     if constexpr (D == 3) xs[2] = px[c2];
     float g[F];
 #pragma unroll
-    for (int f = 0; f < F; ++f) {
-        if constexpr (GRAD_F16) g[f] = (float)reinterpret_cast<const _Float16*>(grad_out)[(size_t)m * go_stride + (size_t)l * go_level + f];
-        else g[f] = reinterpret_cast<const float*>(grad_out)[(size_t)m * go_stride + (size_t)l * go_level + f];
-    }
+    for (int f = 0; f < F; ++f) g[f] = load_grad<GRAD_F16>(grad_out, (size_t)m * go_stride + (size_t)l * go_level + f);
     bool any = false;
 #pragma unroll
     for (int f = 0; f < F; ++f) any |= (g[f] != 0.0f);
@@ -164,13 +152,7 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_bwd(const float* __restrict
     const uint32_t res = meta.res[l], row0 = meta.offset[l], hsize = meta.offset[l + 1] - row0;
     float frac[D];
     uint32_t cell[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const float pos = fmaf(scale, xs[d], 0.5f);
-        const float fl = floorf(pos);
-        frac[d] = pos - fl;
-        cell[d] = (uint32_t)(int32_t)fl;
-    }
+    grid_cell<D>(xs, scale, cell, frac);
 #pragma unroll
     for (int c = 0; c < (1 << D); ++c) {
         uint32_t cc[D];
@@ -240,9 +222,7 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_bwd_corners(const float* __
             rw.xs[j][0] = px[c0];
             rw.xs[j][1] = px[c1];
             if constexpr (D == 3) rw.xs[j][2] = px[c2];
-            if (!live) rw.g[j] = 0.0f;
-            else if constexpr (GRAD_F16) rw.g[j] = (float)reinterpret_cast<const _Float16*>(grad_out)[(size_t)mj * go_stride + gcol];
-            else rw.g[j] = reinterpret_cast<const float*>(grad_out)[(size_t)mj * go_stride + gcol];
+            rw.g[j] = live ? load_grad<GRAD_F16>(grad_out, (size_t)mj * go_stride + gcol) : 0.0f;
         }
     };
     Rows nxt;
@@ -259,17 +239,14 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_bwd_corners(const float* __
             const unsigned long long nz = __ballot(g != 0.0f);
             const unsigned long long item_bits = G == 64 ? ~0ull : ((1ull << G) - 1ull);
             if (((nz >> (sub * G)) & item_bits) != 0ull) {
-                float w = 1.0f;
+                float w = 1.0f, frac[D];
                 uint32_t cell[D];
                 bool same = have;
+                grid_cell<D>(rw.xs[j], scale, cell, frac);
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
-                    const float pos = fmaf(scale, rw.xs[j][d], 0.5f);
-                    const float fl = floorf(pos);
-                    const float frac = pos - fl;
-                    cell[d] = (uint32_t)(int32_t)fl;
                     same = same && (cell[d] == cur[d]);
-                    w = w * ((c & (1 << d)) ? frac : (1.0f - frac));
+                    w = w * ((c & (1 << d)) ? frac[d] : (1.0f - frac[d]));
                 }
                 if (!same) {
                     // A step into a neighbouring cell keeps the grid vertices the two cells share (4 of 8 across a face, 2 across
@@ -330,6 +307,7 @@ template <int F> struct BinCfg {
     static constexpr int kBinRows = 8192 / F;             // rows per bin: 64 KB of 64-bit sums
     static constexpr int kBinShift = F <= 2 ? 12 : 11;
     static constexpr int kMaxBins = 256;                  // rows per level <= 256 bins (checked on the host)
+    static constexpr int kRowBits = 20;                   // a staged pair is row | rank << kRowBits: rows per level <= 2^20 (host), rank < kPairs <= 2^12
 };
 
 // The binned levels of one launch: level, bins, capacity of a bin, where its cursors / pairs / reduce workgroups start.  `merged`: the
@@ -385,9 +363,7 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_bwd_bin(const float* __rest
             bool any = false;
 #pragma unroll
             for (int f = 0; f < F; ++f) {
-                const size_t at = (size_t)(mrow[s] < M ? mrow[s] : 0u) * go_stride + (size_t)l * go_level + f;
-                if constexpr (GRAD_F16) g[f] = (float)reinterpret_cast<const _Float16*>(grad_out)[at];
-                else g[f] = reinterpret_cast<const float*>(grad_out)[at];
+                g[f] = load_grad<GRAD_F16>(grad_out, (size_t)(mrow[s] < M ? mrow[s] : 0u) * go_stride + (size_t)l * go_level + f);
                 if (mrow[s] >= M) g[f] = 0.0f;
                 // an inf / NaN gradient (an fp16 overflow under GradScaler) must REACH the table -- the memory-atomic path adds it
                 // there and the scaler's found_inf check skips the step -- but it must not enter the fixed-point image: fmaxf drops
@@ -399,13 +375,7 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_bwd_bin(const float* __rest
             }
             uint32_t cell[3];
             float frac[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const float pos = fmaf(scale, xs[s][d], 0.5f);
-                const float fl = floorf(pos);
-                frac[d] = pos - fl;
-                cell[d] = (uint32_t)(int32_t)fl;
-            }
+            grid_cell<3>(xs[s], scale, cell, frac);
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 const float w = ((1.0f * ((c & 1) ? frac[0] : 1.0f - frac[0])) * ((c & 2) ? frac[1] : 1.0f - frac[1])) *
@@ -481,7 +451,7 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_bwd_bin(const float* __rest
                         }
                     }
                     const uint32_t rank = atomicAdd(&s_cnt[row >> C::kBinShift], 1u);
-                    pk[s][c] = row | (rank << 20);
+                    pk[s][c] = row | (rank << C::kRowBits);
                 }
             }
         }
@@ -518,7 +488,7 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_bwd_bin(const float* __rest
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 if (pk[s][c] == 0xFFFFFFFFu) continue;
-                const uint32_t row = pk[s][c] & 0xFFFFFu, rank = pk[s][c] >> 20;
+                const uint32_t row = pk[s][c] & ((1u << C::kRowBits) - 1u), rank = pk[s][c] >> C::kRowBits;
                 const uint32_t at = s_pre[row >> C::kBinShift] + rank;
                 s_row[at] = row;
 #pragma unroll
@@ -612,29 +582,51 @@ __global__ __launch_bounds__(kReduceBlock) void k_hashgrid_bwd_reduce(const uint
     }
 }
 
-int fill_meta(GridMeta& meta, uint32_t L, const float* scales, const uint32_t* res, const uint32_t* offsets) {
-    if (L == 0 || L > (uint32_t)kMaxLevels || !scales || !res || !offsets) return NVSF_ERR_INVALID_ARG;
+template <int V> using int_c = std::integral_constant<int, V>;
+
+// Calls fn(int_c<D>, int_c<F>) for the shapes the kernels are instantiated for; NVSF_ERR_UNSUPPORTED otherwise
+template <class Fn>
+int dispatch_df(uint32_t D, uint32_t F, Fn&& fn) {
+    if (D == 2 && F == 2) return fn(int_c<2>{}, int_c<2>{});
+    if (D == 2 && F == 4) return fn(int_c<2>{}, int_c<4>{});
+    if (D == 2 && F == 8) return fn(int_c<2>{}, int_c<8>{});
+    if (D == 3 && F == 2) return fn(int_c<3>{}, int_c<2>{});
+    if (D == 3 && F == 4) return fn(int_c<3>{}, int_c<4>{});
+    if (D == 3 && F == 8) return fn(int_c<3>{}, int_c<8>{});
+    return NVSF_ERR_UNSUPPORTED;
+}
+// fn(std::bool_constant<fp16 gradient>), and fn(int_c<D>, int_c<F>, std::bool_constant<fp16 gradient>): the backward kernels
+template <class Fn>
+int dispatch_g(int grad_is_f16, Fn&& fn) {
+    return grad_is_f16 ? fn(std::true_type{}) : fn(std::false_type{});
+}
+template <class Fn>
+int dispatch_dfg(uint32_t D, uint32_t F, int grad_is_f16, Fn&& fn) {
+    return dispatch_df(D, F, [&](auto d, auto f) { return dispatch_g(grad_is_f16, [&](auto g16) { return fn(d, f, g16); }); });
+}
+
+// The grid k_hashgrid_fwd_levels8 is built for: eight levels of F = 4, every one hashed into a power-of-two table, byte offsets below 2^31
+bool levels8_grid(uint32_t L, uint32_t F, const uint32_t* h_res, const uint32_t* h_offsets) {
+    if (!(F == 4 && L == 8) || (unsigned long long)h_offsets[L] * 8ull >= (1ull << 31)) return false;
     for (uint32_t l = 0; l < L; ++l) {
-        meta.scale[l] = scales[l];
-        meta.res[l] = res[l];
-        meta.offset[l] = offsets[l];
-        if (offsets[l + 1] <= offsets[l] || res[l] == 0) return NVSF_ERR_INVALID_ARG;
+        const unsigned long long cells = (unsigned long long)h_res[l] * h_res[l] * h_res[l];
+        const uint32_t rows = h_offsets[l + 1] - h_offsets[l];
+        if (!(cells > rows && (rows & (rows - 1u)) == 0u)) return false;  // hashed, power-of-two table
     }
-    meta.offset[L] = offsets[L];
-    return NVSF_OK;
+    return true;
+}
+
+// `planes` = 0: rows [M, out_stride]; 1: level-major [8][M][4]
+int launch_levels8(const float* x, uint32_t M, uint32_t x_stride, const void* table_f16, uint32_t table_rows, const GridMeta& meta, void* out_f16,
+                   uint32_t out_stride, uint32_t planes, hipStream_t stream) {
+    const uint32_t units = (M + 31u) / 32u;
+    uint32_t ps = (units + kBlock / kWave - 1) / (kBlock / kWave);
+    if (ps > 512u) ps = 512u;
+    hipLaunchKernelGGL(k_hashgrid_fwd_levels8, dim3(8u * ps), dim3(kBlock), 0, stream, x, M, x_stride, reinterpret_cast<const _Float16*>(table_f16),
+                       (uint32_t)(table_rows * 8u), meta, reinterpret_cast<_Float16*>(out_f16), out_stride, planes);
+    return nvsf_launch_status();
 }
 }  // namespace
-
-#define DISPATCH_DF(D, F, CALL)                                         \
-    do {                                                                \
-        if (D == 2 && F == 2) { CALL(2, 2); }                           \
-        else if (D == 2 && F == 4) { CALL(2, 4); }                      \
-        else if (D == 2 && F == 8) { CALL(2, 8); }                      \
-        else if (D == 3 && F == 2) { CALL(3, 2); }                      \
-        else if (D == 3 && F == 4) { CALL(3, 4); }                      \
-        else if (D == 3 && F == 8) { CALL(3, 8); }                      \
-        else return NVSF_ERR_UNSUPPORTED;                               \
-    } while (0)
 
 NVSF_API int nvsf_hashgrid_fwd(const float* x, uint32_t M, uint32_t x_stride, const uint32_t* cols, uint32_t D, const void* table_f16,
                                uint32_t L, uint32_t F, const float* h_scales, const uint32_t* h_res, const uint32_t* h_offsets,
@@ -648,32 +640,18 @@ NVSF_API int nvsf_hashgrid_fwd(const float* x, uint32_t M, uint32_t x_stride, co
     const int st = fill_meta(meta, L, h_scales, h_res, h_offsets);
     if (st != NVSF_OK) return st;
     const uint32_t c0 = cols[0], c1 = cols[1], c2 = D == 3 ? cols[2] : 0;
-    {   // eight hashed levels of F = 4 on a batch large enough to fill the chip: one level per XCD (k_hashgrid_fwd_levels8)
-        bool sliced = D == 3 && F == 4 && L == 8 && c0 == 0 && c1 == 1 && c2 == 2 && M >= (1u << 16) && out_stride % 4 == 0 &&
-                      (reinterpret_cast<uintptr_t>(out_f16) & 7u) == 0 && (unsigned long long)h_offsets[L] * 8ull < (1ull << 31);
-        for (uint32_t l = 0; l < L && sliced; ++l) {
-            const unsigned long long cells = (unsigned long long)h_res[l] * h_res[l] * h_res[l];
-            const uint32_t rows = h_offsets[l + 1] - h_offsets[l];
-            sliced = cells > rows && (rows & (rows - 1u)) == 0u;  // hashed, power-of-two table
-        }
-        if (sliced && nvsf_variant(kVarHashgridFwd) == 0) {  // 1 (tests): the one-workgroup-per-64-samples kernel, the reference form
-            const uint32_t units = (M + 31u) / 32u;
-            uint32_t ps = (units + kBlock / kWave - 1) / (kBlock / kWave);
-            if (ps > 512u) ps = 512u;
-            hipLaunchKernelGGL(k_hashgrid_fwd_levels8, dim3(8u * ps), dim3(kBlock), 0, stream, x, M, x_stride,
-                               reinterpret_cast<const _Float16*>(table_f16), (uint32_t)(h_offsets[L] * 8u), meta,
-                               reinterpret_cast<_Float16*>(out_f16), out_stride, 0u);
-            return nvsf_launch_status();
-        }
-    }
+    // eight hashed levels of F = 4 on a batch large enough to fill the chip: one level per XCD (k_hashgrid_fwd_levels8)
+    const bool sliced = D == 3 && c0 == 0 && c1 == 1 && c2 == 2 && M >= (1u << 16) && out_stride % 4 == 0 &&
+                        (reinterpret_cast<uintptr_t>(out_f16) & 7u) == 0 && levels8_grid(L, F, h_res, h_offsets);
+    if (sliced && nvsf_variant(kVarHashgridFwd) == 0)  // 1 (tests): the one-workgroup-per-64-samples kernel, the reference form
+        return launch_levels8(x, M, x_stride, table_f16, h_offsets[L], meta, out_f16, out_stride, 0u, stream);
     const size_t lds = (size_t)kSamplesPerBlock * (L * F / 2 + 1) * sizeof(uint32_t);
-#define CALL(DD, FF)                                                                                                        \
-    hipLaunchKernelGGL((k_hashgrid_fwd<DD, FF>), dim3(cdiv(M, kSamplesPerBlock)), dim3(kBlock), lds, stream, x, M, x_stride, c0, \
-                       c1, c2, reinterpret_cast<const _Float16*>(table_f16), L, meta, reinterpret_cast<_Float16*>(out_f16),  \
-                       out_stride)
-    DISPATCH_DF(D, F, CALL);
-#undef CALL
-    return nvsf_launch_status();
+    return dispatch_df(D, F, [&](auto d, auto f) {
+        hipLaunchKernelGGL((k_hashgrid_fwd<decltype(d)::value, decltype(f)::value>), dim3(cdiv(M, kSamplesPerBlock)), dim3(kBlock), lds, stream, x,
+                           M, x_stride, c0, c1, c2, reinterpret_cast<const _Float16*>(table_f16), L, meta, reinterpret_cast<_Float16*>(out_f16),
+                           out_stride);
+        return nvsf_launch_status();
+    });
 }
 
 // The same encoder with the output LEVEL-MAJOR, fp16 [L][M][F]: what a consumer that reads whole levels per lane wants
@@ -690,19 +668,8 @@ NVSF_API int nvsf_hashgrid_fwd_level_major(const float* x, uint32_t M, uint32_t 
     GridMeta meta;
     const int st = fill_meta(meta, L, h_scales, h_res, h_offsets);
     if (st != NVSF_OK) return st;
-    if ((unsigned long long)h_offsets[L] * 8ull >= (1ull << 31)) return NVSF_ERR_UNSUPPORTED;
-    for (uint32_t l = 0; l < L; ++l) {
-        const unsigned long long cells = (unsigned long long)h_res[l] * h_res[l] * h_res[l];
-        const uint32_t rows = h_offsets[l + 1] - h_offsets[l];
-        if (!(cells > rows && (rows & (rows - 1u)) == 0u)) return NVSF_ERR_UNSUPPORTED;
-    }
-    const uint32_t units = (M + 31u) / 32u;
-    uint32_t ps = (units + kBlock / kWave - 1) / (kBlock / kWave);
-    if (ps > 512u) ps = 512u;
-    hipLaunchKernelGGL(k_hashgrid_fwd_levels8, dim3(8u * ps), dim3(kBlock), 0, stream, x, M, x_stride,
-                       reinterpret_cast<const _Float16*>(table_f16), (uint32_t)(h_offsets[L] * 8u), meta,
-                       reinterpret_cast<_Float16*>(out_f16), 0u, 1u);
-    return nvsf_launch_status();
+    if (!levels8_grid(L, F, h_res, h_offsets)) return NVSF_ERR_UNSUPPORTED;
+    return launch_levels8(x, M, x_stride, table_f16, h_offsets[L], meta, out_f16, 0u, 1u, stream);
 }
 
 namespace {
@@ -717,7 +684,7 @@ bool bin_plan(uint32_t M, uint32_t L, uint32_t F, const uint32_t* h_res, const u
               BinPlan& bp) {
     if ((F != 2 && F != 4) || merge_from > fine_from || fine_from > L || merge_from == L || L - merge_from > 16u) return false;
     if ((unsigned long long)M * 8ull > (1ull << 26)) return false;  // 2^26 contributions per row at most (fixed-point headroom)
-    const uint32_t bin_rows = 8192u / F;
+    const uint32_t bin_rows = (uint32_t)(F == 2 ? BinCfg<2>::kBinRows : BinCfg<4>::kBinRows);
     BinLevels& bl = bp.bl;
     bl.n = L - merge_from;
     unsigned long long pairs = 0;
@@ -725,9 +692,9 @@ bool bin_plan(uint32_t M, uint32_t L, uint32_t F, const uint32_t* h_res, const u
     for (uint32_t j = 0; j < bl.n; ++j) {
         const uint32_t l = merge_from + j, rows = h_offsets[l + 1] - h_offsets[l];
         const bool hashed = (unsigned long long)h_res[l] * h_res[l] * h_res[l] > rows;
-        if (rows > (1u << 20) || (hashed && (rows & (rows - 1u)) != 0u)) return false;
+        if (rows > (1u << BinCfg<2>::kRowBits) || (hashed && (rows & (rows - 1u)) != 0u)) return false;
         const uint32_t nbins = (rows + bin_rows - 1) / bin_rows;
-        if (nbins > 256u) return false;
+        if (nbins > (uint32_t)BinCfg<2>::kMaxBins) return false;
         const unsigned long long all = (unsigned long long)M * 8ull, mean = (all + nbins - 1) / nbins;
         unsigned long long cap;
         if (l >= fine_from) cap = mean + mean / 4 + 2048ull;          // uniform hash, one contribution per (row, vertex)
@@ -788,21 +755,21 @@ int hashgrid_bwd_launch(const float* x, uint32_t M, uint32_t x_stride, const uin
             if (e != hipSuccess) return (int)e;
         }
         uint32_t* level_max = cursors + bp.total_bins;
-#define CALLB(FF)                                                                                                                      \
-    do {                                                                                                                               \
-        const dim3 bgrid(cdiv(M, (uint32_t)BinCfg<FF>::kTile));                                                                        \
-        if (grad_is_f16)                                                                                                               \
-            hipLaunchKernelGGL((k_hashgrid_bwd_bin<FF, true>), bgrid, dim3(kBlock), 0, stream, x, M, x_stride, c0, c1, c2, meta,       \
-                               bp.bl, grad_out, go_stride, go_level, grad_table_f32, cursors, level_max, pair_row, pair_val);                    \
-        else                                                                                                                           \
-            hipLaunchKernelGGL((k_hashgrid_bwd_bin<FF, false>), bgrid, dim3(kBlock), 0, stream, x, M, x_stride, c0, c1, c2, meta,      \
-                               bp.bl, grad_out, go_stride, go_level, grad_table_f32, cursors, level_max, pair_row, pair_val);                    \
-        hipLaunchKernelGGL((k_hashgrid_bwd_reduce<FF>), dim3(bp.total_wgs), dim3(kReduceBlock), 0, stream, cursors, level_max,         \
-                           pair_row, pair_val, bp.bl, meta, grad_table_f32);                                                           \
-    } while (0)
-        if (F == 2) CALLB(2);
-        else CALLB(4);
-#undef CALLB
+        // the bin pass and the reduce pass of the binned levels (D = 3, F = 2 or 4: checked above), then the levels below through
+        // the corner-parallel kernel
+        auto bins = [&](auto f, auto g16) {
+            constexpr int FF = decltype(f)::value;
+            hipLaunchKernelGGL((k_hashgrid_bwd_bin<FF, decltype(g16)::value>), dim3(cdiv(M, (uint32_t)BinCfg<FF>::kTile)), dim3(kBlock), 0, stream, x,
+                               M, x_stride, c0, c1, c2, meta, bp.bl, grad_out, go_stride, go_level, grad_table_f32, cursors, level_max, pair_row,
+                               pair_val);
+            hipLaunchKernelGGL((k_hashgrid_bwd_reduce<FF>), dim3(bp.total_wgs), dim3(kReduceBlock), 0, stream, cursors, level_max, pair_row,
+                               pair_val, bp.bl, meta, grad_table_f32);
+        };
+        dispatch_g(grad_is_f16, [&](auto g16) {
+            if (F == 2) bins(int_c<2>{}, g16);
+            else bins(int_c<4>{}, g16);
+            return (int)NVSF_OK;
+        });
         if (merge_from == 0) return nvsf_launch_status();
     }
     const uint32_t l_end = merge_from;  // the levels below go through the atomics
@@ -814,32 +781,17 @@ int hashgrid_bwd_launch(const float* x, uint32_t M, uint32_t x_stride, const uin
         const uint32_t l_items = (l_end + ipw - 1) / ipw * ipw;  // items of a wave = ipw consecutive levels of one chunk
         const unsigned long long waves = (unsigned long long)cdiv(M, run) * (l_items / ipw);
         const dim3 cgrid((uint32_t)((waves + kBlock / kWave - 1) / (kBlock / kWave)));
-#define CALLC(DD, FF)                                                                                                                \
-    do {                                                                                                                             \
-        if (grad_is_f16)                                                                                                             \
-            hipLaunchKernelGGL((k_hashgrid_bwd_corners<DD, FF, true>), cgrid, dim3(kBlock), 0, stream, x, M, x_stride, c0, c1, c2, l_items, meta, \
-                               grad_out, go_stride, go_level, grad_table_f32, run, l_end);                                                     \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((k_hashgrid_bwd_corners<DD, FF, false>), cgrid, dim3(kBlock), 0, stream, x, M, x_stride, c0, c1, c2, l_items, meta, \
-                               grad_out, go_stride, go_level, grad_table_f32, run, l_end);                                                     \
-    } while (0)
-        DISPATCH_DF(D, F, CALLC);
-#undef CALLC
-        return nvsf_launch_status();
+        return dispatch_dfg(D, F, grad_is_f16, [&](auto d, auto f, auto g16) {
+            hipLaunchKernelGGL((k_hashgrid_bwd_corners<decltype(d)::value, decltype(f)::value, decltype(g16)::value>), cgrid, dim3(kBlock), 0, stream,
+                               x, M, x_stride, c0, c1, c2, l_items, meta, grad_out, go_stride, go_level, grad_table_f32, run, l_end);
+            return nvsf_launch_status();
+        });
     }
-    const dim3 grid(cdiv(M, kBlock), L);
-#define CALL(DD, FF)                                                                                                          \
-    do {                                                                                                                         \
-        if (grad_is_f16)                                                                                                         \
-            hipLaunchKernelGGL((k_hashgrid_bwd<DD, FF, true>), grid, dim3(kBlock), 0, stream, x, M, x_stride, c0, c1, c2, L, meta, \
-                               grad_out, go_stride, go_level, grad_table_f32);                                                   \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((k_hashgrid_bwd<DD, FF, false>), grid, dim3(kBlock), 0, stream, x, M, x_stride, c0, c1, c2, L, meta, \
-                               grad_out, go_stride, go_level, grad_table_f32);                                                   \
-    } while (0)
-    DISPATCH_DF(D, F, CALL);
-#undef CALL
-    return nvsf_launch_status();
+    return dispatch_dfg(D, F, grad_is_f16, [&](auto d, auto f, auto g16) {
+        hipLaunchKernelGGL((k_hashgrid_bwd<decltype(d)::value, decltype(f)::value, decltype(g16)::value>), dim3(cdiv(M, kBlock), L), dim3(kBlock), 0,
+                           stream, x, M, x_stride, c0, c1, c2, L, meta, grad_out, go_stride, go_level, grad_table_f32);
+        return nvsf_launch_status();
+    });
 }
 }  // namespace
 

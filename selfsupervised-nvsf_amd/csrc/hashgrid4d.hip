@@ -19,19 +19,25 @@ constexpr int kSamplesPerBlock = 64;
 constexpr int kPlaneLevels = 8;   // HashGridT: n_levels = 8, F = 4, num_basis = 4 (hash_field.py:35-38)
 constexpr int kF = 4;
 
-struct PlaneSet {
-    const _Float16* table_lo[3];  // slice floor(idx) of the pairs (x,y), (x,z), (y,z)
-    const _Float16* table_hi[3];  // slice ceil(idx)
-    GridMeta meta[3];
+// The time side of one evaluation: the two slices around t and the time weights.  T = const _Float16: the slice tables of a forward;
+// T = float: their fp32 gradient buffers.
+template <typename T>
+struct TimeSet {
+    T* table_lo[3];               // slice floor(idx) of the pairs (x,y), (x,z), (y,z)
+    T* table_hi[3];               // slice ceil(idx)
     float blend_lo, blend_hi;     // (k2 - idx), (idx - k1)
     float lag[4];                 // Lagrange weights at t
     int same_slice;               // idx integral: no blend, the slice features are used as they are (fp16)
 };
+struct PlaneSet {
+    TimeSet<const _Float16> ts;
+    GridMeta meta[3];
+};
 
 __device__ __forceinline__ float r16(float v) { return (float)(_Float16)v; }  // round-trip through fp16
 
-template <int MODE, typename PS>
-__device__ __forceinline__ float blend_reduce(const float (&f_lo)[kF], const float (&f_hi)[kF], const PS& ps) {
+template <int MODE, typename T>
+__device__ __forceinline__ float blend_reduce(const float (&f_lo)[kF], const float (&f_hi)[kF], const TimeSet<T>& ps) {
     float feat[kF];
 #pragma unroll
     for (int i = 0; i < kF; ++i) {
@@ -73,18 +79,18 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic(const float* __restrict
         const GridMeta& g = ps.meta[pl];
         const uint32_t rows = g.offset[l + 1] - g.offset[l];
         float f_lo[kF], f_hi[kF];
-        encode_level<2, kF>(xy, ps.table_lo[pl], g.scale[l], g.res[l], g.offset[l], rows, f_lo);
+        encode_level<2, kF>(xy, ps.ts.table_lo[pl], g.scale[l], g.res[l], g.offset[l], rows, f_lo);
 #pragma unroll
         for (int i = 0; i < kF; ++i) f_lo[i] = r16(f_lo[i]);  // the slice encoders return fp16
-        if (!ps.same_slice) {
-            encode_level<2, kF>(xy, ps.table_hi[pl], g.scale[l], g.res[l], g.offset[l], rows, f_hi);
+        if (!ps.ts.same_slice) {
+            encode_level<2, kF>(xy, ps.ts.table_hi[pl], g.scale[l], g.res[l], g.offset[l], rows, f_hi);
 #pragma unroll
             for (int i = 0; i < kF; ++i) f_hi[i] = r16(f_hi[i]);
         } else {
 #pragma unroll
             for (int i = 0; i < kF; ++i) f_hi[i] = 0.0f;
         }
-        stage[lane][item] = blend_reduce<MODE>(f_lo, f_hi, ps);
+        stage[lane][item] = blend_reduce<MODE>(f_lo, f_hi, ps.ts);
     }
     __syncthreads();
     const uint32_t n_rows = min((uint32_t)kSamplesPerBlock, M - blockIdx.x * kSamplesPerBlock);
@@ -104,15 +110,8 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic(const float* __restrict
 // base cell and its slices are the base slices, the 2 x 4 table entries the base evaluation has just gathered (kept as
 // raw 8-byte values, 16 registers) are re-used and only the weights differ; otherwise the neighbour gathers its own.
 // Same gathers / same arithmetic per evaluation as three k_hash_dynamic launches: bit-identical outputs.
-struct TimeSet {  // what differs between the evaluations: the two slices and the time weights
-    const _Float16* table_lo[3];
-    const _Float16* table_hi[3];
-    float blend_lo, blend_hi;
-    float lag[4];
-    int same_slice;
-};
 struct PlaneSet3 {
-    TimeSet ev[3];
+    TimeSet<const _Float16> ev[3];  // what differs between the evaluations
     GridMeta meta[3];  // per pair (shared by the evaluations)
     int enabled[3];    // ev[0] always; ev[1], ev[2]: neighbour present
     int share[3];      // ev[e] reads the same slice tables as ev[0] (same k1, k2): its cells may re-use ev[0]'s gathers
@@ -120,57 +119,16 @@ struct PlaneSet3 {
 
 typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void gather_quad(const float (&xy)[2], const _Float16* __restrict__ table, float scale, uint32_t res, uint32_t row0,
-                                            uint32_t hsize, uint32_t (&cell)[2], float (&frac)[2], u2_t (&raw)[4]) {
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-        const float pos = fmaf(scale, xy[d], 0.5f);
-        const float fl = floorf(pos);
-        frac[d] = pos - fl;
-        cell[d] = (uint32_t)(int32_t)fl;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const uint32_t cc[2] = {cell[0] + (uint32_t)(c & 1), cell[1] + (uint32_t)((c >> 1) & 1)};
-        raw[c] = *reinterpret_cast<const u2_t*>(table + ((size_t)row0 + grid_row<2>(cc, res, hsize)) * kF);
-    }
-}
-// encode_level<2, 4>'s arithmetic on already gathered entries: acc[f] = fma(w_c, v_c[f], acc[f]) over the corners in order
-__device__ __forceinline__ void blend_quad(const u2_t (&raw)[4], const float (&frac)[2], float (&acc)[kF]) {
-#pragma unroll
-    for (int f = 0; f < kF; ++f) acc[f] = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        float wc = 1.0f;
-#pragma unroll
-        for (int d = 0; d < 2; ++d) wc = wc * ((c & (1 << d)) ? frac[d] : (1.0f - frac[d]));
-        const h4_t v = __builtin_bit_cast(h4_t, raw[c]);
-#pragma unroll
-        for (int f = 0; f < kF; ++f) acc[f] = fmaf(wc, (float)v[f], acc[f]);
-    }
-}
-
 // Two lanes per sample (lane = 2 * sample + x-bit, 32 samples per pass, two passes per item): a lane gathers the two corners with
 // its x-bit of a slice, so a gather instruction fetches BOTH x-neighbours of 32 samples -- the same 16-byte pair for even cells,
 // the same 128-byte line otherwise -- and the kernel, which is bound by the L1 look-ups of its ~200 eight-byte gathers per sample,
 // makes half of them.  The even lane blends features 0, 1 of all four corners, the odd lane features 2, 3 (the partner's halves
-// arrive by a quad swap), each in the corner order of encode_level<2, 4>; the odd lane then hands its two rounded features per
+// arrive by lane_swap), each in the corner order of encode_level<2, 4>; the odd lane then hands its two rounded features per
 // slice to the even lane, which runs blend_reduce as the one-lane form does: bit-identical outputs.
-__device__ __forceinline__ uint32_t pair_swap(uint32_t v) {  // value of lane ^ 1
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
-}
-__device__ __forceinline__ float pair_swap_f(float v) { return __builtin_bit_cast(float, pair_swap(__builtin_bit_cast(uint32_t, v))); }
-
-// this lane's two corners (x-bit xb, y = 0, 1) of the cell of xy
+// gather_pair: this lane's two corners (x-bit xb, y = 0, 1) of the cell of xy
 __device__ __forceinline__ void gather_pair(const float (&xy)[2], uint32_t xb, const _Float16* __restrict__ table, float scale, uint32_t res,
                                             uint32_t row0, uint32_t hsize, uint32_t (&cell)[2], float (&frac)[2], u2_t (&raw)[2]) {
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-        const float pos = fmaf(scale, xy[d], 0.5f);
-        const float fl = floorf(pos);
-        frac[d] = pos - fl;
-        cell[d] = (uint32_t)(int32_t)fl;
-    }
+    grid_cell<2>(xy, scale, cell, frac);
 #pragma unroll
     for (int y = 0; y < 2; ++y) {
         const uint32_t cc[2] = {cell[0] + xb, cell[1] + (uint32_t)y};
@@ -183,7 +141,7 @@ __device__ __forceinline__ void blend_pair(const u2_t (&raw)[2], uint32_t xb, co
 #pragma unroll
     for (int y = 0; y < 2; ++y) {
         const uint32_t own = xb ? raw[y][1] : raw[y][0], send = xb ? raw[y][0] : raw[y][1];
-        const uint32_t recv = pair_swap(send);
+        const uint32_t recv = lane_swap(send);
         mine[2 * y] = xb ? recv : own;
         mine[2 * y + 1] = xb ? own : recv;
     }
@@ -199,6 +157,19 @@ __device__ __forceinline__ void blend_pair(const u2_t (&raw)[2], uint32_t xb, co
     }
     f[0] = r16(f[0]);
     f[1] = r16(f[1]);
+}
+
+// One evaluation's features from its gathered slices: both slices blended over the corners, features 2, 3 fetched from the odd lane, and the
+// even lane reduces (*dst belongs to the sample; the odd lane writes nothing)
+template <int MODE>
+__device__ __forceinline__ void reduce_pairs(const u2_t (&lo)[2], const u2_t (&hi)[2], uint32_t xb, const float (&frac)[2],
+                                             const TimeSet<const _Float16>& ts, float* dst) {
+    float a[2], b[2] = {0.0f, 0.0f};
+    blend_pair(lo, xb, frac, a);
+    if (!ts.same_slice) blend_pair(hi, xb, frac, b);
+    const float a2 = lane_swap_f(a[0]), a3 = lane_swap_f(a[1]), b2 = lane_swap_f(b[0]), b3 = lane_swap_f(b[1]);
+    const float f_lo[kF] = {a[0], a[1], a2, a3}, f_hi[kF] = {b[0], b[1], b2, b3};
+    if (xb == 0u) *dst = blend_reduce<MODE>(f_lo, f_hi, ts);
 }
 
 __global__ __launch_bounds__(kBlock) void k_hash_dynamic3(const float* __restrict__ x, uint32_t x_stride, const float* __restrict__ off,
@@ -244,29 +215,17 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic3(const float* __restric
                     hi0[0] = lo0[0];
                     hi0[1] = lo0[1];
                 }
-                float a[2], b[2] = {0.0f, 0.0f};
-                blend_pair(lo0, xb, frac0, a);
-                if (!ps.ev[0].same_slice) blend_pair(hi0, xb, frac0, b);
-                // features 2, 3 come from the odd lane; the even lane reduces
-                const float a2 = pair_swap_f(a[0]), a3 = pair_swap_f(a[1]), b2 = pair_swap_f(b[0]), b3 = pair_swap_f(b[1]);
-                const float f_lo[kF] = {a[0], a[1], a2, a3}, f_hi[kF] = {b[0], b[1], b2, b3};
-                if (xb == 0u) stage[0][row][item] = blend_reduce<0>(f_lo, f_hi, ps.ev[0]);
+                reduce_pairs<0>(lo0, hi0, xb, frac0, ps.ev[0], &stage[0][row][item]);
             }
             // ---- neighbour evaluations (regime 1)
 #pragma unroll
             for (int e = 1; e < 3; ++e) {
                 if (!ps.enabled[e]) continue;
-                const TimeSet& pe = ps.ev[e];
+                const TimeSet<const _Float16>& pe = ps.ev[e];
                 const float xy[2] = {p[h][e][ia], p[h][e][ib]};
                 uint32_t cell[2];
                 float frac[2];
-#pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    const float pos = fmaf(scale, xy[d], 0.5f);
-                    const float fl = floorf(pos);
-                    frac[d] = pos - fl;
-                    cell[d] = (uint32_t)(int32_t)fl;
-                }
+                grid_cell<2>(xy, scale, cell, frac);
                 u2_t lo[2], hi[2];
                 const bool reuse = ps.share[e] && cell[0] == cell0[0] && cell[1] == cell0[1];  // the same for both lanes of a sample
                 if (reuse) {
@@ -279,12 +238,7 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic3(const float* __restric
                     if (!pe.same_slice) gather_pair(xy, xb, pe.table_hi[pl], scale, res, row0, rows, c_, f_, hi);
                     else { hi[0] = lo[0]; hi[1] = lo[1]; }
                 }
-                float a[2], b[2] = {0.0f, 0.0f};
-                blend_pair(lo, xb, frac, a);
-                if (!pe.same_slice) blend_pair(hi, xb, frac, b);
-                const float a2 = pair_swap_f(a[0]), a3 = pair_swap_f(a[1]), b2 = pair_swap_f(b[0]), b3 = pair_swap_f(b[1]);
-                const float f_lo[kF] = {a[0], a[1], a2, a3}, f_hi[kF] = {b[0], b[1], b2, b3};
-                if (xb == 0u) stage[e][row][item] = blend_reduce<1>(f_lo, f_hi, pe);
+                reduce_pairs<1>(lo, hi, xb, frac, pe, &stage[e][row][item]);
             }
         }
     }
@@ -341,19 +295,54 @@ __global__ __launch_bounds__(kBlock) void k_hash3d_lagrange(const float* __restr
 // rows, pair, level, slice), 16 lanes per item (lane = corner x 4 + feature), the sums of the current cell in registers,
 // one atomic instruction per cell change covering whole 16-byte table entries.
 struct PlaneGrads {
-    float* g_lo[3];
-    float* g_hi[3];
+    TimeSet<float> ts;  // the slice gradients: fp32 buffers in the layout of the slice tables
     GridMeta meta[3];
-    float blend_lo, blend_hi;
-    float lag[4];
-    int same_slice;
 };
+
+// The run-merging walk of one item: rows [m0, m1) of column `gcol` of grad_out at one level of the pair with coordinate columns (ca, cb), on
+// 4 lanes (corner c) per scattered float.  The lane keeps the sum of its corner of the current cell and adds it to dst_of(row of the corner)
+// when the cell changes.  `factor`: what the gradient is multiplied by before the weight (the literal 1 folds away).
+template <class Dst>
+__device__ __forceinline__ void walk_runs(const float* __restrict__ x, uint32_t x_stride, const float* __restrict__ grad_out, uint32_t gcol, uint32_t m0,
+                                          uint32_t m1, uint32_t ca, uint32_t cb, const GridMeta& g, uint32_t l, int c, float factor, Dst dst_of) {
+    const float scale = g.scale[l];
+    const uint32_t res = g.res[l], row0 = g.offset[l], hsize = g.offset[l + 1] - row0;
+    float acc = 0.0f;
+    uint32_t cur[2] = {0u, 0u};
+    bool have = false;
+    float* dst = dst_of(0);
+    float xy_n[2] = {x[(size_t)m0 * x_stride + ca], x[(size_t)m0 * x_stride + cb]};
+    float g_n = grad_out[(size_t)m0 * (3 * kPlaneLevels) + gcol];
+    for (uint32_t m = m0; m < m1; ++m) {
+        const float xy[2] = {xy_n[0], xy_n[1]}, go = g_n;
+        if (m + 1 < m1) {
+            xy_n[0] = x[(size_t)(m + 1) * x_stride + ca];
+            xy_n[1] = x[(size_t)(m + 1) * x_stride + cb];
+            g_n = grad_out[(size_t)(m + 1) * (3 * kPlaneLevels) + gcol];
+        }
+        if (go == 0.0f) continue;
+        float frac[2];
+        uint32_t cell[2];
+        grid_cell<2>(xy, scale, cell, frac);
+        const float w = ((c & 1) ? frac[0] : (1.0f - frac[0])) * ((c & 2) ? frac[1] : (1.0f - frac[1]));
+        if (!(have && cell[0] == cur[0] && cell[1] == cur[1])) {
+            if (acc != 0.0f) atomicAdd(dst, acc);
+            acc = 0.0f;
+            have = true;
+            cur[0] = cell[0]; cur[1] = cell[1];
+            const uint32_t cc[2] = {cell[0] + (uint32_t)(c & 1), cell[1] + (uint32_t)((c >> 1) & 1)};
+            dst = dst_of((size_t)row0 + grid_row<2>(cc, res, hsize));
+        }
+        acc += w * (go * factor);
+    }
+    if (acc != 0.0f) atomicAdd(dst, acc);
+}
 
 __global__ __launch_bounds__(kBlock) void k_hash_dynamic_bwd(const float* __restrict__ x, uint32_t x_stride, uint32_t M,
                                                              const float* __restrict__ grad_out, PlaneGrads pg, uint32_t run) {
     const int lane = lane_id();
     const int sub = lane >> 4, r = lane & 15, c = r >> 2, f = r & 3;
-    const uint32_t n_sl = pg.same_slice ? 1u : 2u;
+    const uint32_t n_sl = pg.ts.same_slice ? 1u : 2u;
     const uint32_t per_chunk = 3u * kPlaneLevels * n_sl;
     const unsigned long long item = ((unsigned long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 4ull + (unsigned)sub;
     const uint32_t chunk = (uint32_t)(item / per_chunk), rest = (uint32_t)(item - (unsigned long long)chunk * per_chunk);
@@ -361,42 +350,11 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic_bwd(const float* __rest
     const unsigned long long first = (unsigned long long)chunk * run;
     if (first >= M) return;
     const uint32_t m0 = (uint32_t)first, m1 = (uint32_t)(first + run < M ? first + run : M);
-    const GridMeta& g = pg.meta[pl];
-    const float scale = g.scale[l];
-    const uint32_t res = g.res[l], row0 = g.offset[l], hsize = g.offset[l + 1] - row0;
-    float* table = sl ? pg.g_hi[pl] : pg.g_lo[pl];
-    const float factor = pg.lag[f] * (pg.same_slice ? 1.0f : (sl ? pg.blend_hi : pg.blend_lo));
+    float* table = sl ? pg.ts.table_hi[pl] : pg.ts.table_lo[pl];
+    const float factor = pg.ts.lag[f] * (pg.ts.same_slice ? 1.0f : (sl ? pg.ts.blend_hi : pg.ts.blend_lo));
     const uint32_t ca = pl == 2 ? 1u : 0u, cb = pl == 0 ? 1u : 2u;  // coordinate columns of the pair: (x,y), (x,z), (y,z)
-    float acc = 0.0f;
-    uint32_t cur0 = 0u, cur1 = 0u;
-    bool have = false;
-    float* dst = table;
-    float xa_n = x[(size_t)m0 * x_stride + ca], xb_n = x[(size_t)m0 * x_stride + cb];
-    float g_n = grad_out[(size_t)m0 * (3 * kPlaneLevels) + pl * kPlaneLevels + l];
-    for (uint32_t m = m0; m < m1; ++m) {
-        const float xa = xa_n, xb = xb_n, go = g_n;
-        if (m + 1 < m1) {
-            xa_n = x[(size_t)(m + 1) * x_stride + ca];
-            xb_n = x[(size_t)(m + 1) * x_stride + cb];
-            g_n = grad_out[(size_t)(m + 1) * (3 * kPlaneLevels) + pl * kPlaneLevels + l];
-        }
-        if (go == 0.0f) continue;
-        const float pa = fmaf(scale, xa, 0.5f), pb = fmaf(scale, xb, 0.5f);
-        const float fa = floorf(pa), fb = floorf(pb);
-        const float ra = pa - fa, rb = pb - fb;
-        const uint32_t ia = (uint32_t)(int32_t)fa, ib = (uint32_t)(int32_t)fb;
-        const float w = ((c & 1) ? ra : (1.0f - ra)) * ((c & 2) ? rb : (1.0f - rb));
-        if (!(have && ia == cur0 && ib == cur1)) {
-            if (acc != 0.0f) atomicAdd(dst, acc);
-            acc = 0.0f;
-            have = true;
-            cur0 = ia; cur1 = ib;
-            const uint32_t cc[2] = {ia + (uint32_t)(c & 1), ib + (uint32_t)((c >> 1) & 1)};
-            dst = table + ((size_t)row0 + grid_row<2>(cc, res, hsize)) * kF + f;
-        }
-        acc += w * (go * factor);
-    }
-    if (acc != 0.0f) atomicAdd(dst, acc);
+    walk_runs(x, x_stride, grad_out, pl * kPlaneLevels + l, m0, m1, ca, cb, pg.meta[pl], l, c, factor,
+              [&](size_t row) { return table + row * kF + f; });
 }
 
 // The scalar form of the same gradient: the four features of a table entry are the four Lagrange chunks, so their gradients
@@ -418,41 +376,9 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic_bwd_scalar(const float*
     const unsigned long long first = (unsigned long long)chunk * run;
     if (first >= M) return;
     const uint32_t m0 = (uint32_t)first, m1 = (uint32_t)(first + run < M ? first + run : M);
-    const GridMeta& g = pg.meta[pl];
-    const float scale = g.scale[l];
-    const uint32_t res = g.res[l], row0 = g.offset[l], hsize = g.offset[l + 1] - row0;
     float* table = pg.g[pl];
     const uint32_t ca = pl == 2 ? 1u : 0u, cb = pl == 0 ? 1u : 2u;
-    float acc = 0.0f;
-    uint32_t cur0 = 0u, cur1 = 0u;
-    bool have = false;
-    float* dst = table;
-    float xa_n = x[(size_t)m0 * x_stride + ca], xb_n = x[(size_t)m0 * x_stride + cb];
-    float g_n = grad_out[(size_t)m0 * (3 * kPlaneLevels) + pl * kPlaneLevels + l];
-    for (uint32_t m = m0; m < m1; ++m) {
-        const float xa = xa_n, xb = xb_n, go = g_n;
-        if (m + 1 < m1) {
-            xa_n = x[(size_t)(m + 1) * x_stride + ca];
-            xb_n = x[(size_t)(m + 1) * x_stride + cb];
-            g_n = grad_out[(size_t)(m + 1) * (3 * kPlaneLevels) + pl * kPlaneLevels + l];
-        }
-        if (go == 0.0f) continue;
-        const float pa = fmaf(scale, xa, 0.5f), pb = fmaf(scale, xb, 0.5f);
-        const float fa = floorf(pa), fb = floorf(pb);
-        const float ra = pa - fa, rb = pb - fb;
-        const uint32_t ia = (uint32_t)(int32_t)fa, ib = (uint32_t)(int32_t)fb;
-        const float w = ((c & 1) ? ra : (1.0f - ra)) * ((c & 2) ? rb : (1.0f - rb));
-        if (!(have && ia == cur0 && ib == cur1)) {
-            if (acc != 0.0f) atomicAdd(dst, acc);
-            acc = 0.0f;
-            have = true;
-            cur0 = ia; cur1 = ib;
-            const uint32_t cc[2] = {ia + (uint32_t)(c & 1), ib + (uint32_t)((c >> 1) & 1)};
-            dst = table + ((size_t)row0 + grid_row<2>(cc, res, hsize));
-        }
-        acc += w * go;
-    }
-    if (acc != 0.0f) atomicAdd(dst, acc);
+    walk_runs(x, x_stride, grad_out, pl * kPlaneLevels + l, m0, m1, ca, cb, pg.meta[pl], l, c, 1.0f, [&](size_t row) { return table + row; });
 }
 
 // The same sums through LDS (the form nvsf_hashgrid4d_dynamic_bwd_scalar launches).  A time-sliced 2-D grid has 2^13 - 2^15
@@ -506,14 +432,14 @@ __global__ void k_hash_dynamic_bwd_lds(const float* __restrict__ x, uint32_t x_s
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (go[u] == 0.0f) continue;
-            const float pa = fmaf(scale, xa[u], 0.5f), pb = fmaf(scale, xb[u], 0.5f);
-            const float fa = floorf(pa), fb = floorf(pb);
-            const float ra = pa - fa, rb = pb - fb;
-            const uint32_t ia = (uint32_t)(int32_t)fa, ib = (uint32_t)(int32_t)fb;
+            const float xy[2] = {xa[u], xb[u]};
+            float frac[2];
+            uint32_t cell[2];
+            grid_cell<2>(xy, scale, cell, frac);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const float w = ((c & 1) ? ra : (1.0f - ra)) * ((c & 2) ? rb : (1.0f - rb));
-                const uint32_t cc[2] = {ia + (uint32_t)(c & 1), ib + (uint32_t)((c >> 1) & 1)};
+                const float w = ((c & 1) ? frac[0] : (1.0f - frac[0])) * ((c & 2) ? frac[1] : (1.0f - frac[1]));
+                const uint32_t cc[2] = {cell[0] + (uint32_t)(c & 1), cell[1] + (uint32_t)((c >> 1) & 1)};
                 const uint32_t row = grid_row<2>(cc, res, hsize) - row_lo;
                 const float v = w * go[u];
                 if (row < n_rows && v != 0.0f) atomicAdd(&s_sum[row], (double)v);
@@ -528,16 +454,34 @@ __global__ void k_hash_dynamic_bwd_lds(const float* __restrict__ x, uint32_t x_s
     }
 }
 
-int fill_meta(GridMeta& meta, uint32_t L, const float* scales, const uint32_t* res, const uint32_t* offsets) {
-    if (L == 0 || L > (uint32_t)kMaxLevels || !scales || !res || !offsets) return NVSF_ERR_INVALID_ARG;
-    for (uint32_t l = 0; l < L; ++l) {
-        meta.scale[l] = scales[l];
-        meta.res[l] = res[l];
-        meta.offset[l] = offsets[l];
-        if (offsets[l + 1] <= offsets[l] || res[l] == 0) return NVSF_ERR_INVALID_ARG;
+// The level tables of the three pairs from the entry points' [3][8] / [3][9] arrays
+int fill_pair_metas(GridMeta (&meta)[3], const float* h_scales, const uint32_t* h_res, const uint32_t* h_offsets) {
+    for (int p = 0; p < 3; ++p) {
+        const int st = fill_meta(meta[p], kPlaneLevels, h_scales + p * kPlaneLevels, h_res + p * kPlaneLevels, h_offsets + p * (kPlaneLevels + 1));
+        if (st != NVSF_OK) return st;
     }
-    meta.offset[L] = offsets[L];
     return NVSF_OK;
+}
+
+// One evaluation's time side: tables6 = lo slice of pair 0,1,2 then hi slice of pair 0,1,2; h_time = {blend_lo, blend_hi, w0, w1, w2, w3}
+template <typename T, typename P>
+void fill_time_set(TimeSet<T>& ts, P* const* tables6, const float* h_time, int same_slice) {
+    for (int p = 0; p < 3; ++p) {
+        ts.table_lo[p] = reinterpret_cast<T*>(tables6[p]);
+        ts.table_hi[p] = reinterpret_cast<T*>(tables6[3 + p]);
+    }
+    ts.blend_lo = h_time[0]; ts.blend_hi = h_time[1];
+    for (int i = 0; i < 4; ++i) ts.lag[i] = h_time[2 + i];
+    ts.same_slice = same_slice;
+}
+// every slice it reads is there (the hi slices only when there is a blend) and aligned to `align_mask` + 1 bytes
+template <typename T>
+bool time_set_ok(const TimeSet<T>& ts, uintptr_t align_mask) {
+    for (int p = 0; p < 3; ++p) {
+        if (!(ts.table_lo[p] && (ts.same_slice || ts.table_hi[p]))) return false;
+        if (((reinterpret_cast<uintptr_t>(ts.table_lo[p]) | reinterpret_cast<uintptr_t>(ts.table_hi[p])) & align_mask) != 0) return false;
+    }
+    return true;
 }
 }  // namespace
 
@@ -551,17 +495,10 @@ NVSF_API int nvsf_hashgrid4d_dynamic_fwd(const float* x, uint32_t x_stride, cons
     REQUIRE(x && h_tables_f16 && h_time && out && x_stride >= 3 && (mode == 0 || mode == 1));
     REQUIRE(!offset || off_stride >= off_col + 3);
     PlaneSet ps;
-    for (int p = 0; p < 3; ++p) {
-        ps.table_lo[p] = reinterpret_cast<const _Float16*>(h_tables_f16[p]);
-        ps.table_hi[p] = reinterpret_cast<const _Float16*>(h_tables_f16[3 + p]);
-        REQUIRE(ps.table_lo[p] && (same_slice || ps.table_hi[p]));
-        REQUIRE((reinterpret_cast<uintptr_t>(ps.table_lo[p]) & 7u) == 0 && (reinterpret_cast<uintptr_t>(ps.table_hi[p]) & 7u) == 0);
-        const int st = fill_meta(ps.meta[p], kPlaneLevels, h_scales + p * kPlaneLevels, h_res + p * kPlaneLevels, h_offsets + p * (kPlaneLevels + 1));
-        if (st != NVSF_OK) return st;
-    }
-    ps.blend_lo = h_time[0]; ps.blend_hi = h_time[1];
-    for (int i = 0; i < 4; ++i) ps.lag[i] = h_time[2 + i];
-    ps.same_slice = same_slice;
+    fill_time_set(ps.ts, h_tables_f16, h_time, same_slice);
+    REQUIRE(time_set_ok(ps.ts, 7u));
+    const int st = fill_pair_metas(ps.meta, h_scales, h_res, h_offsets);
+    if (st != NVSF_OK) return st;
     const dim3 grid(cdiv(M, kSamplesPerBlock)), block(kBlock);
     if (mode == 0) hipLaunchKernelGGL(k_hash_dynamic<0>, grid, block, 0, stream, x, x_stride, offset, off_stride, off_col, M, ps, out);
     else hipLaunchKernelGGL(k_hash_dynamic<1>, grid, block, 0, stream, x, x_stride, offset, off_stride, off_col, M, ps, out);
@@ -591,16 +528,10 @@ NVSF_API int nvsf_hashgrid4d_dynamic_bwd(const float* x, uint32_t x_stride, uint
     if (M == 0) return NVSF_OK;
     REQUIRE(x && h_time && grad_out && h_grad_tables_f32 && x_stride >= 3);
     PlaneGrads pg;
-    for (int p = 0; p < 3; ++p) {
-        pg.g_lo[p] = reinterpret_cast<float*>(h_grad_tables_f32[p]);
-        pg.g_hi[p] = reinterpret_cast<float*>(h_grad_tables_f32[3 + p]);
-        REQUIRE(pg.g_lo[p] && (same_slice || pg.g_hi[p]));
-        const int st = fill_meta(pg.meta[p], kPlaneLevels, h_scales + p * kPlaneLevels, h_res + p * kPlaneLevels, h_offsets + p * (kPlaneLevels + 1));
-        if (st != NVSF_OK) return st;
-    }
-    pg.blend_lo = h_time[0]; pg.blend_hi = h_time[1];
-    for (int i = 0; i < 4; ++i) pg.lag[i] = h_time[2 + i];
-    pg.same_slice = same_slice;
+    fill_time_set(pg.ts, h_grad_tables_f32, h_time, same_slice);
+    REQUIRE(time_set_ok(pg.ts, 0u));
+    const int st = fill_pair_metas(pg.meta, h_scales, h_res, h_offsets);
+    if (st != NVSF_OK) return st;
     const uint32_t run = M >= (1u << 20) ? 128u : 32u;
     const unsigned long long items = (unsigned long long)cdiv(M, run) * 3ull * kPlaneLevels * (same_slice ? 1u : 2u);
     const unsigned long long waves = (items + 3) / 4;
@@ -620,25 +551,14 @@ NVSF_API int nvsf_hashgrid4d_dynamic3_fwd(const float* x, uint32_t x_stride, con
     if (M == 0) return NVSF_OK;
     REQUIRE(x && h_tables_f16 && h_time && h_flags && out0 && x_stride >= 3);
     PlaneSet3 ps;
-    for (int p = 0; p < 3; ++p) {
-        const int st = fill_meta(ps.meta[p], kPlaneLevels, h_scales + p * kPlaneLevels, h_res + p * kPlaneLevels, h_offsets + p * (kPlaneLevels + 1));
-        if (st != NVSF_OK) return st;
-    }
+    const int st = fill_pair_metas(ps.meta, h_scales, h_res, h_offsets);
+    if (st != NVSF_OK) return st;
     for (int e = 0; e < 3; ++e) {
         ps.enabled[e] = e == 0 ? 1 : h_flags[3 * e];
         ps.share[e] = h_flags[3 * e + 2];
-        TimeSet& pe = ps.ev[e];
-        pe.same_slice = h_flags[3 * e + 1];
-        for (int p = 0; p < 3; ++p) {
-            pe.table_lo[p] = reinterpret_cast<const _Float16*>(h_tables_f16[6 * e + p]);
-            pe.table_hi[p] = reinterpret_cast<const _Float16*>(h_tables_f16[6 * e + 3 + p]);
-            if (ps.enabled[e]) {
-                REQUIRE(pe.table_lo[p] && (pe.same_slice || pe.table_hi[p]));
-                REQUIRE((reinterpret_cast<uintptr_t>(pe.table_lo[p]) & 7u) == 0 && (reinterpret_cast<uintptr_t>(pe.table_hi[p]) & 7u) == 0);
-            }
-        }
-        pe.blend_lo = h_time[6 * e]; pe.blend_hi = h_time[6 * e + 1];
-        for (int i = 0; i < 4; ++i) pe.lag[i] = h_time[6 * e + 2 + i];
+        TimeSet<const _Float16>& pe = ps.ev[e];
+        fill_time_set(pe, h_tables_f16 + 6 * e, h_time + 6 * e, h_flags[3 * e + 1]);
+        if (ps.enabled[e]) REQUIRE(time_set_ok(pe, 7u));
         if (e > 0 && ps.enabled[e]) {
             REQUIRE(offsets && off_stride >= 6 && (e == 1 ? out1 : out2));
             if (ps.share[e]) REQUIRE(pe.same_slice == ps.ev[0].same_slice);
@@ -659,9 +579,9 @@ static int hash4d_bwd_scalar_impl(const float* x, uint32_t x_stride, uint32_t M,
     for (int p = 0; p < 3; ++p) {
         pg.g[p] = reinterpret_cast<float*>(h_sums_f32[p]);
         REQUIRE(pg.g[p]);
-        const int st = fill_meta(pg.meta[p], kPlaneLevels, h_scales + p * kPlaneLevels, h_res + p * kPlaneLevels, h_offsets + p * (kPlaneLevels + 1));
-        if (st != NVSF_OK) return st;
     }
+    const int st = fill_pair_metas(pg.meta, h_scales, h_res, h_offsets);
+    if (st != NVSF_OK) return st;
     // LDS form: one launch per group of pairs with the same level size (pair 0: 2^15 rows = two row ranges of 128 KB of 64-bit sums,
     // 1024-thread workgroups; pairs 1, 2: 2^13 rows = 64 KB, 512 threads).  Variant 1 (tests) selects the run-merging global-atomic
     // kernel (the reference form; also taken when a level does not fit LDS or the batch is too small to fill the chip with slices).

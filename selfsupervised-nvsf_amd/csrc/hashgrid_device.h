@@ -14,6 +14,19 @@ struct GridMeta {
     uint32_t offset[kMaxLevels + 1];  // first feature-vector row of each level; offset[L] = total rows
 };
 
+// Host: the level table of an entry point's (scales, res, offsets) arrays, checked
+static inline int fill_meta(GridMeta& meta, uint32_t L, const float* scales, const uint32_t* res, const uint32_t* offsets) {
+    if (L == 0 || L > (uint32_t)kMaxLevels || !scales || !res || !offsets) return NVSF_ERR_INVALID_ARG;
+    for (uint32_t l = 0; l < L; ++l) {
+        meta.scale[l] = scales[l];
+        meta.res[l] = res[l];
+        meta.offset[l] = offsets[l];
+        if (offsets[l + 1] <= offsets[l] || res[l] == 0) return NVSF_ERR_INVALID_ARG;
+    }
+    meta.offset[L] = offsets[L];
+    return NVSF_OK;
+}
+
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
@@ -33,6 +46,25 @@ __device__ __forceinline__ void load_feat(const _Float16* __restrict__ table, si
         const vec_t t = *reinterpret_cast<const vec_t*>(table + row * F);
 #pragma unroll
         for (int f = 0; f < F; ++f) v[f] = (float)t[f];
+    }
+}
+
+// Element i of a gradient matrix that arrives as fp16 or fp32
+template <bool GRAD_F16>
+__device__ __forceinline__ float load_grad(const void* __restrict__ g, size_t i) {
+    if constexpr (GRAD_F16) return (float)reinterpret_cast<const _Float16*>(g)[i];
+    else return reinterpret_cast<const float*>(g)[i];
+}
+
+// Cell and position inside the cell of a sample at one level: pos = scale * x + 0.5 (one fma), cell = floor(pos), frac = pos - cell
+template <int D>
+__device__ __forceinline__ void grid_cell(const float (&x)[D], float scale, uint32_t (&cell)[D], float (&frac)[D]) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        const float pos = fmaf(scale, x[d], 0.5f);
+        const float fl = floorf(pos);
+        frac[d] = pos - fl;
+        cell[d] = (uint32_t)(int32_t)fl;
     }
 }
 
@@ -67,13 +99,7 @@ __device__ __forceinline__ void encode_level(const float (&x)[D], const _Float16
                                              uint32_t res, uint32_t row0, uint32_t hsize, float (&acc)[F]) {
     float frac[D];
     uint32_t cell[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const float pos = fmaf(scale, x[d], 0.5f);
-        const float fl = floorf(pos);
-        frac[d] = pos - fl;
-        cell[d] = (uint32_t)(int32_t)fl;
-    }
+    grid_cell<D>(x, scale, cell, frac);
 #pragma unroll
     for (int f = 0; f < F; ++f) acc[f] = 0.0f;
     // issue all 2^D gathers first, then blend (keeps 2^D loads in flight per lane)

@@ -23,8 +23,8 @@ struct PlaneMeta {
     uint32_t n_scales;
 };
 
-__device__ __constant__ const int kPa[6] = {0, 0, 0, 1, 1, 2};
-__device__ __constant__ const int kPb[6] = {1, 2, 3, 2, 3, 3};
+constexpr int kPa[6] = {0, 0, 0, 1, 1, 2};  // the two axes of plane q (host and device)
+constexpr int kPb[6] = {1, 2, 3, 2, 3, 3};
 
 struct Tap {
     uint32_t i00, i01, i10, i11;   // texel indices (row-major, clamped into the image)
@@ -33,24 +33,40 @@ struct Tap {
     float ix_f, iy_f, x0, y0;
 };
 
-__device__ __forceinline__ Tap make_tap(float pa, float pb, uint32_t W, uint32_t H) {
-    Tap t;
-    float ix = ((pa * 2.0f - 1.0f + 1.0f) / 2.0f) * (float)(W - 1);
-    float iy = ((pb * 2.0f - 1.0f + 1.0f) / 2.0f) * (float)(H - 1);
+// One coordinate axis of grid_sample (align_corners, border padding): u = ((p * 2 - 1 + 1) / 2) * (R - 1) clamped into the image, its cell
+// and the two linear weights (x1 - u, u - x0).  A plane's bilinear weights are products of two axes' weights, so whoever evaluates
+// several planes of one position shares the axes (k_planes_fwd_runs: three or four axis evaluations for three planes instead of six).
+struct Axis {
+    uint32_t c0, c1;   // cell and its upper neighbour (clamped into the image: an out-of-image tap carries weight 0)
+    float w0, w1;
+    float u, f0;       // the clamped coordinate and its floor
+    float grad;        // d u / d p (0 where the border clamp is active)
+};
+__device__ __forceinline__ Axis make_axis(float pv, uint32_t R) {
+    Axis a;
+    float u = ((pv * 2.0f - 1.0f + 1.0f) / 2.0f) * (float)(R - 1);
     // torch's border clamp passes no gradient AT the border either (clip_coordinates_set_grad: in <= 0, in >= max)
-    t.gx = (ix <= 0.0f || ix >= (float)(W - 1)) ? 0.0f : (float)(W - 1);
-    t.gy = (iy <= 0.0f || iy >= (float)(H - 1)) ? 0.0f : (float)(H - 1);
-    ix = fminf((float)(W - 1), fmaxf(ix, 0.0f));
-    iy = fminf((float)(H - 1), fmaxf(iy, 0.0f));
-    const float x0 = floorf(ix), y0 = floorf(iy), x1 = x0 + 1.0f, y1 = y0 + 1.0f;
-    t.nw = (x1 - ix) * (y1 - iy);
-    t.ne = (ix - x0) * (y1 - iy);
-    t.sw = (x1 - ix) * (iy - y0);
-    t.se = (ix - x0) * (iy - y0);
-    const uint32_t X0 = (uint32_t)x0, Y0 = (uint32_t)y0;
-    const uint32_t X1 = X0 + 1 < W ? X0 + 1 : W - 1, Y1 = Y0 + 1 < H ? Y0 + 1 : H - 1;  // out-of-image taps carry weight 0
-    t.i00 = Y0 * W + X0; t.i01 = Y0 * W + X1; t.i10 = Y1 * W + X0; t.i11 = Y1 * W + X1;
-    t.ix_f = ix; t.iy_f = iy; t.x0 = x0; t.y0 = y0;
+    a.grad = (u <= 0.0f || u >= (float)(R - 1)) ? 0.0f : (float)(R - 1);
+    u = fminf((float)(R - 1), fmaxf(u, 0.0f));
+    const float f0 = floorf(u), f1 = f0 + 1.0f;
+    a.w0 = f1 - u;
+    a.w1 = u - f0;
+    a.c0 = (uint32_t)f0;
+    a.c1 = a.c0 + 1 < R ? a.c0 + 1 : R - 1;
+    a.u = u; a.f0 = f0;
+    return a;
+}
+
+__device__ __forceinline__ Tap make_tap(float pa, float pb, uint32_t W, uint32_t H) {
+    const Axis A = make_axis(pa, W), B = make_axis(pb, H);
+    Tap t;
+    t.gx = A.grad; t.gy = B.grad;
+    t.nw = A.w0 * B.w0;
+    t.ne = A.w1 * B.w0;
+    t.sw = A.w0 * B.w1;
+    t.se = A.w1 * B.w1;
+    t.i00 = B.c0 * W + A.c0; t.i01 = B.c0 * W + A.c1; t.i10 = B.c1 * W + A.c0; t.i11 = B.c1 * W + A.c1;
+    t.ix_f = A.u; t.iy_f = B.u; t.x0 = A.f0; t.y0 = B.f0;
     return t;
 }
 
@@ -129,19 +145,33 @@ __global__ __launch_bounds__(kBlock) void k_planes_fwd(const float* __restrict__
 // are ONE launch and no [M,4] position copies are built for the neighbours.
 constexpr int kRun = 64;
 constexpr int kMaxEval = 4;
-struct PlaneEvals {
+struct EvalSet {               // what the forward and the backward of a set of evaluations share
     const float* x;            // [M, x_stride] positions in [0,1]
     uint32_t x_stride;
     int n;
     int grp[kMaxEval];         // 0: static planes (pairs 0, 1, 3), 1: time planes (pairs 2, 4, 5)
     const float* off[kMaxEval];  // optional offsets added to x (fp32 add, as torch.add): row stride / first column below
     uint32_t off_stride[kMaxEval], off_col[kMaxEval];
-    float t[kMaxEval];         // time coordinate ...
-    int t_from_x[kMaxEval];    // ... unless taken from column 3 of x
+    float t[kMaxEval];         // time coordinate
+};
+struct PlaneEvals : EvalSet {
+    int t_from_x[kMaxEval];    // the time is taken from column 3 of x instead
     float* out[kMaxEval];      // [M, n_scales * 8]
     int blend;                 // 2: as 1 with fp16 output rows; 1: the evaluations are (static, dynamic, dynamic at neighbour 1, dynamic at neighbour 2) and out[1]
                                // receives 0.5 d + 0.25 (d1 + d2) (network_dynamic.py:273); out[2], out[3] are not written
 };
+
+// Position of row m of an evaluation: x (+ its offset), and the evaluation's time
+__device__ __forceinline__ float4 eval_position(const float* __restrict__ x, uint32_t x_stride, const float* __restrict__ off, uint32_t off_stride,
+                                                uint32_t off_col, float t, uint32_t m) {
+    const float* px = x + (size_t)m * x_stride;
+    float4 p = make_float4(px[0], px[1], px[2], t);
+    if (off) {
+        const float* po = off + (size_t)m * off_stride + off_col;
+        p.x = p.x + po[0]; p.y = p.y + po[1]; p.z = p.z + po[2];  // fp32 adds, as torch.add forms x + flow
+    }
+    return p;
+}
 
 __global__ __launch_bounds__(kBlock) void k_planes_fwd_runs(PlaneEvals ev, uint32_t M, const float* __restrict__ planes, PlaneMeta meta) {
     __shared__ uint32_t s_res[kMaxScales][4], s_off[kMaxScales][6];
@@ -172,12 +202,8 @@ __global__ __launch_bounds__(kBlock) void k_planes_fwd_runs(PlaneEvals ev, uint3
         for (uint32_t k = li; k < (uint32_t)kRun; k += lanes_per_item) {
             const uint32_t m = mb + k;
             if (active && m < M) {
-                const float* px = ev.x + (size_t)m * ev.x_stride;
-                float4 p = make_float4(px[0], px[1], px[2], tx ? px[3] : tc);
-                if (soff) {
-                    const float* po = soff + (size_t)m * so_stride + so_col;
-                    p.x = p.x + po[0]; p.y = p.y + po[1]; p.z = p.z + po[2];
-                }
+                float4 p = eval_position(ev.x, ev.x_stride, soff, so_stride, so_col, tc, m);
+                if (tx) p.w = ev.x[(size_t)m * ev.x_stride + 3];
                 s_pos[item_local][k] = p;
             }
         }
@@ -198,23 +224,9 @@ __global__ __launch_bounds__(kBlock) void k_planes_fwd_runs(PlaneEvals ev, uint3
     const float t_const = ev.t[e];
     float* out = ev.out[e] + (size_t)s * kC + half * 4u;
     const uint32_t stride = meta.n_scales * kC;
-    // One coordinate axis of make_tap: u = ((p * 2 - 1 + 1) / 2) * (R - 1) clamped into the image, its cell and the two linear
-    // weights (x1 - u, u - x0).  A plane's bilinear weights are products of two axes' weights -- the same products, in the same
-    // order, as make_tap forms them -- so the three planes of a group share three (static) or four (dynamic; the time axis is
-    // constant along the chunk) axis evaluations instead of six.
-    struct Axis { uint32_t c0, c1; float w0, w1; };
-    auto axis = [](float pv, uint32_t R) {
-        Axis a;
-        float u = ((pv * 2.0f - 1.0f + 1.0f) / 2.0f) * (float)(R - 1);
-        u = fminf((float)(R - 1), fmaxf(u, 0.0f));
-        const float f0 = floorf(u), f1 = f0 + 1.0f;
-        a.w0 = f1 - u;
-        a.w1 = u - f0;
-        a.c0 = (uint32_t)f0;
-        a.c1 = a.c0 + 1 < R ? a.c0 + 1 : R - 1;
-        return a;
-    };
-    const Axis at = axis(t_const, s_res[s][3]);  // used by the dynamic group unless the time comes from the rows
+    // the three planes of a group share three (static) or four (dynamic; the time axis is constant along the chunk) axis evaluations:
+    // the same products of two axes' weights, in the same order, as make_tap forms them
+    const Axis at = make_axis(t_const, s_res[s][3]);  // used by the dynamic group unless the time comes from the rows
     uint32_t key[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
     float4 tex[3][4];
     const uint32_t m0 = chunk * kRun, m1 = m0 + kRun < M ? m0 + kRun : M;
@@ -223,8 +235,8 @@ __global__ __launch_bounds__(kBlock) void k_planes_fwd_runs(PlaneEvals ev, uint3
         const float p[3] = {pp.x, pp.y, pp.z};
         Axis ax[4];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) ax[d] = axis(p[d], s_res[s][d]);
-        ax[3] = t_from_x ? axis(pp.w, s_res[s][3]) : at;
+        for (int d = 0; d < 3; ++d) ax[d] = make_axis(p[d], s_res[s][d]);
+        ax[3] = t_from_x ? make_axis(pp.w, s_res[s][3]) : at;
         float4 f;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -341,50 +353,26 @@ __global__ __launch_bounds__(kBlock) void k_planes_bwd(const float* __restrict__
     if (g_xt) reinterpret_cast<float4*>(g_xt)[m] = make_float4(gp[0], gp[1], gp[2], gp[3]);
 }
 
-// Plane gradients with run merging (the form nvsf_planes_bwd launches; k_planes_bwd above then only produces grad_xt).
-// One atomic per (sample, texel, channel) is 1.2 G adds per 1.6 M samples into tables of 8 K - 0.5 M floats, and the time
-// planes receive all of them in the two rows around the frame's t: float atomics execute at the memory side and many
-// adders on one row are the slowest case (MI355X_MICROARCH.md, Global float atomics) -- 171 ms per call.  Rows of xt are
-// consecutive samples of a ray, 0.07 - 0.3 texels apart even at the finest scale, so an item = (chunk of `run` rows,
-// scale, static | time group) keeps the sums of the current texel quad of each of its three planes in registers and adds
-// them only when that plane's quad changes.  32 lanes per item: lane = (texel of the quad, channel), i.e. a flush is one
-// atomic instruction covering four whole 32-byte texels.  The interpolated values the products need are rebuilt from the
-// lanes' own gathers (butterfly sum over the four texel lanes).
-__global__ __launch_bounds__(kBlock) void k_planes_bwd_runs(const float* __restrict__ xt, uint32_t M, const float* __restrict__ planes,
-                                                            PlaneMeta meta, int want, const float* __restrict__ g_static,
-                                                            const float* __restrict__ g_dynamic, float* __restrict__ g_planes,
-                                                            uint32_t run) {
-    // taps of 32 samples x 3 planes of an item: {nw, ne, sw, se, i00, i01, i10, i11}.  All 32 lanes of an item would compute
-    // the same taps; instead lane k computes those of sample k of a round of 32 and the round then reads them back as
-    // broadcasts (the tap arithmetic was 3/4 of this kernel's instructions).
-    __shared__ uint32_t s_taps[kBlock / 32][32][3][8];
+// The run-merging walk of one item of the texel scatter (k_planes_bwd_runs, k_planes_multi_bwd_runs: the comments there): rows
+// [m0, m0 + n_rows) of one (scale ss, group of three planes) on 32 lanes, positions from pos(m) (a float4), the gradient rows of `stride`
+// floats at gbase times g_scale (x 1 is exact and the literal folds away: the unblended form is unchanged).  `taps`: the item's staging rows.
+template <class Pos>
+__device__ __forceinline__ void scatter_runs(const Pos& pos, const float* __restrict__ gbase, uint32_t stride, float g_scale, int grp, uint32_t ss,
+                                             uint32_t m0, uint32_t n_rows, uint32_t M, uint32_t run, const float* __restrict__ planes,
+                                             const PlaneMeta& meta, float* __restrict__ g_planes, uint32_t (*taps)[3][8]) {
     const int lane = lane_id();
     // lane of an item = (texel of the quad, channel): texel = bits 2-3, channel = bits 0-1 and bit 4 -- the four texel lanes of a channel
     // are then 4 apart inside one DPP row of 16 and their sum is two rotate-and-add instructions (no LDS round trip)
-    const int half = lane >> 5, k32 = lane & 31, tex = (lane >> 2) & 3, ch = (lane & 3) | ((lane >> 2) & 4);
-    const uint32_t n_grp = (want & 1 ? 1u : 0u) + (want & 2 ? 1u : 0u);
-    const unsigned long long item = ((unsigned long long)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6)) * 2ull + (unsigned)half;
-    const uint32_t per_chunk = meta.n_scales * n_grp;
-    const uint32_t chunk = (uint32_t)(item / per_chunk), rest = (uint32_t)(item - (unsigned long long)chunk * per_chunk);
-    const uint32_t s = rest / n_grp;
-    const int grp = n_grp == 2 ? (int)(rest - s * n_grp) : ((want & 1) ? 0 : 1);
-    const unsigned long long first = (unsigned long long)chunk * run;
-    const bool active = first < M;  // inactive halves still execute the shuffles below
-    const uint32_t m0 = active ? (uint32_t)first : 0u, m1 = active ? (uint32_t)(first + run < M ? first + run : M) : 0u;
-    const uint32_t ss = active ? s : 0u;
-    const float* gbase = grp == 0 ? g_static : g_dynamic;
-    const uint32_t stride = meta.n_scales * kC;
+    const int k32 = lane & 31, tex = (lane >> 2) & 3, ch = (lane & 3) | ((lane >> 2) & 4);
     const int pairs[3] = {grp == 0 ? 0 : 2, grp == 0 ? 1 : 4, grp == 0 ? 3 : 5};
-    uint32_t (*taps)[3][8] = s_taps[(threadIdx.x >> 5)];
     float acc[3] = {0.0f, 0.0f, 0.0f};
     uint32_t cur[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};  // i00 of the quad being summed (identifies the quad)
     uint32_t dst[3] = {0u, 0u, 0u};
-    const uint32_t n_rows = m1 - m0;
     for (uint32_t r0 = 0; r0 < run; r0 += 32) {  // uniform trip count over the wave
-        {   // lane k32: taps of row r0 + k32
+        {   // lane k32: taps of row r0 + k32 at the item's own position
             const uint32_t r = r0 + (uint32_t)k32;
             const uint32_t m = r < n_rows ? m0 + r : (M - 1);
-            const float4 p4 = reinterpret_cast<const float4*>(xt)[m];
+            const float4 p4 = pos(m);
             const float p[4] = {p4.x, p4.y, p4.z, p4.w};
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
@@ -403,7 +391,7 @@ __global__ __launch_bounds__(kBlock) void k_planes_bwd_runs(const float* __restr
             const uint32_t r = r0 + k;
             const bool row_ok = r < n_rows;
             const uint32_t m = row_ok ? m0 + r : (M - 1);
-            const float g = row_ok ? gbase[(size_t)m * stride + ss * kC + ch] : 0.0f;
+            const float g = row_ok ? gbase[(size_t)m * stride + ss * kC + ch] * g_scale : 0.0f;
             float v[3], w[3];
             uint32_t idx[3], quad[3];
 #pragma unroll
@@ -436,6 +424,40 @@ __global__ __launch_bounds__(kBlock) void k_planes_bwd_runs(const float* __restr
         if (acc[j] != 0.0f) atomicAdd(g_planes + dst[j], acc[j]);
 }
 
+// Plane gradients with run merging (the form nvsf_planes_bwd launches; k_planes_bwd above then only produces grad_xt).
+// One atomic per (sample, texel, channel) is 1.2 G adds per 1.6 M samples into tables of 8 K - 0.5 M floats, and the time
+// planes receive all of them in the two rows around the frame's t: float atomics execute at the memory side and many
+// adders on one row are the slowest case (MI355X_MICROARCH.md, Global float atomics) -- 171 ms per call.  Rows of xt are
+// consecutive samples of a ray, 0.07 - 0.3 texels apart even at the finest scale, so an item = (chunk of `run` rows,
+// scale, static | time group) keeps the sums of the current texel quad of each of its three planes in registers and adds
+// them only when that plane's quad changes.  32 lanes per item: lane = (texel of the quad, channel), i.e. a flush is one
+// atomic instruction covering four whole 32-byte texels.  The interpolated values the products need are rebuilt from the
+// lanes' own gathers (butterfly sum over the four texel lanes).
+__global__ __launch_bounds__(kBlock) void k_planes_bwd_runs(const float* __restrict__ xt, uint32_t M, const float* __restrict__ planes,
+                                                            PlaneMeta meta, int want, const float* __restrict__ g_static,
+                                                            const float* __restrict__ g_dynamic, float* __restrict__ g_planes,
+                                                            uint32_t run) {
+    // taps of 32 samples x 3 planes of an item: {nw, ne, sw, se, i00, i01, i10, i11}.  All 32 lanes of an item would compute
+    // the same taps; instead lane k computes those of sample k of a round of 32 and the round then reads them back as
+    // broadcasts (the tap arithmetic was 3/4 of this kernel's instructions).
+    __shared__ uint32_t s_taps[kBlock / 32][32][3][8];
+    const int lane = lane_id();
+    const int half = lane >> 5;
+    const uint32_t n_grp = (want & 1 ? 1u : 0u) + (want & 2 ? 1u : 0u);
+    const unsigned long long item = ((unsigned long long)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6)) * 2ull + (unsigned)half;
+    const uint32_t per_chunk = meta.n_scales * n_grp;
+    const uint32_t chunk = (uint32_t)(item / per_chunk), rest = (uint32_t)(item - (unsigned long long)chunk * per_chunk);
+    const uint32_t s = rest / n_grp;
+    const int grp = n_grp == 2 ? (int)(rest - s * n_grp) : ((want & 1) ? 0 : 1);
+    const unsigned long long first = (unsigned long long)chunk * run;
+    const bool active = first < M;  // inactive halves still execute the shuffles below
+    const uint32_t m0 = active ? (uint32_t)first : 0u, m1 = active ? (uint32_t)(first + run < M ? first + run : M) : 0u;
+    const uint32_t ss = active ? s : 0u;
+    const float* gbase = grp == 0 ? g_static : g_dynamic;
+    scatter_runs([&](uint32_t m) { return reinterpret_cast<const float4*>(xt)[m]; }, gbase, meta.n_scales * kC, 1.0f, grp, ss, m0, m1 - m0, M,
+                 run, planes, meta, g_planes, s_taps[(threadIdx.x >> 5)]);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Backward of SEVERAL evaluations of one position set in one launch (nvsf_planes_multi_bwd; the forward is k_planes_fwd_runs with the same
 // PlaneEvals): what a density query of the space-time field evaluates under autograd -- the static planes and the time planes at (x, t),
@@ -445,14 +467,7 @@ __global__ __launch_bounds__(kBlock) void k_planes_bwd_runs(const float* __restr
 // products, same run sums: the same addends into the texels, in another order across items).  A first form that let one item walk
 // its group's evaluations in turn with ONE set of quad sums -- merging the neighbours' addends with the base evaluation's -- was
 // 25 % slower (5.4 against 3 x 1.44 ms per 3.1 M rows): three times longer items, a third of the parallelism.
-struct PlaneGradEvals {
-    const float* x;
-    uint32_t x_stride;
-    int n;
-    int grp[kMaxEval];
-    const float* off[kMaxEval];
-    uint32_t off_stride[kMaxEval], off_col[kMaxEval];
-    float t[kMaxEval];
+struct PlaneGradEvals : EvalSet {
     const float* g[kMaxEval];      // gradient of the evaluation's features, rows of n_scales * 8 floats g_stride apart (nullptr: contributes nothing)
     uint32_t g_stride[kMaxEval];   // ... a slice of a wider matrix is read in place (the density tail's input gradient)
     float g_scale[kMaxEval];       // ... times this factor: the evaluations of a BLEND 0.5 d + 0.25 (d1 + d2) share one gradient (x 0.5, 0.25, 0.25)
@@ -460,21 +475,11 @@ struct PlaneGradEvals {
     uint32_t g_off_stride[kMaxEval], g_off_col[kMaxEval];
 };
 
-__device__ __forceinline__ float4 eval_position(const PlaneGradEvals& ev, int e, uint32_t m) {
-    const float* px = ev.x + (size_t)m * ev.x_stride;
-    float4 p = make_float4(px[0], px[1], px[2], ev.t[e]);
-    if (ev.off[e]) {
-        const float* po = ev.off[e] + (size_t)m * ev.off_stride[e] + ev.off_col[e];
-        p.x = p.x + po[0]; p.y = p.y + po[1]; p.z = p.z + po[2];  // fp32 adds, as torch.add forms x + flow
-    }
-    return p;
-}
-
 __global__ __launch_bounds__(kBlock) void k_planes_multi_bwd_runs(PlaneGradEvals ev, uint32_t M, const float* __restrict__ planes, PlaneMeta meta,
                                                                   int live, float* __restrict__ g_planes, uint32_t run) {
     __shared__ uint32_t s_taps[kBlock / 32][32][3][8];
     const int lane = lane_id();
-    const int half = lane >> 5, k32 = lane & 31, tex = (lane >> 2) & 3, ch = (lane & 3) | ((lane >> 2) & 4);
+    const int half = lane >> 5;
     // item = (chunk, live evaluation, scale), the scale fastest: the two halves of a wave (consecutive items, n_scales even) share the chunk
     // AND the evaluation, whose constants are therefore wave-uniform (selected below by compares: a run-time index into the by-value
     // struct would send it to scratch).  `live`: bit e set = evaluation e has a gradient.
@@ -504,71 +509,8 @@ __global__ __launch_bounds__(kBlock) void k_planes_multi_bwd_runs(PlaneGradEvals
     const bool active = first < M && gbase != nullptr;
     const uint32_t m0 = active ? (uint32_t)first : 0u, m1 = active ? (uint32_t)(first + run < M ? first + run : M) : 0u;
     const uint32_t ss = active ? s : 0u;
-    const uint32_t stride = g_stride;
-    const int pairs[3] = {grp == 0 ? 0 : 2, grp == 0 ? 1 : 4, grp == 0 ? 3 : 5};
-    uint32_t (*taps)[3][8] = s_taps[(threadIdx.x >> 5)];
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    uint32_t cur[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    uint32_t dst[3] = {0u, 0u, 0u};
-    const uint32_t n_rows = m1 - m0;
-    for (uint32_t r0 = 0; r0 < run; r0 += 32) {  // uniform trip count over the wave
-        {   // lane k32: taps of row r0 + k32 at the evaluation's own position (x + offset, t_e)
-            const uint32_t r = r0 + (uint32_t)k32;
-            const uint32_t m = r < n_rows ? m0 + r : (M - 1);
-            const float* px = ev.x + (size_t)m * ev.x_stride;
-            float p[4] = {px[0], px[1], px[2], t_e};
-            if (off) {
-                const float* po = off + (size_t)m * off_stride + off_col;
-                p[0] = p[0] + po[0]; p[1] = p[1] + po[1]; p[2] = p[2] + po[2];  // fp32 adds, as torch.add forms x + flow
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int a = kPa[pairs[j]], b = kPb[pairs[j]];
-                const Tap t = make_tap(p[a], p[b], meta.res[ss][a], meta.res[ss][b]);
-                uint32_t* o = taps[k32][j];
-                o[0] = __builtin_bit_cast(uint32_t, t.nw); o[1] = __builtin_bit_cast(uint32_t, t.ne);
-                o[2] = __builtin_bit_cast(uint32_t, t.sw); o[3] = __builtin_bit_cast(uint32_t, t.se);
-                o[4] = t.i00; o[5] = t.i01; o[6] = t.i10; o[7] = t.i11;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (uint32_t k = 0; k < 32u; ++k) {
-            const uint32_t r = r0 + k;
-            const bool row_ok = r < n_rows;
-            const uint32_t m = row_ok ? m0 + r : (M - 1);
-            const float g = row_ok ? gbase[(size_t)m * stride + ss * kC + ch] * g_scale : 0.0f;  // (x 1 is exact: the unblended form is unchanged)
-            float v[3], w[3];
-            uint32_t idx[3], quad[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                w[j] = __builtin_bit_cast(float, taps[k][j][tex]);
-                idx[j] = taps[k][j][4 + tex];
-                quad[j] = taps[k][j][4];
-                float part = planes[meta.off[ss][pairs[j]] + (size_t)idx[j] * kC + ch] * w[j];
-                part += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, part), 0x124 /* row_ror:4 */, 0xF, 0xF, false));
-                part += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, part), 0x128 /* row_ror:8 */, 0xF, 0xF, false));
-                v[j] = part;
-            }
-            if (!row_ok) continue;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const float gv = g * (v[(j + 1) % 3] * v[(j + 2) % 3]);
-                if (quad[j] != cur[j]) {
-                    if (acc[j] != 0.0f) atomicAdd(g_planes + dst[j], acc[j]);
-                    acc[j] = 0.0f;
-                    cur[j] = quad[j];
-                    dst[j] = meta.off[ss][pairs[j]] + idx[j] * kC + ch;
-                }
-                acc[j] += gv * w[j];
-            }
-        }
-        __builtin_amdgcn_wave_barrier();  // the taps are overwritten by the next round
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        if (acc[j] != 0.0f) atomicAdd(g_planes + dst[j], acc[j]);
+    scatter_runs([&](uint32_t m) { return eval_position(ev.x, ev.x_stride, off, off_stride, off_col, t_e, m); }, gbase, g_stride, g_scale, grp, ss,
+                 m0, m1 - m0, M, run, planes, meta, g_planes, s_taps[(threadIdx.x >> 5)]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -602,20 +544,6 @@ constexpr int kTimeItems = kTimeBlock / 16;
 constexpr int kTimeRows = 8;                // rows of an item per round (taps and gradient rows staged in LDS)
 constexpr int kTimeUnroll = 4;
 
-struct TimeTap {
-    uint32_t Y0, Y1;
-    float wy0, wy1;   // (y1 - iy), (iy - y0) of make_tap
-};
-__device__ __forceinline__ TimeTap make_time_tap(float t, uint32_t H) {
-    float iy = ((t * 2.0f - 1.0f + 1.0f) / 2.0f) * (float)(H - 1);
-    iy = fminf((float)(H - 1), fmaxf(iy, 0.0f));
-    const float y0 = floorf(iy), y1 = y0 + 1.0f;
-    TimeTap r;
-    r.wy0 = y1 - iy; r.wy1 = iy - y0;
-    r.Y0 = (uint32_t)y0; r.Y1 = r.Y0 + 1 < H ? r.Y0 + 1 : H - 1;
-    return r;
-}
-
 __global__ __launch_bounds__(kTimeBlock) void k_planes_multi_bwd_time_lds(PlaneGradEvals ev, uint32_t M, const float* __restrict__ planes,
                                                                           PlaneMeta meta, int live, float* __restrict__ g_planes, uint32_t run,
                                                                           uint32_t chunks_per_slice, uint32_t s) {
@@ -625,7 +553,6 @@ __global__ __launch_bounds__(kTimeBlock) void k_planes_multi_bwd_time_lds(PlaneG
     __shared__ float s_g[kTimeItems][kTimeRows][kC];      // ... and the rows' gradient values (scaled)
     const int lane = lane_id();
     const int l16 = lane & 15, xs = (lane >> 3) & 1, ch = lane & 7;
-    const uint32_t slot = blockIdx.y;
     const float* gbase = nullptr;
     const float* off = nullptr;
     uint32_t off_stride = 0, off_col = 0, stride = 0;
@@ -635,7 +562,7 @@ __global__ __launch_bounds__(kTimeBlock) void k_planes_multi_bwd_time_lds(PlaneG
 #pragma unroll
         for (int e = 0; e < kMaxEval; ++e) {
             if (!((live >> e) & 1)) continue;
-            if (seen == slot) {
+            if (seen == blockIdx.y) {
                 gbase = ev.g[e]; off = ev.off[e]; off_stride = ev.off_stride[e]; off_col = ev.off_col[e]; t_e = ev.t[e];
                 stride = ev.g_stride[e]; g_scale = ev.g_scale[e];
             }
@@ -650,14 +577,14 @@ __global__ __launch_bounds__(kTimeBlock) void k_planes_multi_bwd_time_lds(PlaneG
     const uint32_t ioff[3] = {0u, W[0] * kC, (W[0] + W[1]) * kC};
     const uint32_t n_img = (W[0] + W[1] + W[2]) * kC;
     float* const s_A = reinterpret_cast<float*>(s_img + n_img);
-    const TimeTap ty = make_time_tap(t_e, H);
+    const Axis ty = make_axis(t_e, H);  // the two rows around t_e and their weights: (y1 - iy), (iy - y0) of make_tap
 
     // ---- the folded planes ---------------------------------------------------------------------------------------------------------
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const uint32_t row_len = W[j] * kC;
         for (uint32_t i = threadIdx.x; i < row_len; i += kTimeBlock)
-            s_A[ioff[j] + i] = planes[poff[j] + ty.Y0 * row_len + i] * ty.wy0 + planes[poff[j] + ty.Y1 * row_len + i] * ty.wy1;
+            s_A[ioff[j] + i] = planes[poff[j] + ty.c0 * row_len + i] * ty.w0 + planes[poff[j] + ty.c1 * row_len + i] * ty.w1;
     }
     for (uint32_t i = threadIdx.x; i < n_img; i += kTimeBlock) s_img[i] = 0.0;
     __syncthreads();
@@ -785,13 +712,13 @@ __global__ __launch_bounds__(kTimeBlock) void k_planes_multi_bwd_time_lds(PlaneG
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const uint32_t row_len = W[j] * kC;
-        float* r0p = g_planes + poff[j] + (size_t)ty.Y0 * row_len;
-        float* r1p = g_planes + poff[j] + (size_t)ty.Y1 * row_len;
+        float* r0p = g_planes + poff[j] + (size_t)ty.c0 * row_len;
+        float* r1p = g_planes + poff[j] + (size_t)ty.c1 * row_len;
         for (uint32_t i = threadIdx.x; i < row_len; i += kTimeBlock) {
             const double G = s_img[ioff[j] + i];
             if (G == 0.0) continue;
-            atomicAdd(r0p + i, (float)(G * (double)ty.wy0));
-            if (ty.wy1 != 0.0f) atomicAdd(r1p + i, (float)(G * (double)ty.wy1));
+            atomicAdd(r0p + i, (float)(G * (double)ty.w0));
+            if (ty.w1 != 0.0f) atomicAdd(r1p + i, (float)(G * (double)ty.w1));
         }
     }
 }
@@ -817,7 +744,7 @@ __global__ __launch_bounds__(kBlock) void k_planes_multi_coord_bwd(PlaneGradEval
         if ((int)blockIdx.y == e) {
             grp = ev.grp[e]; g_e = ev.g[e]; go_e = ev.g_off[e]; go_stride = ev.g_off_stride[e]; go_col = ev.g_off_col[e];
             g_stride = ev.g_stride[e]; g_scale = ev.g_scale[e];
-            if (g_e && go_e) p4 = eval_position(ev, e, m);
+            if (g_e && go_e) p4 = eval_position(ev.x, ev.x_stride, ev.off[e], ev.off_stride[e], ev.off_col[e], ev.t[e], m);
         }
     if (!g_e || !go_e) return;
     const float p[4] = {p4.x, p4.y, p4.z, p4.w};
@@ -867,7 +794,6 @@ __global__ __launch_bounds__(kBlock) void k_planes_multi_coord_bwd(PlaneGradEval
 
 int fill_plane_meta(PlaneMeta& meta, uint32_t n_scales, const uint32_t* h_res) {
     if (n_scales == 0 || n_scales > (uint32_t)kMaxScales || !h_res) return NVSF_ERR_INVALID_ARG;
-    static const int pa[6] = {0, 0, 0, 1, 1, 2}, pb[6] = {1, 2, 3, 2, 3, 3};
     meta.n_scales = n_scales;
     unsigned long long off = 0;
     for (uint32_t s = 0; s < n_scales; ++s) {
@@ -877,11 +803,31 @@ int fill_plane_meta(PlaneMeta& meta, uint32_t n_scales, const uint32_t* h_res) {
         }
         for (int q = 0; q < 6; ++q) {
             meta.off[s][q] = (uint32_t)off;
-            off += (unsigned long long)h_res[4 * s + pa[q]] * h_res[4 * s + pb[q]] * kC;
+            off += (unsigned long long)h_res[4 * s + kPa[q]] * h_res[4 * s + kPb[q]] * kC;
             if (off >= (1ull << 31)) return NVSF_ERR_INVALID_ARG;
         }
     }
     return NVSF_OK;
+}
+
+// What the two multi entry points share of their arguments, checked (the caller has checked the pointers themselves)
+int fill_evals(EvalSet& ev, const float* x, uint32_t x_stride, uint32_t n_evals, const int* h_group, const float* const* h_offsets,
+               const uint32_t* h_offset_stride, const uint32_t* h_offset_col, const float* h_time) {
+    ev.x = x; ev.x_stride = x_stride; ev.n = (int)n_evals;
+    for (uint32_t e = 0; e < n_evals; ++e) {
+        REQUIRE(h_group[e] == 0 || h_group[e] == 1);
+        REQUIRE(!h_offsets[e] || h_offset_stride[e] >= h_offset_col[e] + 3);
+        ev.grp[e] = h_group[e]; ev.off[e] = h_offsets[e]; ev.off_stride[e] = h_offset_stride[e]; ev.off_col[e] = h_offset_col[e];
+        ev.t[e] = h_time[e];
+    }
+    return NVSF_OK;
+}
+
+// k_planes_fwd_runs over ev's evaluations: 8 lanes per (chunk of kRun rows, evaluation)
+int launch_fwd_runs(const PlaneEvals& ev, uint32_t M, const float* planes_cl, const PlaneMeta& meta, hipStream_t stream) {
+    const unsigned long long threads = (unsigned long long)cdiv(M, kRun) * ev.n * 2u * meta.n_scales;
+    hipLaunchKernelGGL(k_planes_fwd_runs, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, ev, M, planes_cl, meta);
+    return nvsf_launch_status();
 }
 }  // namespace
 
@@ -907,9 +853,7 @@ NVSF_API int nvsf_planes_fwd(const float* xt, uint32_t M, const float* planes_cl
         ev.grp[ev.n] = grp; ev.off[ev.n] = nullptr; ev.t_from_x[ev.n] = 1; ev.out[ev.n] = grp == 0 ? out_static : out_dynamic;
         ++ev.n;
     }
-    const unsigned long long threads = (unsigned long long)cdiv(M, kRun) * ev.n * 2u * n_scales;
-    hipLaunchKernelGGL(k_planes_fwd_runs, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, ev, M, planes_cl, meta);
-    return nvsf_launch_status();
+    return launch_fwd_runs(ev, M, planes_cl, meta, stream);
 }
 
 NVSF_API int nvsf_planes_multi_fwd(const float* x, uint32_t x_stride, uint32_t M, const float* planes_cl, uint32_t n_scales, uint32_t C,
@@ -924,18 +868,15 @@ NVSF_API int nvsf_planes_multi_fwd(const float* x, uint32_t x_stride, uint32_t M
     const int st = fill_plane_meta(meta, n_scales, h_res);
     if (st != NVSF_OK) return st;
     PlaneEvals ev = {};
-    ev.x = x; ev.x_stride = x_stride; ev.n = (int)n_evals;
+    const int se = fill_evals(ev, x, x_stride, n_evals, h_group, h_offsets, h_offset_stride, h_offset_col, h_time);
+    if (se != NVSF_OK) return se;
     ev.blend = blend == 2 ? 2 : (blend ? 1 : 0);
     if (blend) REQUIRE(n_evals == 4 && h_group[0] == 0 && h_group[1] == 1 && h_group[2] == 1 && h_group[3] == 1);
     for (uint32_t e = 0; e < n_evals; ++e) {
-        REQUIRE((h_group[e] == 0 || h_group[e] == 1) && (h_out[e] || (blend && e >= 2)) && (reinterpret_cast<uintptr_t>(h_out[e]) & 15u) == 0);
-        REQUIRE(!h_offsets[e] || h_offset_stride[e] >= h_offset_col[e] + 3);
-        ev.grp[e] = h_group[e]; ev.off[e] = h_offsets[e]; ev.off_stride[e] = h_offset_stride[e]; ev.off_col[e] = h_offset_col[e];
-        ev.t[e] = h_time[e]; ev.t_from_x[e] = 0; ev.out[e] = h_out[e];
+        REQUIRE((h_out[e] || (blend && e >= 2)) && (reinterpret_cast<uintptr_t>(h_out[e]) & 15u) == 0);
+        ev.t_from_x[e] = 0; ev.out[e] = h_out[e];
     }
-    const unsigned long long threads = (unsigned long long)cdiv(M, kRun) * ev.n * 2u * n_scales;
-    hipLaunchKernelGGL(k_planes_fwd_runs, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, ev, M, planes_cl, meta);
-    return nvsf_launch_status();
+    return launch_fwd_runs(ev, M, planes_cl, meta, stream);
 }
 
 NVSF_API int nvsf_planes_bwd(const float* xt, uint32_t M, const float* planes_cl, uint32_t n_scales, uint32_t C, const uint32_t* h_res,
@@ -981,13 +922,11 @@ NVSF_API int nvsf_planes_multi_bwd(const float* x, uint32_t x_stride, uint32_t M
     const int st = fill_plane_meta(meta, n_scales, h_res);
     if (st != NVSF_OK) return st;
     PlaneGradEvals ev = {};
-    ev.x = x; ev.x_stride = x_stride; ev.n = (int)n_evals;
+    const int se = fill_evals(ev, x, x_stride, n_evals, h_group, h_offsets, h_offset_stride, h_offset_col, h_time);
+    if (se != NVSF_OK) return se;
     int groups = 0, any_coord = 0;
     for (uint32_t e = 0; e < n_evals; ++e) {
-        REQUIRE(h_group[e] == 0 || h_group[e] == 1);
-        REQUIRE(!h_offsets[e] || h_offset_stride[e] >= h_offset_col[e] + 3);
-        ev.grp[e] = h_group[e]; ev.off[e] = h_offsets[e]; ev.off_stride[e] = h_offset_stride[e]; ev.off_col[e] = h_offset_col[e];
-        ev.t[e] = h_time[e]; ev.g[e] = h_grad_out[e];
+        ev.g[e] = h_grad_out[e];
         ev.g_stride[e] = h_grad_stride ? h_grad_stride[e] : n_scales * (uint32_t)kC;
         ev.g_scale[e] = h_grad_scale ? h_grad_scale[e] : 1.0f;
         REQUIRE(!ev.g[e] || ev.g_stride[e] >= n_scales * (uint32_t)kC);

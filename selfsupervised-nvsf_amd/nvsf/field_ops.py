@@ -5,6 +5,8 @@ the trainer needs.  No arithmetic of the hot path happens in Python: every funct
 kernel launch on the current stream, forward and backward.
 """
 
+import ctypes
+
 import numpy as np
 import torch
 from torch.autograd import Function
@@ -1048,30 +1050,41 @@ class PlanesFn(Function):
         return g_xt, g_planes, None, None, None
 
 
+def _f32_rows(t):
+    """fp32 rows with unit column stride are read where they are (a column slice of a wider matrix keeps its row stride); anything else is
+    copied -- also rows that overlap (stride(0) < shape[1], an expanded tensor), which the positions / offsets normalisers this replaces
+    passed on and the kernels could not have read as rows.  None stays None."""
+    if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+        t = t.float().contiguous()
+    return t
+
+
+def _ptr_array(tensors):
+    """Host array of device pointers (None -> NULL)."""
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _eval_args(groups, offs, off_cols, times):
+    """The per-evaluation host arrays nvsf_planes_multi_fwd / _bwd share: groups, offset pointers (`offs`: the offset rows of each
+    evaluation, or None), their row strides and first columns, times."""
+    return (_hip.host_i32(groups), _ptr_array(offs), _hip.host_u32([0 if o is None else o.stride(0) for o in offs]), _hip.host_u32(off_cols),
+            _hip.host_f32(times))
+
+
 def planes_multi_forward(x, evals, planes_cl, res_host, blend=False, out_f16=False):
     """Several evaluations of ONE position set in one launch (nvsf_planes_multi_fwd): `evals` = [(group, offsets | None, offset_col, time)]
     with group 0 = static / 1 = dynamic planes; returns the list of [M, n_scales * 8] feature matrices (fp32; blend: [static, blended
     dynamic], fp16 rows with out_f16).  No autograd here: Planes4D.forward_multi (no-grad render) and PlanesMultiFn (training) call it."""
-    import ctypes
-    x = x.float()
-    if x.dim() != 2 or x.stride(1) != 1:
-        x = x.contiguous()
+    x = _f32_rows(x)
     M, n = x.shape[0], len(evals)
     S = len(res_host) // 4
     width = S * 8
     if out_f16 and not blend:
         raise ValueError("planes_multi_forward: out_f16 needs blend=True")
     outs = [torch.empty(M, width, dtype=torch.float16 if out_f16 else torch.float32, device=x.device) for _ in (evals[:2] if blend else evals)]
-    offs = []
-    for _, o, _, _ in evals:
-        if o is not None and (o.dtype != torch.float32 or o.dim() != 2 or o.stride(1) != 1):
-            o = o.float().contiguous()
-        offs.append(o)
     _hip.call("nvsf_planes_multi_fwd", _hip.ptr_rows(x), x.stride(0), M, _hip.ptr(planes_cl), S, 8, _hip.host_u32(res_host), n,
-              _hip.host_i32([e[0] for e in evals]), (ctypes.c_void_p * n)(*[None if o is None else o.data_ptr() for o in offs]),
-              _hip.host_u32([0 if o is None else o.stride(0) for o in offs]), _hip.host_u32([e[2] for e in evals]),
-              _hip.host_f32([e[3] for e in evals]), (ctypes.c_void_p * n)(*([t.data_ptr() for t in outs] + [None] * (n - len(outs)))),
-              (2 if out_f16 else 1) if blend else 0)
+              *_eval_args([e[0] for e in evals], [_f32_rows(e[1]) for e in evals], [e[2] for e in evals], [e[3] for e in evals]),
+              _ptr_array(outs + [None] * (n - len(outs))), (2 if out_f16 else 1) if blend else 0)
     return outs
 
 
@@ -1090,17 +1103,11 @@ class PlanesMultiFn(Function):
 
     @staticmethod
     def forward(ctx, x, flow, planes_cl, res_host, t0, t1, t2, train_ctx, blend=False):
-        x = x.float()
-        if x.dim() != 2 or x.stride(1) != 1:
-            x = x.contiguous()
+        x = _f32_rows(x)
         cl = planes_cl.detach()
         if cl.dtype != torch.float32 or not cl.is_contiguous():
             cl = cl.float().contiguous()
-        fl = None
-        if flow is not None:
-            fl = flow.detach().float()
-            if fl.dim() != 2 or fl.stride(1) != 1:
-                fl = fl.contiguous()
+        fl = None if flow is None else _f32_rows(flow.detach())
         base = (1, None, 0, float(t0))
         evals = [(0, None, 0, float(t0)), base]
         slots = [0, 1]
@@ -1125,46 +1132,35 @@ class PlanesMultiFn(Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        import ctypes
         saved = ctx.saved_tensors
         x, cl = saved[0], saved[1]
         fl = saved[2] if len(saved) > 2 else None
         M, S = x.shape[0], len(ctx.res_host) // 4
         need_flow, need_p = ctx.needs_input_grad[1] and fl is not None, ctx.needs_input_grad[2]
         n = len(ctx.evals_meta)
-
-        def rows(t):  # fp32 rows with unit column stride are read where they are (a slice of the density tail's input gradient)
-            if t is None:
-                return None
-            if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-                t = t.float().contiguous()
-            return t
+        # gradients that are fp32 rows with unit column stride are read where they are (a slice of the density tail's input gradient)
         if ctx.blend:
-            g_s, g_b = rows(grads[0]), rows(grads[1])
+            g_s, g_b = _f32_rows(grads[0]), _f32_rows(grads[1])
             g = [g_s] + [g_b] * (n - 1)
             scales = [1.0, 0.5] + [0.25] * (n - 2)
         else:
-            g = [rows(grads[slot]) for slot in ctx.slots]
+            g = [_f32_rows(grads[slot]) for slot in ctx.slots]
             scales = [1.0] * n
         res = _hip.host_u32(ctx.res_host)
-        groups = _hip.host_i32([m[0] for m in ctx.evals_meta])
-        has_off = [m[3] for m in ctx.evals_meta]
-        offs = (ctypes.c_void_p * n)(*[fl.data_ptr() if has_off[i] else None for i in range(n)])
-        off_stride = _hip.host_u32([fl.stride(0) if has_off[i] else 0 for i in range(n)])
-        off_col = _hip.host_u32([m[1] for m in ctx.evals_meta])
-        times = _hip.host_f32([m[2] for m in ctx.evals_meta])
-        g_ptrs = (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in g])
+        groups, off_cols, times, has_off = zip(*ctx.evals_meta)
+        eval_args = _eval_args(groups, [fl if h else None for h in has_off], off_cols, times)
+        g_ptrs = _ptr_array(g)
         g_strides = _hip.host_u32([S * 8 if t is None else t.stride(0) for t in g])
         g_scales = _hip.host_f32(scales)
 
         def launch(g_planes, g_flow):
             if g_flow is not None:
-                go = (ctypes.c_void_p * n)(*[g_flow.data_ptr() if has_off[i] else None for i in range(n)])
-                gs = _hip.host_u32([g_flow.stride(0) if has_off[i] else 0 for i in range(n)])
-                gc = _hip.host_u32([ctx.evals_meta[i][1] if has_off[i] else 0 for i in range(n)])
+                go = _ptr_array([g_flow if h else None for h in has_off])
+                gs = _hip.host_u32([g_flow.stride(0) if h else 0 for h in has_off])
+                gc = _hip.host_u32([c if h else 0 for c, h in zip(off_cols, has_off)])
             else:
                 go = gs = gc = None
-            _hip.call("nvsf_planes_multi_bwd", _hip.ptr_rows(x), x.stride(0), M, _hip.ptr(cl), S, 8, res, n, groups, offs, off_stride, off_col, times,
+            _hip.call("nvsf_planes_multi_bwd", _hip.ptr_rows(x), x.stride(0), M, _hip.ptr(cl), S, 8, res, n, *eval_args,
                       g_ptrs, g_strides, g_scales, _hip.ptr(g_planes), go, gs, gc)
         g_flow = None
         if need_flow:
