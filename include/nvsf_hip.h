@@ -845,6 +845,57 @@ int nvsf_lidar_depth_images(const float* range_m, uint32_t F, uint32_t Hl, uint3
 int nvsf_points_depth_image(const float* points, uint32_t P, const float* lidar2cam, const double* K, uint32_t H, uint32_t W, float* out,
                             nvsf_stream_t stream);
 
+/* ---- 12. object masks (static / dynamic evaluation tables) and the range-image z-buffer ------------------------------------- */
+
+/* Contract as sections 10 and 11: status return, explicit stream, no allocation, workspaces passed in and their size checked,
+ * NVSF_ERR_INVALID_ARG before any launch with outputs and workspace untouched.  `geom` is a HOST pointer to five doubles
+ * (fov_up, fov, fov_hoz_up, fov_hoz, max_depth; degrees and the cloud's length unit), read before the call returns: fov > 0,
+ * fov_hoz > 0, max_depth > 0.  `planes` [B, KMAX, 4] fp64 = (nx, ny, nz, d) with unit outward normals and `plane_counts` [B] uint32
+ * (values above KMAX count as KMAX) are DEVICE arrays; box b is the set of points with n.p + d <= 0 for its first plane_counts[b]
+ * planes, and a box without planes holds nothing.  The planes of a launch are staged in LDS once per workgroup: B KMAX <= 768
+ * (24 KiB; 64 boxes of 12 planes), a larger product is NVSF_ERR_INVALID_ARG.  B = 0 is valid (no pointer is read). */
+
+/* ref: tools.check_in_hull, nvsf/lib/tools.py:138-160 (scipy.spatial.Delaunay(hull).find_simplex(p) >= 0), as called by
+ * utils.compute_object_masks, nvsf/nerf/utils.py:781-794, and OR-ed over the boxes there.  mask[p] = 1 iff some box holds point p:
+ * the point [P, 3] fp32 is widened to fp64 and ((nx x + ny y) + nz z) + d is evaluated left to right in fp64; every element of mask
+ * [P] uint8 is written.  A NaN coordinate is in no box.  One thread per point, early exit per box.  P = 0 is a no-op, P < 2^31. */
+int nvsf_points_in_hulls(const float* points, uint32_t P, const double* planes, const uint32_t* plane_counts, uint32_t B, uint32_t KMAX,
+                         uint8_t* mask, nvsf_stream_t stream);
+
+/* ref: lidar_to_pano_with_intensities, nvsf/lib/convert.py:105-181 (LiDAR_2_Pano, nvsf/preprocess/generate_rangeview.py:185-217): the
+ * range image of a cloud with a per-point payload.  points [P, 3] fp32, payload [P] fp32 or NULL, pano and payload_img [H, W] fp32
+ * (payload_img may be NULL; it needs a payload), workspace: H W uint64, 8-byte aligned.  The arithmetic of :128-176 as numpy 2 executes
+ * it on an fp32 cloud, every operation rounded to fp32 by itself; the Python-float constants are formed in double from `geom` and
+ * rounded to fp32 once:
+ *   dist = sqrt((x x + y y) + z z); dropped if dist >= max_depth;
+ *   beta = fov_hoz_up pi / 180 - atan2(y, x), alpha = atan2(z, sqrt(x x + y y)) + (fov - fov_up) / 180 pi;
+ *   c = rint(beta / ((fov_hoz pi / 180) / W)), r = rint(H - alpha / (fov / 180 pi / H))   (half to even, as Python's round);
+ *   dropped unless 0 <= r < H and 0 <= c < W.
+ * pano = the smallest dist of the pixel (0 where empty), payload_img = the payload of the point that set it; among bit-equal dists the
+ * LOWEST index wins (the reference's strict `>` in arrival order).  A 64-bit integer atomic minimum of (bits(dist) << 32) | index over a
+ * workspace filled with ones, then a resolve pass: independent of scheduling, two runs give the same bits.  atan2 is the device's (the
+ * reference's is its libm's): a point whose fractional row or column lies within their difference of .5 may land one pixel off.
+ * Deviations: a point at distance exactly 0 is skipped (the reference reads a stored 0 as "unset" and keeps an arrival-order-dependent
+ * payload), and so is a NaN one (the reference raises).  P = 0 gives zeros.  H W < 2^31.  One memset, two launches. */
+int nvsf_lidar_to_pano(const float* points, const float* payload, uint32_t P, uint32_t H, uint32_t W, const double* geom, void* workspace,
+                       size_t ws_bytes, float* pano, float* payload_img, nvsf_stream_t stream);
+
+/* ref: utils.compute_object_masks, nvsf/nerf/utils.py:750-807, after its host part, fused: per pixel of range_m [H, W] fp32 the point
+ * of section 11 step 1 (the same device function), nvsf_points_in_hulls' test, nvsf_lidar_to_pano's projection with the membership bit
+ * as payload (the key's low word is 2 pixel + bit: the cloud is in pixel order), then the resolve pass.  dyn_mask [H, W] fp32 = 1 where the
+ * nearest point that returns to the pixel lies in a box, else 0; the static mask is dyn_mask == 0 (utils.py:805: an empty pixel is
+ * static).  Equals nvsf_lidar_to_pano over the cloud with nvsf_points_in_hulls' mask as payload, bit for bit.  workspace as above.
+ * B = 0 gives zeros.  H W < 2^30.  One memset, two launches. */
+int nvsf_range_image_object_mask(const float* range_m, uint32_t H, uint32_t W, const double* geom, const double* planes,
+                                 const uint32_t* plane_counts, uint32_t B, uint32_t KMAX, void* workspace, size_t ws_bytes, float* dyn_mask,
+                                 nvsf_stream_t stream);
+
+/* ref: the pixel loops of utils.compute_object_masks_img, nvsf/nerf/utils.py:857-868.  boxes [B, 4] int32 = (x_min, y_min, x_max,
+ * y_max), inclusive, already clamped by the caller (device); dyn_mask [H, W] uint8 = 1 inside any box, every element written.  A box
+ * with x_max < x_min or y_max < y_min covers nothing.  One thread per pixel, boxes staged in LDS 1024 at a time.  B <= 2^20,
+ * H W < 2^31.  One launch. */
+int nvsf_box_mask_image(const int32_t* boxes, uint32_t B, uint32_t H, uint32_t W, uint8_t* dyn_mask, nvsf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

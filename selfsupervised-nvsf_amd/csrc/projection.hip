@@ -16,6 +16,7 @@
 // "empty" in the finished image, so the minimum is taken by a compare-and-swap that treats 0 as the identity: a memset and one
 // kernel, no pass that rewrites a sentinel afterwards.  At ~1 % occupied pixels the swap almost never repeats.
 #include "common.h"
+#include "pano_device.h"
 #include <math.h>
 
 namespace {
@@ -57,15 +58,12 @@ __global__ __launch_bounds__(kBlock) void k_lidar_depth_images(const float* __re
     const float r = range_m[n];
     if (r == 0.0f) return;  // np.where(pano != 0.0): a NaN range goes on and lands nowhere
     const uint32_t f = n / per_frame, pix = n - f * per_frame;
-    const float i = (float)(pix % Wl), j = (float)(pix / Wl);
-    const float kPi = 3.14159265358979323846f;
-    const float beta = (-(i - (float)Wl / 2.0f)) / (float)Wl * fov_hoz / 180.0f * kPi;
-    const float alpha = (fov_up - j / (float)Hl * fov) / 180.0f * kPi;
-    const float ca = cosf(alpha), sa = sinf(alpha), cb = cosf(beta), sb = sinf(beta);
     double m[12];
 #pragma unroll
     for (int e = 0; e < 12; ++e) m[e] = (double)lidar2cam[16 * (size_t)f + e];
-    splat((ca * cb) * r, (ca * sb) * r, sa * r, m, cam.k, H, W, out + (size_t)f * H * W);
+    float x, y, z;
+    pano_point(pix, Hl, Wl, fov_up, fov, fov_hoz, r, x, y, z);  // step 1 (pano_device.h)
+    splat(x, y, z, m, cam.k, H, W, out + (size_t)f * H * W);
 }
 
 __global__ __launch_bounds__(kBlock) void k_points_depth_image(const float* __restrict__ points, uint32_t P, Extrinsic ext, Pinhole cam, uint32_t H, uint32_t W,

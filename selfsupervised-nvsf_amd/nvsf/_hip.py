@@ -117,6 +117,11 @@ SIGNATURES = {
     # section 11: LiDAR-projected camera depth maps
     "nvsf_lidar_depth_images": [_P, _U, _U, _U, _F, _F, _F, _P, _P, _U, _U, _P],
     "nvsf_points_depth_image": [_P, _U, _P, _P, _U, _U, _P],
+    # section 12: object masks and the range-image z-buffer
+    "nvsf_points_in_hulls": [_P, _U, _P, _P, _U, _U, _P],
+    "nvsf_lidar_to_pano": [_P, _P, _U, _U, _U, _P, _P, ctypes.c_size_t, _P, _P],
+    "nvsf_range_image_object_mask": [_P, _U, _U, _P, _P, _P, _U, _U, _P, ctypes.c_size_t, _P],
+    "nvsf_box_mask_image": [_P, _U, _U, _U, _P],
 }
 
 _lib = None

@@ -108,10 +108,14 @@ class FrameSet:
 
     def __init__(self, root_path, sequence_id, split, scale, intrinsics_lidar=(2.0, 26.9), intrinsics_hoz_lidar=(180.0, 360.0),
                  num_rays=4096, num_rays_lidar=4096, patch_size=1, patch_size_lidar=1, device="cuda", training=True,
-                 images=None, range_images=None, camera_depth=False):
+                 images=None, range_images=None, camera_depth=False, annotations=None, offset=(0.0, 0.0, 0.0)):
         """images / range_images: optional pre-decoded lists (skips file reads, e.g. synthetic data).  camera_depth: build
         `image_depths` [F, H, W], the LiDAR-projected camera depth map of every frame in metres (base_dataset.py:153-157), in one
-        launch (nvsf/nerf/dataset/depth_image.py); `collate` / `train_batch` then carry it."""
+        launch (nvsf/nerf/dataset/depth_image.py); `collate` / `train_batch` then carry it.  annotations: the 3-D boxes of the moving
+        objects, per frame a list of {"class": str, "vertices": [8, 3] world frame, metres} -- a list with one entry per frame, or the
+        path of a JSON sidecar keyed by frame id (nvsf/nerf/object_masks.py::load_annotations; a frame it does not name has no box);
+        `collate` then adds "3d_annotation" (base_dataset.py:314).  offset: the reference's --offset, the recentring the poses went
+        through (world = pose / scale + offset), which the object masks need to bring the boxes into the sensor frames."""
         t = load_transforms(transforms_path(root_path, sequence_id, split))
         self.meta, self.device, self.training, self.scale = t, torch.device(device), training, scale
         self.H, self.W, self.H_lidar, self.W_lidar = t["H"], t["W"], t["H_lidar"], t["W_lidar"]
@@ -134,6 +138,17 @@ class FrameSet:
         self.error_map = self.error_map_rgb = None
         self.use_error_map = False  # set per epoch by RenderTrainStep.set_epoch (trainer.py:1056-1059)
         self._em_stats, self._em_owner = {}, {}
+        self.offset = tuple(float(v) for v in offset)
+        self.annotations = None
+        if annotations is not None:
+            if isinstance(annotations, (str, os.PathLike)):
+                from nvsf.nerf import object_masks
+                by_id = object_masks.load_annotations(annotations)
+                annotations = [by_id.get(int(i), []) for i in t["frame_ids"]]
+            if len(annotations) != len(t["frames"]):
+                raise ValueError(f"annotations: {len(annotations)} entries for {len(t['frames'])} frames")
+            self.annotations = [[{"class": str(a.get("class", "")), "vertices": np.asarray(a["vertices"], dtype=np.float64).reshape(8, 3)}
+                                 for a in frame] for frame in annotations]
         self.image_depths = None
         if camera_depth:
             from nvsf.nerf.dataset import depth_image
@@ -190,6 +205,8 @@ class FrameSet:
         if self.image_depths is not None:  # base_dataset.py:373-388: [B, N, 1] at the camera rays' pixels in training, else [B, H, W]
             depths = self.image_depths[idx]
             res["image_depths"] = gather_pixels(depths.unsqueeze(-1), rays["inds"]) if self.training else depths
+        if self.annotations is not None:  # base_dataset.py:314: the boxes of the (one) frame of the batch
+            res["3d_annotation"] = self.annotations[int(index[0])]
         res["pano_frame"] = self.images_lidar[idx]  # the whole ground-truth frame (base_dataset.py:403): the structural regulariser's masks
         return res
 

@@ -412,6 +412,52 @@ def update_table(meters, e, scale=1.0):
         meters[k].update(e["pred_rgb"], e["gt_rgb"])
 
 
+SPLITS = ("static", "dynamic")
+
+
+def split_table_meters(scale, intensity_inv_scale=1, raydrop_ratio=0.5, camera_depth=False):
+    """The meters of ONE of the reference's two further tables (metrics_static / depth_metrics_static, or the _dynamic pair,
+    main_nvsf.py:224-240) minus PointsMeter and LPIPSMeter: {"depth", "intensity", "raydrop", "psnr", "ssim"} and, when the frames carry
+    the camera depth map, "rgb_depth"."""
+    m = {"depth": DepthMeter_L4D(scale), "intensity": IntensityMeter_L4D(intensity_inv_scale), "raydrop": RaydropMeter(raydrop_ratio),
+         "psnr": PSNRMeter(), "ssim": SSIMMeter()}
+    if camera_depth:
+        m["rgb_depth"] = RMSEMeter(rgb_metric=True)
+    return m
+
+
+def frame_object_masks(e, data, frames, lidar_max_depth):
+    """The masks of one evaluated frame as trainer.py:1545-1551, 1586-1602 build them: {"static": (range-image mask of the prediction,
+    of the ground truth, camera-image mask), "dynamic": likewise}, each [1, H, W] fp32 on the device.  A frame without boxes gets
+    ones / zeros."""
+    from nvsf.nerf import object_masks as OM
+    pd, gd = e["pred_depth"], e["gt_depth"]
+    if len(data["3d_annotation"]) > 0:
+        args = (data, frames.scale, frames.offset, frames.intrinsics_lidar, frames.intrinsics_hoz_lidar, lidar_max_depth)
+        sp, dp = OM.compute_object_masks(pd[0].float().contiguous(), *args)
+        sg, dg = OM.compute_object_masks(gd[0].float().contiguous(), *args)
+        si, di = OM.compute_object_masks_img(data, frames.scale, frames.offset, device=pd.device)
+    else:
+        sp = sg = torch.ones_like(pd[0])
+        dp = dg = torch.zeros_like(pd[0])
+        si = torch.ones(e["pred_rgb"].shape[1:3], dtype=pd.dtype, device=pd.device)
+        di = torch.zeros_like(si)
+    cast = lambda *ms: tuple(m[None].to(pd.dtype) for m in ms)
+    return {"static": cast(sp, sg, si), "dynamic": cast(dp, dg, di)}
+
+
+def update_split_table(meters, e, scale, mask_pred, mask_gt, mask_img):
+    """Feeds one of the two further tables as trainer.py:1553-1569, 1604-1626 do: the prediction times its own mask, the ground truth
+    times the ground truth's; the camera image and its depth times the one image mask."""
+    if "rgb_depth" in meters:
+        meters["rgb_depth"].update(e["pred_rgb_depth"] / scale * mask_img, e["gt_rgb_depth"] * mask_img)
+    meters["depth"].update(e["pred_depth"] * mask_pred, e["gt_depth"] * mask_gt)
+    meters["intensity"].update(e["pred_intensity"] * mask_pred, e["gt_intensity"] * mask_gt)
+    meters["raydrop"].update(e["pred_raydrop"] * mask_pred, e["gt_raydrop"] * mask_gt)
+    for k in ("psnr", "ssim"):
+        meters[k].update(e["pred_rgb"] * mask_img[..., None], e["gt_rgb"] * mask_img[..., None])
+
+
 def report_lines(meters):
     """The reference's report lines, LiDAR meters first (trainer.py:1794-1827)."""
     return [meters[k].report() for k in ("depth", "intensity", "raydrop", "psnr", "rmse", "ssim", "rgb_depth") if k in meters]
@@ -424,4 +470,16 @@ def table_report(res):
             f"Intensity_error (RMSE, MedAE, LPIPS, SSIM, PNSR) = {np.array(res['intensity'])}",
             f"Rdrop_error (RMSE, Accuracy, F_score) = {np.array(res['raydrop'])}",
             f"RMSE_intensity = {res['rgb_rmse']:.3f}", f"PSNR = {res['psnr']:.3f}", f"SSIM = {res['rgb_ssim']:.3f}"] + \
-        ([f"RMSE = {res['rgb_depth_rmse']:.3f}"] if "rgb_depth_rmse" in res else [])
+        ([f"RMSE = {res['rgb_depth_rmse']:.3f}"] if "rgb_depth_rmse" in res else []) + \
+        [line for s in SPLITS if f"depth_{s}" in res for line in _split_report(res, s)]
+
+
+def _split_report(res, s):
+    """The lines of the static / dynamic table (trainer.py:1800-1840 print the same meters under "Background" / "Foreground")."""
+    g = lambda k: res[f"{k}_{s}"]
+    return [f"[{s}] Points_error(CD, F-score) = {[round(float(g('chamfer_distance')), 3), round(float(g('f_score')), 3)]}",
+            f"[{s}] Depth_error (RMSE, MedAE, LPIPS, SSIM, PNSR) = {np.array(g('depth'))}",
+            f"[{s}] Intensity_error (RMSE, MedAE, LPIPS, SSIM, PNSR) = {np.array(g('intensity'))}",
+            f"[{s}] Rdrop_error (RMSE, Accuracy, F_score) = {np.array(g('raydrop'))}",
+            f"[{s}] PSNR = {g('rgb_psnr'):.3f}", f"[{s}] SSIM = {g('rgb_ssim'):.3f}"] + \
+        ([f"[{s}] RMSE = {g('rgb_depth_rmse'):.3f}"] if f"rgb_depth_rmse_{s}" in res else [])

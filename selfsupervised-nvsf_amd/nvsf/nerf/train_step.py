@@ -904,7 +904,14 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
     (RaydropMeter at `raydrop_thres`), "rgb_ssim" (SSIMMeter) and "rgb_rmse" (RMSE of the rendered against the measured image);
     frame means, the per-frame values riding in the same all-reduce under shard="frames".  Over a FrameSet opened with camera_depth=True
     the table also has "rgb_depth_rmse": RMSEMeter(rgb_metric=True) on pred_rgb_depth / scale against the LiDAR-projected depth map, as
-    trainer.py:761-762, 1540-1541 feed it.  The default (None) returns exactly the six keys above from the same code path as before."""
+    trainer.py:761-762, 1540-1541 feed it.  Over a FrameSet opened with `annotations` the table is also reported over the static
+    background and over the annotated moving objects, as trainer.py:1545-1626 feeds metrics_static / metrics_dynamic and
+    depth_metrics_static / depth_metrics_dynamic: per frame the masks of nvsf/nerf/object_masks.py (the prediction's range image gives
+    the prediction's mask, the ground truth's its own; the camera image one mask from the projected boxes; a frame without boxes: ones /
+    zeros), products by plain torch ops, the same meter kernels; keys "depth", "intensity", "raydrop", "chamfer_distance", "f_score",
+    "rgb_psnr", "rgb_ssim" (and "rgb_depth_rmse") with the suffixes "_static" and "_dynamic", riding in the same all-reduce.  The range
+    limit of the masks' z-buffer is the model's `lidar_max_depth`.  The default (None) returns exactly the six keys above from the same
+    code path as before."""
     from nvsf import frame_shard
     if shard not in ("rays", "frames"):
         raise ValueError("shard: 'rays' or 'frames'")
@@ -919,22 +926,32 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
     try:
         points = PointsMeter(frames.scale, frames.intrinsics_lidar, frames.intrinsics_hoz_lidar)
         ps, rm, ls = [], [], []
-        table = None
+        table = split = None
         if meters == "table":
             from nvsf.nerf import meters as M
             table = M.table_meters(frames.scale, intensity_inv_scale, eval_kwargs.get("raydrop_thres", 0.5))
             if getattr(frames, "image_depths", None) is not None:  # FrameSet(camera_depth=True): the reference's camera depth RMSE
                 table["rgb_depth"] = M.RMSEMeter(rgb_metric=True)
+            if getattr(frames, "annotations", None) is not None:  # FrameSet(annotations=...): the static / dynamic tables
+                split = {s: M.split_table_meters(frames.scale, intensity_inv_scale, eval_kwargs.get("raydrop_thres", 0.5), "rgb_depth" in table)
+                         for s in M.SPLITS}
+                split_points = {s: PointsMeter(frames.scale, frames.intrinsics_lidar, frames.intrinsics_hoz_lidar) for s in M.SPLITS}
         todo = list(range(len(frames)) if indices is None else indices)
         if shard == "frames" and ws > 1:
             todo = todo[rank::ws]
         for i in todo:
-            e = eval_step(model, frames.collate([int(i)]), num_steps, split_rays=(shard == "rays"), **eval_kwargs)
+            data = frames.collate([int(i)])
+            e = eval_step(model, data, num_steps, split_rays=(shard == "rays"), **eval_kwargs)
             ps.append(psnr(e["pred_rgb"], e["gt_rgb"]))
             rm.append(depth_rmse(e["pred_depth"], e["gt_depth"], frames.scale))
             points.update(e["pred_depth"], e["gt_depth"])
             if table is not None:
                 M.update_table(table, e, frames.scale)  # launches only; read once, after the last frame
+            if split is not None:
+                masks = M.frame_object_masks(e, data, frames, model.lidar_max_depth)
+                for s in M.SPLITS:
+                    M.update_split_table(split[s], e, frames.scale, *masks[s])
+                    split_points[s].update(e["pred_depth"] * masks[s][0], e["gt_depth"] * masks[s][1])
             ls.append(float(e["loss"]))
     finally:
         if ema is not None:
@@ -948,6 +965,13 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
                 table["rmse"].frame_values().reshape(-1, 1)]
         if "rgb_depth" in table:
             cols.append(table["rgb_depth"].frame_values().reshape(-1, 1))
+        for s in (M.SPLITS if split is not None else ()):  # behind the unsplit table: static, then dynamic
+            t = split[s]
+            cols += [t["depth"].frame_values().reshape(-1, 5), t["intensity"].frame_values().reshape(-1, 5),
+                     t["raydrop"].frame_values().reshape(-1, 3), np.array(split_points[s].V, dtype=np.float64).reshape(-1, 2),
+                     t["psnr"].frame_values().reshape(-1, 1), t["ssim"].frame_values().reshape(-1, 1)]
+            if "rgb_depth" in t:
+                cols.append(t["rgb_depth"].frame_values().reshape(-1, 1))
         sums += [float(v) for v in np.concatenate(cols, axis=1).sum(0)]
     if shard == "frames":
         sums = frame_shard.allreduce_sums(sums, device=next(model.parameters()).device)
@@ -957,6 +981,15 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
     if table is not None:
         t = [v / n for v in sums[6:]]
         res.update(depth=t[0:5], intensity=t[5:10], raydrop=t[10:13], rgb_ssim=t[13], rgb_rmse=t[14])
-        if len(t) > 15:
+        k = 15
+        if "rgb_depth" in table:
             res["rgb_depth_rmse"] = t[15]
+            k = 16
+        for s in (M.SPLITS if split is not None else ()):
+            res.update({f"depth_{s}": t[k:k + 5], f"intensity_{s}": t[k + 5:k + 10], f"raydrop_{s}": t[k + 10:k + 13],
+                        f"chamfer_distance_{s}": t[k + 13], f"f_score_{s}": t[k + 14], f"rgb_psnr_{s}": t[k + 15], f"rgb_ssim_{s}": t[k + 16]})
+            k += 17
+            if "rgb_depth" in table:
+                res[f"rgb_depth_rmse_{s}"] = t[k]
+                k += 1
     return res

@@ -2,7 +2,7 @@
 
     python tools/train_example.py --root /path/to/kitti360_nvsf --sequence 1908 [--dynamic] [--epochs 6] [--plain]
                                   [--export-mesh out.ply --mesh-res 256 256 256 --mesh-threshold 10] [--dynamic --flow-loss]
-                                  [--eval-table] [--rgbd-loss]
+                                  [--eval-table] [--rgbd-loss] [--annotations boxes.json [--offset X Y Z]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 tools/train_example.py ...
 
 Data: the reference's on-disk formats (transforms_{seq}_{split}.json + range-image .npy + images; nvsf/nerf/dataset/formats.py).
@@ -20,6 +20,9 @@ LPIPS / SSIM / PSNR, ray-drop RMSE / accuracy / F1, camera PSNR / RMSE / SSIM, c
 --rgbd-loss (the reference's --use_rgbd_loss, main_nvsf.py:84) projects every frame's range image into its camera once, on the device
 (nvsf/nerf/dataset/depth_image.py), and supervises the camera render's depth with that map; with --eval-table the table gets the camera
 depth RMSE line the reference prints as "RMSE = ".
+--annotations PATH (with --eval-table): a JSON sidecar of the moving objects' 3-D boxes, {"<frame_id>": [{"class": str, "vertices":
+[[x, y, z] x 8]}, ...]} in the world frame in metres (--offset: the recentring of the poses, the reference's --offset); the table is then
+also printed over the static background and over the boxes (trainer.py:1545-1626; masks on the device, nvsf/nerf/object_masks.py).
 """
 import argparse
 import os
@@ -83,7 +86,12 @@ def main():
                     "(device-side meters, nvsf/nerf/meters.py)")
     ap.add_argument("--rgbd-loss", action="store_true", help="camera depth supervision from the LiDAR-projected depth map (FrameSet(camera_depth=True), "
                     "RenderTrainStep(use_rgbd_loss=True)); adds the camera depth RMSE to --eval-table")
+    ap.add_argument("--annotations", default=None, metavar="PATH", help="JSON sidecar of the moving objects' 3-D boxes per frame id (world frame, "
+                    "metres); --eval-table then also prints the static / dynamic tables (nvsf/nerf/object_masks.py)")
+    ap.add_argument("--offset", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"), help="world = pose / scale + offset")
     args = ap.parse_args()
+    if args.annotations and not args.eval_table:
+        ap.error("--annotations splits the evaluation table: add --eval-table")
     if args.flow_loss and not args.dynamic:
         ap.error("--flow-loss supervises the flow head of the space-time model: add --dynamic")
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -152,7 +160,8 @@ def main():
             print(line, flush=True)
     # whole-frame evaluation (Trainer.eval_step / evaluate_one_epoch): every frame rendered with the staged loop, its rays split over the ranks
     from nvsf.nerf.train_step import evaluate_frames
-    whole = FrameSet(root, args.sequence, "train", scale, device=dev, training=False, camera_depth=args.rgbd_loss)
+    whole = FrameSet(root, args.sequence, "train", scale, device=dev, training=False, camera_depth=args.rgbd_loss,
+                     annotations=args.annotations, offset=args.offset)
     res = evaluate_frames(model, whole, args.num_steps, indices=range(min(len(whole), 4)), ema=trainer.ema,
                           meters="table" if args.eval_table else None)
     if rank == 0:
