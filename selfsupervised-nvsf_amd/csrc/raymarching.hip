@@ -873,8 +873,15 @@ __global__ __launch_bounds__(kBlock) void k_composite_train_bwd(const float* __r
         const float b = b_carry + wave_scan_add(w * cb);
         if (live) {
             grad_rgbs[3 * p] = gr * w; grad_rgbs[3 * p + 1] = gg * w; grad_rgbs[3 * p + 2] = gb * w;
-            grad_sigmas[p] = d0 * (gr * (T_after * cr - (rF - r)) + gg * (T_after * cg - (gF - g)) +
-                                   gb * (T_after * cb - (bF - b)) + gws * (1.0f - wsF));
+            // Behind the ray's last live sample, or behind one that leaves a transmittance of exactly zero, every weight is exactly
+            // zero: the colour that remains is 0 and 1 - weights_sum is T_after.  Taken from the forward's totals instead they are
+            // the rounding residue of two summation orders (the forward's lane sums against this scan; the reference's sequential
+            // loops give r_final == r there), a few ulps of the total -- which trunc_exp's backward multiplies by up to e^15 on
+            // exactly these samples, the saturating ones
+            const bool nothing_behind = lane == first_stop || i + 1 == count || T_after == 0.0f;
+            const float rem_r = nothing_behind ? 0.0f : rF - r, rem_g = nothing_behind ? 0.0f : gF - g, rem_b = nothing_behind ? 0.0f : bF - b;
+            const float T_final = nothing_behind ? T_after : 1.0f - wsF;
+            grad_sigmas[p] = d0 * (gr * (T_after * cr - rem_r) + gg * (T_after * cg - rem_g) + gb * (T_after * cb - rem_b) + gws * T_final);
         }
         if (stop) break;
         T_carry = __shfl(T_after, 63, 64);

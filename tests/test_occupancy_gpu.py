@@ -164,6 +164,108 @@ def test_fused_occupancy_step_cap_and_empty(dev, setup):
     assert torch.equal(empty["image"], torch.ones_like(empty["image"]))
 
 
+def test_train_step_on_an_occupancy_model(dev):
+    """RenderTrainStep on a model with enable_occupancy_grid(): a LiDAR + camera batch through run_cuda's training branch, three
+    steps with force_all_rays left at its default.  The first step has no mean_count yet and reads the marcher's counter back; after
+    the next update_extra_state the budgeted path runs (mean_count > 0: no host read, rays past the budget recorded but empty, the
+    marcher's failure flag looked at by step()).  One counter row per RENDER: a step with both modalities writes two (camera first)."""
+    from nvsf import synthetic as S
+    from nvsf.nerf.loss_scaler import LossScaler
+    from nvsf.nerf.models.network_static import NeRFNetworkStatic
+    from nvsf.nerf.raymarching import raymarching
+    from nvsf.nerf.train_step import RenderTrainStep
+    from test_train_step_gpu import _batch
+    kw = dict(bound=S.BOUND, min_near=S.MIN_NEAR, min_near_lidar=S.MIN_NEAR, lidar_max_depth=S.LIDAR_MAX_DEPTH, log2_hashmap_size=14)
+    torch.manual_seed(3)
+    teacher = NeRFNetworkStatic(**kw)
+    with torch.no_grad():
+        for enc in (teacher.hash_encoder_lidar, teacher.hash_encoder_camera):
+            enc.params.normal_(0.0, 0.2)
+    teacher = teacher.to(dev).eval()
+    n = 256
+    batch = _batch(S, teacher, dev, n=n, T=32, seed=4)
+    torch.manual_seed(4)
+    m = NeRFNetworkStatic(**kw)
+    with torch.no_grad():
+        for enc in (m.hash_encoder_lidar, m.hash_encoder_camera):
+            enc.params.normal_(0.0, 0.1)
+    m = m.to(dev).enable_occupancy_grid().to(dev)
+    step = RenderTrainStep(m, num_steps=32, scale=S.SCALE, ema_decay=None)
+    step.scaler = LossScaler(init_scale=64.0, growth_interval=10 ** 6)  # no overflow at this scale: no step is skipped
+    t = batch["time"]
+    m.update_extra_state(t, cal_lidar_color=True)
+    assert m.mean_count == 0 and m.local_step == 0 and int(m.density_bitfield.count_nonzero()) > 0
+
+    calls, real = [], raymarching.march_rays_train
+
+    def spy(*args):
+        out = real(*args)
+        calls.append(dict(mean_count=args[9], force_all_rays=args[12], rows=out[0].shape[0], rays=out[3].detach().clone()))
+        return out
+
+    def one_step():
+        before = {k: p.detach().clone() for k, p in m.named_parameters()}
+        del calls[:]
+        raymarching.march_rays_train = spy
+        try:
+            loss, parts, _ = step.step(batch)
+        finally:
+            raymarching.march_rays_train = real
+        step.sync()
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(loss)) and all(bool(torch.isfinite(v)) for v in parts.values()), (loss, parts)
+        assert set(parts) == {"depth", "raydrop", "intensity", "chamfer", "rgb"}
+        assert float(step.scaler.get_scale()) == 64.0  # not skipped
+        moved = {k: not torch.equal(p.detach(), before[k]) for k, p in m.named_parameters() if p.grad is not None and p.numel() > 0}
+        assert len(moved) == 6 and all(moved.values()), moved  # two tables, the density MLP, three heads
+        assert len(calls) == 2  # the camera render, then the LiDAR render
+        return list(calls)
+
+    first = one_step()
+    assert all(c["mean_count"] == 0 and not c["force_all_rays"] for c in first)
+    rows = m.step_counter.cpu()
+    for k, c in enumerate(first):
+        total = int(c["rays"][:, 2].sum())
+        assert rows[k].tolist() == [total, n] and total > 0
+        assert c["rows"] == total + (128 - total % 128)  # the counter was read back: sliced to the aligned live count
+    assert m.local_step == 2
+    want = int(int(rows[:2, 0].sum()) / 2)
+    m.update_extra_state(t, cal_lidar_color=True)
+    assert m.mean_count == want > 0 and m.local_step == 0
+
+    dropped = []
+    for k in range(2):
+        later = one_step()
+        rows = m.step_counter.cpu()
+        for j, c in enumerate(later):
+            assert c["mean_count"] == want and not c["force_all_rays"]
+            assert c["rows"] == want + (128 - want % 128)  # the budget, whatever the batch needs
+            assert rows[2 * k + j].tolist() == [int(c["rays"][:, 2].sum()), n]  # rays past the budget are counted too
+            dropped.append(int(((c["rays"][:, 1] + c["rays"][:, 2]) > c["rows"]).sum()))
+        assert not raymarching.march_status_pending()  # step() looked at the failure flag of both launches
+    assert m.local_step == 4
+    print(f"budget {want} rows; rays past it per render (camera, LiDAR, camera, LiDAR): {dropped}")
+    want = int(int(m.step_counter[:4, 0].sum()) / 4)
+    m.update_extra_state(t, cal_lidar_color=True)
+    assert m.mean_count == want
+
+    # a budget that suffices: the budgeted render is the force_all_rays render of the same rays, bit for bit
+    m.train()
+    for lidar in (True, False):
+        sfx = "_lidar" if lidar else ""
+        o, d = (batch["rays_o_lidar"], batch["rays_d_lidar"]) if lidar else (batch["rays_o"], batch["rays_d"])
+        with torch.no_grad():
+            a = m.render(o, d, t, cal_lidar_color=lidar, force_all_rays=True, perturb=False, bg_color=1)
+            total = int(m.step_counter[(m.local_step - 1) % 16, 0])
+            m.mean_count = total + 1000
+            b = m.render(o, d, t, cal_lidar_color=lidar, perturb=False, bg_color=1)
+        raymarching.check_march_status(wait=True)
+        assert int(m.step_counter[(m.local_step - 1) % 16, 0]) == total > 0
+        for key in ("weights_sum" + sfx, "depth" + sfx, "image" + sfx):
+            assert torch.equal(a[key], b[key]), key
+        assert float(a["weights_sum" + sfx].max()) > 0.05
+
+
 def test_density_grid_maintenance(dev, setup):
     m, bits, S = setup
     import copy

@@ -387,6 +387,122 @@ def test_composite_rays_train_backward(rm, dev, scene):
     np.testing.assert_allclose(tc.grad.cpu().numpy(), gc_r, atol=1e-5, rtol=1e-4)
 
 
+# ---- the packed compositor against fp64 autograd of the truncated sums (torch_f64_static.composite_packed) -------------------------
+# The oracle comparisons above share the reference's own fp32 formulation with the kernel (an error common to both cannot show), run
+# on one marched scene whose rays have at most 120 samples, and the backward at one T_thresh.  Here: hand-built rays whose sample
+# counts sit on and around the wave kernel's 64-sample rounds, an independent reference, and a bar in units of the fp32 arithmetic.
+_HB_COUNTS = [0, 1, 2, 63, 64, 65, 127, 128, 129, 192, 200]
+_HB_EXACT_STOPS = [63, 64, 127, 128]  # four more 200-sample rays, scaled so that T falls below 1e-4 exactly at these samples
+_HB_SEED = 9  # chosen on the CPU: every kind of ray asserted below occurs, and no ray comes within 1e-3 of a threshold
+_hb_cache = {}
+
+
+def _handbuilt_packed(seed=_HB_SEED):
+    """-> sigmas [M], rgbs [M, 3], deltas [M, 2] fp32, rays [N, 3] int32.  Rows: the four engineered rays, then _HB_COUNTS four times;
+    per-ray sigma scale log-uniform in 0.3 .. 200 times U(0, 1) per sample with 30 % exact zeros; ray ids a random permutation; the
+    LAST ray (200 samples) does not fit: M ends 100 all-zero rows after the last ray that does."""
+    rng = np.random.default_rng(seed)
+    counts = [200] * len(_HB_EXACT_STOPS) + _HB_COUNTS * 4
+    N = len(counts)
+    offsets = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    M = int(offsets[-1]) + 100
+    assert offsets[-1] + counts[-1] > M
+    sig, rgb = np.zeros(M, np.float32), rng.random((M, 3)).astype(np.float32)
+    dl = rng.uniform(0.005, 0.03, size=(M, 2)).astype(np.float32)
+    assert (dl[:, 0] != dl[:, 1]).all()
+    for n, (off, cnt) in enumerate(zip(offsets[:-1], counts[:-1])):
+        s = rng.random(cnt) * np.exp(rng.uniform(np.log(0.3), np.log(200.0)))
+        s[rng.random(cnt) < 0.3] = 0.0
+        if n < len(_HB_EXACT_STOPS):
+            k = _HB_EXACT_STOPS[n]
+            s[k] = max(s[k], 0.5 * s.max())
+            depth = np.cumsum(s * dl[off:off + cnt, 0].astype(np.float64))
+            s *= -np.log(1e-4) / (depth[k] - 0.5 * s[k] * dl[off + k, 0])  # optical depth ln(1e4) is crossed in the middle of sample k
+        sig[off:off + cnt] = s.astype(np.float32)
+    rays = np.stack([rng.permutation(N), offsets, counts], -1).astype(np.int32)
+    return sig, rgb, dl, rays
+
+
+def _handbuilt_reference(T_thresh):
+    """Everything of the comparison that needs no device, computed once per T_thresh: inputs, output gradients, the fp64 forward
+    and autograd gradients, the live rows, the error units, and the C oracle's own distance from fp64 in those units."""
+    if T_thresh in _hb_cache:
+        return _hb_cache[T_thresh]
+    import torch_f64_static as R
+    sig, rgb, dl, rays = _handbuilt_packed()
+    M, N = sig.shape[0], rays.shape[0]
+    rng = np.random.default_rng(_HB_SEED + 1)
+    g_ws, g_img = rng.standard_normal(N).astype(np.float32), rng.standard_normal((N, 3)).astype(np.float32)
+    s64, c64 = torch.from_numpy(sig).double().requires_grad_(), torch.from_numpy(rgb).double().requires_grad_()
+    ws, dp, img, stop, margin = R.composite_packed(s64, c64, torch.from_numpy(dl), torch.from_numpy(rays), T_thresh)
+    ((ws * torch.from_numpy(g_ws).double()).sum() + (img * torch.from_numpy(g_img).double()).sum()).backward()
+    gs64, gc64 = s64.grad.numpy(), c64.grad.numpy()
+    # live rows and the per-row units: 2^-24 of the magnitudes the closed-form backward adds up for that row
+    live = np.zeros(M, bool)
+    unit_s, unit_c = np.ones(M), np.ones((M, 3))
+    img64 = img.detach().numpy()
+    for (ray_id, off, cnt), k in zip(rays.tolist(), stop.tolist()):
+        if k >= 0:
+            live[off:off + k + 1] = True
+            unit_s[off:off + k + 1] = dl[off:off + k + 1, 0].astype(np.float64) * 2.0 ** -24 * (
+                (np.abs(g_img[ray_id]) * (img64[ray_id] + 1.0)).sum() + abs(g_ws[ray_id]))
+            unit_c[off:off + k + 1] = 2.0 ** -24 * np.abs(g_img[ray_id])[None, :]
+    assert not gs64[~live].any() and not gc64[~live].any()
+    wo, do, io = O.composite_rays_train_forward(sig, rgb, dl, rays, T_thresh)
+    gso, gco = O.composite_rays_train_backward(g_ws, g_img, sig, rgb, dl, rays, wo, io, T_thresh)
+    assert not gso[~live].any() and not gco[~live].any()  # the oracle stops where fp64 stops (the margins below say why)
+    mult_s = float((np.abs(gso - gs64) / unit_s)[live].max())
+    mult_c = float((np.abs(gco - gc64) / unit_c)[live].max())
+    ref = dict(sig=sig, rgb=rgb, dl=dl, rays=rays, g_ws=g_ws, g_img=g_img, ws=ws.detach().numpy(), dp=dp.detach().numpy(), img=img64,
+               stop=stop.numpy(), margin=margin.numpy(), gs64=gs64, gc64=gc64, live=live, unit_s=unit_s, unit_c=unit_c,
+               mult_s=mult_s, mult_c=mult_c)
+    _hb_cache[T_thresh] = ref
+    return ref
+
+
+@pytest.mark.parametrize("T_thresh", [1e-4, 0.0, 0.5])
+def test_composite_rays_train_against_fp64(rm, dev, T_thresh):
+    """composite_rays_train, forward and backward, against fp64 torch autograd of the early-terminated sums on hand-built rays.
+
+    Forward: 1e-5 (this file's bar for the compositors).  Gradients: in units of the fp32 arithmetic of the closed form,
+        unit_sigma[i] = deltas[i, 0] 2^-24 (sum_c |g_c| (image_c + 1) + |g_ws|),    unit_rgb[i, c] = 2^-24 |g_c|,
+    the kernel may be off by 4x what the C oracle -- the reference's sequential fp32 loop, run here on the same inputs -- is off
+    from fp64 in the same units: the wave scan associates the products and running sums differently, and the device's expf may
+    differ from glibc's by an ulp on alpha.  Rows no live sample owns (after a ray's stop, the ray that does not fit, the padding)
+    stay exactly zero.  Measured on an MI355X, in units (T_thresh 1e-4 / 0 / 0.5): the oracle 2.11 / 2.14 / 2.11 on sigma and 1.63 on
+    rgb, the kernel 3.32 on sigma and 1.63 on rgb at all three (allowed: 8.4 - 8.6 and 6.5)."""
+    r = _handbuilt_reference(T_thresh)
+    rays, stop, cnt = r["rays"], r["stop"], r["rays"][:, 2]
+    M = r["sig"].shape[0]
+    fits = (rays[:, 1] + cnt <= M) & (cnt > 0)
+    assert int((~fits & (cnt > 0)).sum()) == 1 and M > int((rays[fits, 1] + cnt[fits]).max())  # one ray does not fit; padding behind the last
+    assert not np.array_equal(rays[:, 0], np.arange(len(rays)))
+    closest = float(r["margin"].min())
+    assert closest > 1e-3, f"a ray comes within {closest:.3g} of T_thresh: fp32 and fp64 could stop one sample apart"
+    early = fits & (stop < cnt - 1)
+    if T_thresh == 1e-4:
+        kinds = {"never stops, three rounds": int((fits & ~early & (cnt > 128)).sum())}
+        kinds.update({f"stops in round {k}": int((early & (stop // 64 == k)).sum()) for k in range(3)})
+        kinds.update({f"stops at sample {k}": int((early & (stop == k)).sum()) for k in _HB_EXACT_STOPS})
+        kinds.update({f"last live sample {k}": int((fits & (stop == k)).sum()) for k in (0, 1, 62)})
+        assert all(v > 0 for v in kinds.values()), kinds
+    ts, tc = _t(r["sig"], dev).requires_grad_(), _t(r["rgb"], dev).requires_grad_()
+    wg, dg, ig = rm.composite_rays_train(ts, tc, _t(r["dl"], dev), _t(rays, dev), T_thresh)
+    for name, got, want in (("weights_sum", wg, r["ws"]), ("depth", dg, r["dp"]), ("image", ig, r["img"])):
+        err = float(np.abs(got.detach().cpu().numpy().astype(np.float64) - want).max())
+        assert err <= 1e-5, f"{name}: {err:.3g} from fp64"
+    (wg * _t(r["g_ws"], dev)).sum().add((ig * _t(r["g_img"], dev)).sum()).add((dg * 3.0).sum()).backward()  # the depth gradient must be dropped
+    gs, gc = ts.grad.cpu().numpy(), tc.grad.cpu().numpy()
+    live = r["live"]
+    assert not gs[~live].any() and not gc[~live].any()
+    k_s = float((np.abs(gs - r["gs64"]) / r["unit_s"])[live].max())
+    k_c = float((np.abs(gc - r["gc64"]) / r["unit_c"])[live].max())
+    print(f"T_thresh {T_thresh}: {int(early.sum())} of {int(fits.sum())} rays stop early; error in fp32 units, oracle sigma {r['mult_s']:.2f} rgb {r['mult_c']:.2f}, "
+          f"kernel sigma {k_s:.2f} rgb {k_c:.2f}")
+    assert k_s <= 4.0 * r["mult_s"], f"grad_sigmas: {k_s:.3g} units, the oracle {r['mult_s']:.3g}"
+    assert k_c <= 4.0 * r["mult_c"], f"grad_rgbs: {k_c:.3g} units, the oracle {r['mult_c']:.3g}"
+
+
 @pytest.mark.parametrize("n_step", [4, 8, 3, 1])  # 8: the record-store march kernel; <= 8: eight lanes per ray in composite_rays
 def test_inference_march_and_composite_loop(rm, dev, scene, n_step):
     """The n_alive loop of the reference's docstrings (raymarching.py:389-409, 480-493), against the oracle."""

@@ -14,6 +14,11 @@ model; the rules that make the two comparable:
   * the table gradient is autograd's gradient of the float64 gather (an fp64 sum);
   * the only values taken from the kernels are the sample depths `z_vals` and the `weights > w_thresh` mask, both inputs of the
     forward, never anything their backward produced.
+
+`render_packed` restates the third training path the same way: the occupancy-grid render (NeRFRenderer.run_cuda in training mode:
+march_rays_train -> density / color on the packed samples -> composite_rays_train).  It takes the marcher's outputs (positions,
+directions, the two step columns and the (id, offset, count) rows; the marcher is pinned bit for bit to the oracle) and nothing else;
+`composite_packed` is its per-ray part, the early-terminated sums of the packed compositor, also compared with the kernel alone.
 """
 import math
 
@@ -161,6 +166,16 @@ def leaves(model, lidar):
     return {n: getattr(model, n).params.detach().double().requires_grad_() for n in names}
 
 
+def head_logits(model, p64, enc_rows, geo, lidar):
+    """Logits of the per-sample heads on the rows [direction encoding | geo] (both already fp16-rounded): [M, 2] = [raydrop,
+    intensity] for LiDAR samples, [M, 3] colour logits otherwise."""
+    rows = torch.cat([enc_rows, geo], -1)
+    if lidar:
+        hs = model.raydrop_net.spec
+        return torch.cat([mlp(rows, p64["raydrop_net"], hs)[:, :1], mlp(rows, p64["intensity_net"], hs)[:, :1]], -1)
+    return mlp(rows, p64["color_net"], model.color_net.spec)[:, :3]
+
+
 def render(model, p64, rays_o, rays_d, nears, fars, z_vals, mask, lidar, bg=None):
     """The training render of `model` (a NeRFNetworkStatic) in fp64 with the parameters `p64` (leaves()).  rays [N, 3], nears / fars
     [N], z_vals [N, T] (fp32, the kernel's samples), mask [N, T] bool (the kernel's weights > w_thresh), bg: camera background
@@ -188,14 +203,74 @@ def render(model, p64, rays_o, rays_d, nears, fars, z_vals, mask, lidar, bg=None
     m = mask.reshape(-1)
     rgbs = torch.zeros(N * T, C, dtype=torch.float64, device=z64.device)
     if bool(m.any()):
-        rows = torch.cat([enc_ray.repeat_interleave(T, 0)[m], geo[m]], -1)
-        if lidar:
-            hs = model.raydrop_net.spec
-            logits = torch.cat([mlp(rows, p64["raydrop_net"], hs)[:, :1], mlp(rows, p64["intensity_net"], hs)[:, :1]], -1)
-        else:
-            logits = mlp(rows, p64["color_net"], model.color_net.spec)[:, :3]
+        logits = head_logits(model, p64, enc_ray.repeat_interleave(T, 0)[m], geo[m], lidar)
         rgbs = rgbs.index_put((m.nonzero().squeeze(1),), torch.sigmoid(logits))
     image = (weights[:, :, None] * rgbs.view(N, T, C)).sum(1)
     if not lidar:
         image = image + (1.0 - ws)[:, None] * torch.tensor([float(v) for v in bg], dtype=torch.float64, device=z64.device)
     return {"weights": weights, "weights_sum": ws, "depth": depth, "image": image, "x01": x01, "logits": h[:, 0]}
+
+
+def composite_packed(sigmas, rgbs, deltas, rays, T_thresh):
+    """composite_rays_train in fp64, differentiable in sigmas [M] and rgbs [M, 3] (fp64).  deltas [M, 2]: column 0 is the step that
+    enters alpha, column 1 the step that advances t; rays [N, 3] int = (ray id, first row, row count).  A ray is empty when its count
+    is 0 or its rows do not fit (first + count > M).  alpha_i = 1 - exp(-sigma_i deltas[i, 0]), T the exclusive product of
+    1 - alpha (no 1e-15 term in this compositor), `stop` the first i whose OUTGOING transmittance T_{i+1} is below T_thresh (that
+    sample included), else count - 1; the sums run over i <= stop.  -> weights_sum [N], depth [N], image [N, 3], indexed by ray id,
+    and per ROW of `rays`: stop (int64, -1 for an empty ray) and margin = min_i |T_{i+1} / T_thresh - 1| over i <= stop (how close
+    the ray comes to stopping one sample earlier or later; inf for an empty ray or T_thresh == 0)."""
+    M, N, dev = sigmas.shape[0], rays.shape[0], sigmas.device
+    d64 = deltas.double()
+    ids, ws, dp, im, stops, margins = [], [], [], [], [], []
+    for ray_id, off, cnt in rays.tolist():
+        if cnt == 0 or off + cnt > M:
+            stops.append(-1)
+            margins.append(math.inf)
+            continue
+        alpha = 1.0 - torch.exp(-sigmas[off:off + cnt] * d64[off:off + cnt, 0])
+        T_out = torch.cumprod(1.0 - alpha, 0)
+        below = (T_out.detach() < T_thresh).nonzero()
+        stop = int(below[0]) if below.numel() else cnt - 1
+        k = stop + 1
+        T_in = torch.cat([torch.ones(1, dtype=torch.float64, device=dev), T_out[:stop]])
+        w = alpha[:k] * T_in
+        ids.append(ray_id)
+        ws.append(w.sum())
+        dp.append((w * torch.cumsum(d64[off:off + k, 1], 0)).sum())
+        im.append((w[:, None] * rgbs[off:off + k]).sum(0))
+        stops.append(stop)
+        margins.append(float((T_out.detach()[:k] / T_thresh - 1.0).abs().min()) if T_thresh > 0 else math.inf)
+    out_ws = torch.zeros(N, dtype=torch.float64, device=dev)
+    out_dp = torch.zeros(N, dtype=torch.float64, device=dev)
+    out_im = torch.zeros(N, 3, dtype=torch.float64, device=dev)
+    if ids:
+        at = (torch.tensor(ids, dtype=torch.int64, device=dev),)
+        out_ws, out_dp, out_im = out_ws.index_put(at, torch.stack(ws)), out_dp.index_put(at, torch.stack(dp)), out_im.index_put(at, torch.stack(im))
+    return out_ws, out_dp, out_im, torch.tensor(stops, dtype=torch.int64, device=dev), torch.tensor(margins, dtype=torch.float64, device=dev)
+
+
+def render_packed(model, p64, xyzs, dirs, deltas, rays, lidar, T_thresh, bg=None):
+    """The occupancy-grid training render of `model` (a NeRFNetworkStatic with enable_occupancy_grid()) in fp64 with the parameters
+    `p64` (leaves()), on the packed samples march_rays_train returned: xyzs, dirs [M, 3], deltas [M, 2] (fp32), rays [N, 3] int32.
+    Positions and directions are normalised in fp32 with torch's own operations, as NeRFNetworkStatic.density / color write them (a
+    true division, not the fused render's reciprocal multiply); the direction encoding is per sample; the heads run on every packed
+    row (no weight mask in this path); sigma = trunc_exp(h0) density_scale; LiDAR images get a third channel of zeros; camera:
+    image + (1 - weights_sum) bg after the compositor, as run_cuda does.  -> weights_sum [N], depth [N], image [N, 2 | 3] (by ray id),
+    x01 [M, 3], logits [M] and, per row of `rays`, stop and margin (composite_packed)."""
+    enc = model.hash_encoder_lidar if lidar else model.hash_encoder_camera
+    x01 = (xyzs + model.bound) / (2 * model.bound)
+    feat = hash_features(x01, p64["hash_encoder_lidar" if lidar else "hash_encoder_camera"], enc.spec)
+    h = mlp(feat, p64["sigma_net"], model.sigma_net.spec)
+    sigma = _TruncExp.apply(h[:, 0]) * float(model.density_scale)
+    geo = f16(h[:, 1:model.sigma_net.spec.n_out])
+    d01 = (dirs + 1) / 2
+    enc_rows = freq_encode(d01, model.view_encoder_lidar.n_frequencies) if lidar else sh4_encode(d01)
+    rgbs = torch.sigmoid(head_logits(model, p64, enc_rows, geo, lidar))
+    if lidar:
+        rgbs = torch.cat([rgbs, torch.zeros_like(rgbs[:, :1])], -1)
+    ws, depth, image, stop, margin = composite_packed(sigma, rgbs, deltas, rays, T_thresh)
+    if lidar:
+        image = image[:, :2]
+    else:
+        image = image + (1.0 - ws)[:, None] * torch.tensor([float(v) for v in bg], dtype=torch.float64, device=ws.device)
+    return {"weights_sum": ws, "depth": depth, "image": image, "x01": x01, "logits": h[:, 0], "stop": stop, "margin": margin}
