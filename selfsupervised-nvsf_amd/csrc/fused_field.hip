@@ -189,7 +189,17 @@ struct DensityCtx {
     int g;
     const uint4* lds_lv;  // LDS_LV form of density_encode: {scale, res, byte offset, rows} of level 4q + g at [4 q] (the per-ray
                           // render kernels re-read the 16 B per step instead of holding 20 VGPRs across their long tile loop)
+    // SHARE form of density_encode: bit q set = level group q tries the shared form on this ray (wave-uniform), and this wave's exchange
+    // scratch in LDS (kShareWords dwords)
+    uint32_t share_mask;
+    uint32_t* share_lds;
 };
+
+// lane N of the row of 16 lanes, in every lane of the row (row_newbcast:N)
+template <int N>
+__device__ __forceinline__ uint32_t row_lane(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x150 + N, 0xF, 0xF, false);
+}
 
 // One 16-sample tile: hash-grid encode of x in [0,1]^3 (per lane) -> this lane's B fragment of the sigma MLP
 // (levels {g, g+4, g+8, g+12} of sample lane & 15).
@@ -197,9 +207,20 @@ constexpr uint32_t kFirstHashedC2 = 5;  // L16 F2 T2^19 base 16 -> 2048: 81^3 > 
 // FH >= 0: the first hashed level as a compile-time constant (the launcher picks the instance of the grid at hand): the kind of every
 // level group -- dense, hashed, mixed -- is then known per unrolled q, the other index form and its selects are not compiled in, and the
 // four groups form one basic block.  FH < 0: the run-time value (cx.first_hashed), any grid.
-template <int F, int QG, bool LDS_LV = false, int FH = -1>
+//
+// SHARE (k_render_uniform<*, false>; the rows of 16 lanes are 16 consecutive samples of ONE ray): on the coarse levels a tile lies in one
+// or two cells, and every lane gathers the same eight (sixteen) entries.  A level group q < 2 whose bit is set in cx.share_mask takes
+// cell A = the cell of the row's lane 0 and cell B = that of lane 15; if every lane of the WAVE sits in its row's A or B (one ballot:
+// the branch is wave-uniform), lane c gathers ONE entry -- corner c & 7 of A (c < 8) or B (c >= 8), by the index formula below, so the
+// same table entry -- and after the gathers of the groups q >= 2 are issued the 16 dwords of a row go through the wave's LDS scratch
+// (one ds_write_b32, two ds_read_b128 at row + 32 B * [cell is B]; same wave: LDS operations complete in order): raw[q][0..7] holds
+// exactly what the lane would have gathered, and phase 2 does not know.  Any lane elsewhere: the group runs the per-lane form.
+constexpr float kShareLambdaMax = 2.0f;  // k_render_uniform: a level group tries the shared form up to this many expected face crossings per tile
+constexpr int kShareWords = 2 * kWave;  // per wave: two level groups x 4 rows x 16 dwords
+template <int F, int QG, bool LDS_LV = false, int FH = -1, bool SHARE = false>
 __device__ __forceinline__ half8_t density_encode(const DensityCtx<F>& cx, const float (&x)[3]) {
     constexpr int Q = 8 / F;
+    static_assert(!SHARE || (F == 2 && QG == Q), "the shared form exchanges one dword per lane and runs behind the gathers of all groups");
     LaneLevels<F> lv_local;
     if constexpr (LDS_LV) {
         uint32_t again = 0;
@@ -223,6 +244,8 @@ __device__ __forceinline__ half8_t density_encode(const DensityCtx<F>& cx, const
     for (int q0 = 0; q0 < Q; q0 += QG) {
     float frac[Q][3];
     typename EntryOf<F>::type raw[Q][8];
+    bool shared[2] = {false, false};  // SHARE: level group q took the shared form on this tile (wave-uniform)
+    uint32_t share_sel[2] = {0u, 0u}, share_one[2] = {0u, 0u};
 #pragma unroll
     for (int q = q0; q < q0 + QG; ++q) {
         uint32_t c[3];
@@ -233,8 +256,37 @@ __device__ __forceinline__ half8_t density_encode(const DensityCtx<F>& cx, const
             frac[q][d] = pos - fl;
             c[d] = (uint32_t)(int32_t)fl;
         }
-        uint32_t idx[8];
         const bool all_dense = (uint32_t)(4 * q + 3) < first_hashed, all_hashed = (uint32_t)(4 * q) >= first_hashed;
+        if constexpr (SHARE) {
+            if (q < 2 && ((cx.share_mask >> q) & 1u)) {
+                uint32_t a[3], b[3];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    a[d] = row_lane<0>(c[d]);
+                    b[d] = row_lane<15>(c[d]);
+                }
+                const bool in_a = c[0] == a[0] && c[1] == a[1] && c[2] == a[2], in_b = c[0] == b[0] && c[1] == b[1] && c[2] == b[2];
+                share_sel[q] = in_a ? 0u : 8u;
+                shared[q] = __ballot(!(in_a || in_b)) == 0;
+                if (shared[q]) {
+                    const uint32_t col = (uint32_t)lane_id() & 15u;
+                    const bool of_a = col < 8u;
+                    const uint32_t cc[3] = {(of_a ? a[0] : b[0]) + (col & 1u), (of_a ? a[1] : b[1]) + ((col >> 1) & 1u), (of_a ? a[2] : b[2]) + ((col >> 2) & 1u)};
+                    uint32_t v = 0;
+                    if (all_dense || !all_hashed) {
+                        v = cc[0] + cc[1] * lv.res[q] + cc[2] * lv.res2[q];
+                        v = v >= lv.rows[q] ? v - lv.rows[q] : v;
+                    }
+                    if (all_hashed || !all_dense) {
+                        const uint32_t h = (cc[0] ^ (cc[1] * 2654435761u) ^ (cc[2] * 805459861u)) & (lv.rows[q] - 1u);
+                        v = (all_hashed || (uint32_t)(4 * q + g) >= first_hashed) ? h : v;
+                    }
+                    share_one[q] = gather_raw<2>(cx.rsrc, lv.boff[q] + v * (uint32_t)(F * sizeof(_Float16)));
+                }
+            }
+        }
+        if (!SHARE || q >= 2 || !shared[q]) {
+        uint32_t idx[8];
         if (all_dense || !all_hashed) {  // dense rows: c0 + c1*res + c2*res^2, wrapped once
             const uint32_t b00 = c[0] + c[1] * lv.res[q] + c[2] * lv.res2[q];
             const uint32_t b10 = b00 + lv.res[q], b01 = b00 + lv.res2[q], b11 = b10 + lv.res2[q];
@@ -263,10 +315,10 @@ __device__ __forceinline__ half8_t density_encode(const DensityCtx<F>& cx, const
             if constexpr (F == 2) raw[q][k] = gather_raw<2>(cx.rsrc, lv.boff[q] + idx[k] * (uint32_t)(F * sizeof(_Float16)));
             else raw[q][k] = gather_raw4(cx.rsrc, lv.boff[q] + idx[k] * (uint32_t)(F * sizeof(_Float16)));
         }
+        }
     }
     // phase 2: trilinear blend (corner order and fma chain of the specification)
-#pragma unroll
-    for (int q = q0; q < q0 + QG; ++q) {
+    auto blend = [&](int q, const typename EntryOf<F>::type (&r)[8]) {
         const float fx = frac[q][0], fy = frac[q][1], fz = frac[q][2];
         const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy}, wz[2] = {1.0f - fz, fz};
         if constexpr (F == 2) {
@@ -274,7 +326,7 @@ __device__ __forceinline__ half8_t density_encode(const DensityCtx<F>& cx, const
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const float w = (wx[k & 1] * wy[(k >> 1) & 1]) * wz[k >> 2];
-                fma_entry(w, raw[q][k], a0, a1);
+                fma_entry(w, r[k], a0, a1);
             }
             xf[q * F] = (_Float16)a0;
             xf[q * F + 1] = (_Float16)a1;
@@ -283,15 +335,34 @@ __device__ __forceinline__ half8_t density_encode(const DensityCtx<F>& cx, const
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const float w = (wx[k & 1] * wy[(k >> 1) & 1]) * wz[k >> 2];
-                fma_entry(w, raw[q][k][0], a0, a1);
-                fma_entry(w, raw[q][k][1], a2, a3);
+                fma_entry(w, r[k][0], a0, a1);
+                fma_entry(w, r[k][1], a2, a3);
             }
             xf[q * F] = (_Float16)a0;
             xf[q * F + 1] = (_Float16)a1;
             xf[q * F + 2] = (_Float16)a2;
             xf[q * F + 3] = (_Float16)a3;
         }
+    };
+    if constexpr (SHARE) {
+        // behind the gathers of the fine groups, which stay in flight: a row's 16 dwords -> the 8 of every lane's cell.  Each coarse group
+        // is blended inside its branch, so that the wait in front of a blend counts the loads of ITS form only
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            if (shared[q]) {
+                uint32_t* slot = cx.share_lds + q * kWave;
+                slot[lane_id()] = share_one[q];
+                const uint4* cell = reinterpret_cast<const uint4*>(slot + 16 * g + share_sel[q]);
+                const uint4 lo = cell[0], hi = cell[1];
+                const uint32_t r[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                blend(q, r);
+            } else {
+                blend(q, raw[q]);
+            }
+        }
     }
+#pragma unroll
+    for (int q = (SHARE ? 2 : q0); q < q0 + QG; ++q) blend(q, raw[q]);
     }
     return xf;
 }
@@ -1524,7 +1595,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     RayBatch rb, const _Float16* __restrict__ table, uint32_t table_bytes, GridMeta meta, uint32_t first_hashed,
     const uint2* __restrict__ feat, const _Float16* __restrict__ w_sigma, const _Float16* __restrict__ w_a, const _Float16* __restrict__ w_b,
     float k_scale, float w_thresh, float bg0, float bg1, float bg2, int use_bg, float* __restrict__ z_vals, float* __restrict__ weights,
-    float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image, RenderTrainOut rt = RenderTrainOut()) {
+    float* __restrict__ weights_sum, float* __restrict__ depth, float* __restrict__ image, float share_thresh = -1.0f,
+    RenderTrainOut rt = RenderTrainOut()) {
     using FR = OccFrags<LIDAR>;
     constexpr int F = 2;
     constexpr int IN_STEPS = FR::IN_STEPS;
@@ -1532,6 +1604,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     __shared__ uint4 s_lv[kMaxLevels];
     __shared__ half8_t s_frag[FR::kCount * kWave];
     __shared__ float4_t s_pre[kWavesPerBlock * FR::kPre];
+    __shared__ __attribute__((aligned(16))) uint32_t s_share[FROM_FEATURES ? 1 : kWavesPerBlock * kShareWords];
     fill_level_table<F>(s_lv, meta);
     const int lane = lane_id(), g = lane >> 4, c = lane & 15;
     for (int f = (int)(threadIdx.x >> 6); f < FR::kCount; f += kWavesPerBlock) s_frag[f * kWave + lane] = occ_fragment<LIDAR>(f, lane, w_sigma, w_a, w_b);
@@ -1560,6 +1633,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     const float near = rb.nears[n], range = rb.fars[n] - near;
     const float sample_dist = range / (float)T;
     const float ro[3] = {rb.rays_o[3 * (size_t)n], rb.rays_o[3 * (size_t)n + 1], rb.rays_o[3 * (size_t)n + 2]}, rd[3] = {rd0, rd1, rd2};
+    if constexpr (!FROM_FEATURES) {
+        // which level groups try the shared form of density_encode on this ray: lambda_q = the cell faces a 16-sample tile is expected to
+        // cross at the group's finest level 4 q + 3 (16 x scale x the L1 length of a step in the unit cube); above the threshold a tile
+        // rarely stays inside two cells and the test is wasted.  Steers speed only: either form gives the same bits.
+        const float step1 = (sample_dist * rb.inv_extent) * ((fabsf(rd0) + fabsf(rd1)) + fabsf(rd2));
+        const uint32_t m = ((16.0f * meta.scale[3]) * step1 <= share_thresh ? 1u : 0u) | ((16.0f * meta.scale[7]) * step1 <= share_thresh ? 2u : 0u);
+        cx.share_mask = __builtin_amdgcn_readfirstlane(m);
+        cx.share_lds = s_share + (threadIdx.x >> 6) * kShareWords;
+    }
     const size_t row0 = (size_t)n * T;
     float carry = 1.0f, ws = 0.0f, dp = 0.0f, img[C];
 #pragma unroll
@@ -1599,7 +1681,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             if (i0 + 16u < T) request(i0 + 16u);
             float x[3];
             sample_x01(rb, ro, rd, z, x);
-            feat8 = density_encode<F, 4, true, FH>(cx, x);
+            feat8 = density_encode<F, 4, true, FH, true>(cx, x);
             if constexpr (TRAIN) {
                 if (g == 0 && valid) { rt.x01[3 * s] = x[0]; rt.x01[3 * s + 1] = x[1]; rt.x01[3 * s + 2] = x[2]; }
             }
@@ -2117,16 +2199,19 @@ static int render_uniform_impl(const float* rays_o, const float* rays_d, const f
     const RenderTrainOut rt = train ? *train : RenderTrainOut();
     const int use_bg = (h_bg_color && !lidar) ? 1 : 0;
     const dim3 grid_dim(cdiv(N, kWavesPerBlock)), block(kBlock);
+    // corner_share (tests): 1 never shares (the per-lane form on every tile), 2 tries both coarse groups on every ray
+    const int cs = nvsf_variant(kVarCornerShare);
+    const float share_thresh = cs == 1 ? -1.0f : cs == 2 ? INFINITY : kShareLambdaMax;
 #define LAUNCH_RU_FH(LD, FF, FH)                                                                                                      \
     do {                                                                                                                              \
         if (train)                                                                                                                    \
             hipLaunchKernelGGL((k_render_uniform<LD, FF, true, FH>), grid_dim, block, 0, stream, rb, w.table, (uint32_t)gi.table_bytes, gi.meta, \
                                gi.first_hashed, fp, w.sigma, w.head_a, w.head_b, k_scale, w_thresh, w.bg[0], w.bg[1], w.bg[2], use_bg, z_vals,   \
-                               weights, weights_sum, depth, image, rt);                                                               \
+                               weights, weights_sum, depth, image, share_thresh, rt);                                                               \
         else                                                                                                                          \
             hipLaunchKernelGGL((k_render_uniform<LD, FF, false, FH>), grid_dim, block, 0, stream, rb, w.table, (uint32_t)gi.table_bytes, gi.meta, \
                                gi.first_hashed, fp, w.sigma, w.head_a, w.head_b, k_scale, w_thresh, w.bg[0], w.bg[1], w.bg[2], use_bg, z_vals,    \
-                               weights, weights_sum, depth, image, rt);                                                               \
+                               weights, weights_sum, depth, image, share_thresh, rt);                                                               \
     } while (0)
     // the gathering form has an instance for the grid of BASELINE config 2 (levels 0-4 dense, 5-15 hashed) beside the general one
 #define LAUNCH_RU(LD, FF)                                                                                                             \
