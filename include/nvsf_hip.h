@@ -896,6 +896,34 @@ int nvsf_range_image_object_mask(const float* range_m, uint32_t H, uint32_t W, c
  * H W < 2^31.  One launch. */
 int nvsf_box_mask_image(const int32_t* boxes, uint32_t B, uint32_t H, uint32_t W, uint8_t* dyn_mask, nvsf_stream_t stream);
 
+/* ---- 13. U-Net ray-drop refinement ------------------------------------------------------------------------------------------- */
+
+/* Contract as sections 10 to 12: status return, explicit stream, no allocation, the workspace passed in and its size checked,
+ * NVSF_ERR_INVALID_ARG before any launch.  The network is the reference's UNet(in_channels = 3, channels = 32, out_channels = 1) and
+ * no other; 16 <= H, W and H W <= 2^21.
+ *
+ * Packed weights (device, 16-byte aligned, fp32): twenty records in the order inc, down1 .. down4 (two convolutions each), attention
+ * qkv, attention proj, up1 .. up4 (two each), outc.  A record of a convolution Cin -> Cout with T = 9 or 1 taps, Cp = Cin rounded up
+ * to 16:  scale [Cp], shift [Cp] (the BatchNorm in front of it folded from its running statistics: scale = weight / sqrt(var + eps),
+ * shift = bias - mean scale; 1 and 0 where there is none), bias [Cout] (0 where there is none), w [Cp T, Cout] with
+ * w[(ci T + ky 3 + kx), co] = weight[co, ci, ky, kx] and zero rows for ci >= Cin.  nvsf/nerf/refine.py packs them. */
+
+/* ref: the layer shapes of UNet.__init__, nvsf/nerf/models/unet.py:143-156.  sizes: HOST pointer to two uint64: the workspace bytes
+ * of nvsf_unet_forward at H x W and the length of the packed weights in floats.  Launches nothing; the stream is not used. */
+int nvsf_unet_sizes(uint32_t H, uint32_t W, uint64_t* sizes, nvsf_stream_t stream);
+
+/* ref: UNet.forward in evaluation mode, nvsf/nerf/models/unet.py:158-171, on the input the evaluation builds at
+ * nvsf/nerf/trainer.py:721-733: raydrop, intensity, range [H, W] fp32 planes of one frame; prob [H, W] fp32 = the refined ray-drop
+ * probability.  With gated_intensity and gated_range (both or neither) the last kernel also writes intensity * m and range * m,
+ * m = prob > thres as 1 / 0 (trainer.py:726-733).  Every product runs on v_mfma_f32_32x32x2_f32 (exact fp32); BatchNorm + ReLU are
+ * applied by the load of the convolution that follows, MaxPool by the load of Down's first convolution, upsample + pad + concat by
+ * the load of Up's first convolution, sigmoid and gate by the last kernel.  21 launches: 1 (inc) + 8 (down) + 3 (attention: qkv,
+ * softmax products, proj + residual) + 8 (up) + 1 (outc, sigmoid, gate); DESIGN.md section 9g.  Deterministic (no atomics).
+ * workspace: 16-byte aligned, nvsf_unet_sizes bytes. */
+int nvsf_unet_forward(const float* raydrop, const float* intensity, const float* range, uint32_t H, uint32_t W, const float* packed,
+                      size_t n_packed, void* workspace, size_t ws_bytes, float thres, float* prob, float* gated_intensity,
+                      float* gated_range, nvsf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

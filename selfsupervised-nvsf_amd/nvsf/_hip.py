@@ -122,6 +122,9 @@ SIGNATURES = {
     "nvsf_lidar_to_pano": [_P, _P, _U, _U, _U, _P, _P, ctypes.c_size_t, _P, _P],
     "nvsf_range_image_object_mask": [_P, _U, _U, _P, _P, _P, _U, _U, _P, ctypes.c_size_t, _P],
     "nvsf_box_mask_image": [_P, _U, _U, _U, _P],
+    # section 13: U-Net ray-drop refinement
+    "nvsf_unet_sizes": [_U, _U, _P],
+    "nvsf_unet_forward": [_P, _P, _P, _U, _U, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _F, _P, _P, _P],
 }
 
 _lib = None

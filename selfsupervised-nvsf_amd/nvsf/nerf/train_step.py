@@ -23,7 +23,7 @@ in its `grad_loss` form (trainer.py:296-470: first differences (or Sobel gradien
 ray-drop channel and the flatness of the true frame; `LidarGradLossFn`, csrc/losses.hip), the alternation between random pixels and
 patches (trainer.py:1035-1062: `set_epoch`) and the error maps the patch sampler draws from (trainer.py:552-630: `update_error_maps`).
 The regulariser's criteria (`--depth_grad_loss` l1 / mse / huber / smoothl1 / cos) and `--sobel_grad` are built; its three smoothness switches
-fail in the reference itself (see __init__).  Logging and UNet refinement are out of scope.
+fail in the reference itself (see __init__).  Logging is out of scope; the U-Net ray-drop refinement lives in nvsf/nerf/refine.py.
 """
 import math
 import warnings
@@ -688,14 +688,16 @@ class RenderTrainStep:
         if self.ema is not None:
             self.ema.update()
 
-    def checkpoint_state(self, epoch=0, stats=None, full=True, reference_layout=False):
+    def checkpoint_state(self, epoch=0, stats=None, full=True, reference_layout=False, refiner=None):
         """The dict Trainer.save_checkpoint writes with torch.save (nvsf/nerf/utils.py:622-648): epoch, global_step, stats,
         model and -- for a `full` checkpoint -- optimizer, lr_scheduler, scaler, ema.  `model` always speaks the reference's
         schema (names and shapes).  `optimizer` and `ema` are lists by parameter position: written in this package's layout (one
         entry per `planes_cl`) unless `reference_layout`, which expands the optimiser entry to one state per plane so that a
         reference Trainer resumes from it (checkpoint_compat); the `ema` entry cannot be written for the reference -- torch_ema
         wants shadows for the three unused modules this model does not have -- and the reference then starts a fresh average,
-        as it does for any checkpoint whose ema fails to load (utils.py:728-747).  load_checkpoint reads both layouts."""
+        as it does for any checkpoint whose ema fails to load (utils.py:728-747).  load_checkpoint reads both layouts.
+        `refiner`: a RaydropRefiner (nvsf/nerf/refine.py) whose `unet.*` entries join `model`, which is what the reference saves after
+        its refinement (trainer.py:1011-1012); RaydropRefiner.load_from_checkpoint reads them back."""
         self.sync()
         state = {"epoch": epoch, "global_step": self.global_step, "stats": stats if stats is not None else {}}
         if full:
@@ -708,10 +710,12 @@ class RenderTrainStep:
             if self.ema is not None:
                 state["ema"] = self.ema.state_dict()
         state["model"] = self.model.state_dict()
+        if refiner is not None:
+            state["model"].update(refiner.state_entries())
         return state
 
-    def save_checkpoint(self, path, epoch=0, stats=None, full=True, reference_layout=False):
-        torch.save(self.checkpoint_state(epoch, stats, full, reference_layout), path)
+    def save_checkpoint(self, path, epoch=0, stats=None, full=True, reference_layout=False, refiner=None):
+        torch.save(self.checkpoint_state(epoch, stats, full, reference_layout, refiner), path)
 
     def load_checkpoint(self, checkpoint, model_only=False):
         """Trainer.load_checkpoint (nvsf/nerf/utils.py:682-747): a bare state_dict loads strictly; a checkpoint dict loads its
@@ -843,10 +847,12 @@ class PointsMeter:
 
 
 def eval_step(model, data, num_steps, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, alpha_rgb=1.0, raydrop_thres=0.5, max_ray_batch=4096,
-              split_rays=True, **render_kwargs):
-    """Whole-frame evaluation of one frame, the reference's Trainer.eval_step (nvsf/nerf/trainer.py:658-815) without its optional
-    U-Net ray-drop refinement: `data` = FrameSet(..., training=False).collate([i]) -- every pixel of the range image and of the camera
-    image.  Both modalities go through the staged render, a frame's rays split over the ranks (frame_shard.render_sharded); the
+              split_rays=True, refiner=None, **render_kwargs):
+    """Whole-frame evaluation of one frame, the reference's Trainer.eval_step (nvsf/nerf/trainer.py:658-815):
+    `data` = FrameSet(..., training=False).collate([i]) -- every pixel of the range image and of the camera image.  `refiner`: a
+    RaydropRefiner (nvsf/nerf/refine.py); with one, `pred_raydrop` becomes the U-Net's refined probability of the rendered
+    (ray-drop, intensity, range) planes and the gate below uses it (:721-733, the shipped configuration's `use_refine`), one HIP
+    forward per frame whose last kernel also writes the gated intensity and range.  None: the field's own probability.  Both modalities go through the staged render, a frame's rays split over the ranks (frame_shard.render_sharded); the
     predicted ray-drop mask (`pred_raydrop > raydrop_thres`, :726) gates predicted intensity and range, the ground truth is gated by
     its own mask (:695-696); loss = the reference's mean-reduced L1 range + MSE ray-drop + MSE intensity + MSE RGB (:733-737, :795-796;
     criteria as main_nvsf.py:205-221).  Returns a dict of [B, H, W(, C)] predictions / ground truths and `loss`."""
@@ -866,8 +872,12 @@ def eval_step(model, data, num_steps, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, al
                    max_ray_batch=max_ray_batch, **render_kwargs)
         img = o["image_lidar"].reshape(B, Hl, Wl, 2)
         pred_raydrop, pred_intensity, pred_depth = img[..., 0], img[..., 1], o["depth_lidar"].reshape(B, Hl, Wl)
-        mask = (pred_raydrop > raydrop_thres).to(pred_depth.dtype)
-        pred_intensity, pred_depth = pred_intensity * mask, pred_depth * mask
+        if refiner is not None:
+            refined = [refiner(pred_raydrop[b].float(), pred_intensity[b].float(), pred_depth[b].float(), thres=raydrop_thres) for b in range(B)]
+            pred_raydrop, pred_intensity, pred_depth = (torch.stack([f[k] for f in refined]) for k in range(3))
+        else:
+            mask = (pred_raydrop > raydrop_thres).to(pred_depth.dtype)
+            pred_intensity, pred_depth = pred_intensity * mask, pred_depth * mask
         loss = loss + alpha_d * (pred_depth - gt_depth).abs().mean() + alpha_r * ((pred_raydrop - gt_raydrop) ** 2).mean() \
             + alpha_i * ((pred_intensity - gt_intensity) ** 2).mean()
         out.update(pred_raydrop=pred_raydrop, pred_intensity=pred_intensity, pred_depth=pred_depth, gt_raydrop=gt_raydrop,
@@ -884,7 +894,8 @@ def eval_step(model, data, num_steps, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, al
     return out
 
 
-def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="rays", meters=None, intensity_inv_scale=1, **eval_kwargs):
+def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="rays", meters=None, intensity_inv_scale=1, refiner=None,
+                    **eval_kwargs):
     """The metric half of the reference's evaluate_one_epoch (trainer.py:1458-1560) over a FrameSet opened with training=False:
     per frame eval_step, then the two quality metrics of the headline benchmark -- PSNR of the image (error_matrices.py:48-57), range
     RMSE in metres (:263-285) -- and chamfer distance / F-score of the range image's point cloud (PointsMeter, :299-356, on
@@ -911,7 +922,8 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
     zeros), products by plain torch ops, the same meter kernels; keys "depth", "intensity", "raydrop", "chamfer_distance", "f_score",
     "rgb_psnr", "rgb_ssim" (and "rgb_depth_rmse") with the suffixes "_static" and "_dynamic", riding in the same all-reduce.  The range
     limit of the masks' z-buffer is the model's `lidar_max_depth`.  The default (None) returns exactly the six keys above from the same
-    code path as before."""
+    code path as before.  `refiner`: passed to eval_step -- every LiDAR figure, the split tables included, is then that of the refined
+    ray-drop probability and of the intensity and range it gates; the keys do not change."""
     from nvsf import frame_shard
     if shard not in ("rays", "frames"):
         raise ValueError("shard: 'rays' or 'frames'")
@@ -941,7 +953,7 @@ def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="ray
             todo = todo[rank::ws]
         for i in todo:
             data = frames.collate([int(i)])
-            e = eval_step(model, data, num_steps, split_rays=(shard == "rays"), **eval_kwargs)
+            e = eval_step(model, data, num_steps, split_rays=(shard == "rays"), refiner=refiner, **eval_kwargs)
             ps.append(psnr(e["pred_rgb"], e["gt_rgb"]))
             rm.append(depth_rmse(e["pred_depth"], e["gt_depth"], frames.scale))
             points.update(e["pred_depth"], e["gt_depth"])

@@ -3,6 +3,7 @@
     python tools/train_example.py --root /path/to/kitti360_nvsf --sequence 1908 [--dynamic] [--epochs 6] [--plain]
                                   [--export-mesh out.ply --mesh-res 256 256 256 --mesh-threshold 10] [--dynamic --flow-loss]
                                   [--eval-table] [--rgbd-loss] [--annotations boxes.json [--offset X Y Z]]
+                                  [--refine [--refine-iterations N]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 tools/train_example.py ...
 
 Data: the reference's on-disk formats (transforms_{seq}_{split}.json + range-image .npy + images; nvsf/nerf/dataset/formats.py).
@@ -23,6 +24,10 @@ depth RMSE line the reference prints as "RMSE = ".
 --annotations PATH (with --eval-table): a JSON sidecar of the moving objects' 3-D boxes, {"<frame_id>": [{"class": str, "vertices":
 [[x, y, z] x 8]}, ...]} in the world frame in metres (--offset: the recentring of the poses, the reference's --offset); the table is then
 also printed over the static background and over the boxes (trainer.py:1545-1626; masks on the device, nvsf/nerf/object_masks.py).
+--refine (the shipped configuration's use_refine): after training, the ray-drop refinement U-Net is fitted on the staged renders of the
+training frames (Trainer.refine, trainer.py:905-1017; nvsf/nerf/refine.py, --refine-iterations steps, the reference's 1000) and the
+evaluation is reported twice, without and with it, as the reference logs both; the refined evaluation runs the U-Net's HIP forward
+(csrc/unet.hip) once per frame.
 """
 import argparse
 import os
@@ -88,6 +93,9 @@ def main():
                     "RenderTrainStep(use_rgbd_loss=True)); adds the camera depth RMSE to --eval-table")
     ap.add_argument("--annotations", default=None, metavar="PATH", help="JSON sidecar of the moving objects' 3-D boxes per frame id (world frame, "
                     "metres); --eval-table then also prints the static / dynamic tables (nvsf/nerf/object_masks.py)")
+    ap.add_argument("--refine", action="store_true", help="fit the ray-drop refinement U-Net after training and evaluate with it as well "
+                    "(nvsf/nerf/refine.py; HIP forward csrc/unet.hip)")
+    ap.add_argument("--refine-iterations", type=int, default=1000, help="optimisation steps of the U-Net fit (the reference's 1000)")
     ap.add_argument("--offset", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"), help="world = pose / scale + offset")
     args = ap.parse_args()
     if args.annotations and not args.eval_table:
@@ -162,14 +170,28 @@ def main():
     from nvsf.nerf.train_step import evaluate_frames
     whole = FrameSet(root, args.sequence, "train", scale, device=dev, training=False, camera_depth=args.rgbd_loss,
                      annotations=args.annotations, offset=args.offset)
-    res = evaluate_frames(model, whole, args.num_steps, indices=range(min(len(whole), 4)), ema=trainer.ema,
-                          meters="table" if args.eval_table else None)
-    if rank == 0:
-        print(f"evaluation over {res['frames']} frames: loss {res['loss']:.4f}, PSNR {res['psnr']:.2f} dB, range RMSE {res['depth_rmse_m']:.2f} m, "
-              f"chamfer distance {res['chamfer_distance']:.3f}, F-score {res['f_score']:.3f}")
-        if args.eval_table:
-            from nvsf.nerf.meters import table_report
-            print("\n".join(table_report(res)), flush=True)
+    refiner = None
+    if args.refine:  # every rank fits the same U-Net from the same seed on the same renders
+        import time
+        from nvsf.nerf.refine import RaydropRefiner
+        torch.manual_seed(0)
+        refiner = RaydropRefiner(dev)
+        t0 = time.perf_counter()
+        losses = refiner.fit(model, whole, args.num_steps, ema=trainer.ema, iterations=args.refine_iterations,
+                             generator=torch.Generator().manual_seed(0))
+        torch.cuda.synchronize()
+        if rank == 0:
+            print(f"ray-drop refinement: {len(losses)} iterations over {len(whole)} frames in {time.perf_counter() - t0:.1f} s, "
+                  f"BCE {np.mean(losses[:5]):.4f} -> {np.mean(losses[-5:]):.4f}", flush=True)
+    for label, r in ((("", None),) + ((("refined ", refiner),) if refiner is not None else ())):
+        res = evaluate_frames(model, whole, args.num_steps, indices=range(min(len(whole), 4)), ema=trainer.ema,
+                              meters="table" if args.eval_table else None, refiner=r)
+        if rank == 0:
+            print(f"{label}evaluation over {res['frames']} frames: loss {res['loss']:.4f}, PSNR {res['psnr']:.2f} dB, range RMSE "
+                  f"{res['depth_rmse_m']:.2f} m, chamfer distance {res['chamfer_distance']:.3f}, F-score {res['f_score']:.3f}")
+            if args.eval_table:
+                from nvsf.nerf.meters import table_report
+                print("\n".join(table_report(res)), flush=True)
     if args.export_mesh and rank == 0:
         from nvsf.nerf.mesh import export_mesh_density
         t_first = float(whole.collate([0])["time"].reshape(-1)[0])
