@@ -78,23 +78,17 @@ static int mlp_fwd_impl(const void* x, int x_is_f16, uint32_t M, uint32_t n_in, 
                         uint32_t out_stride, XPrefix pre, hipStream_t stream) {
     if (M == 0) return NVSF_OK;
     REQUIRE(x && weights_f16 && out_f32);
-    REQUIRE(n_in >= 1 && n_in <= in_cols && in_cols % 16 == 0 && x_stride >= n_in - pre.split);
     if (out_cols == 16) REQUIRE(out_stride >= 16 && out_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(out_f32) & 15u) == 0);
     else REQUIRE(out_cols >= 1 && out_cols <= 4 && out_stride >= out_cols && (reinterpret_cast<uintptr_t>(out_f32) & 3u) == 0);
-    REQUIRE((reinterpret_cast<uintptr_t>(weights_f16) & 15u) == 0);
-    if (hidden != (uint32_t)kHidden || n_hidden < 1 || n_hidden > 3 || in_cols > 128) return NVSF_ERR_UNSUPPORTED;
-    const int in_steps = (int)((in_cols + 31) / 32);
-    const size_t esz = x_is_f16 ? 2 : 4;
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(x) & 15u) == 0) && ((x_stride * esz) % 16 == 0);
+    XRowsPlan rows;
+    const int rc = plan_x_rows(x, x_is_f16, n_in, x_stride, weights_f16, in_cols, pre, hidden == (uint32_t)kHidden && n_hidden >= 1 && n_hidden <= 3, true, rows);
+    if (rc != NVSF_OK) return rc;
+    const int in_steps = rows.in_steps, vec_ok = rows.vec_ok;
+    const bool fast = rows.fast;
     const uint32_t n_tiles = (M + 15) / 16;
     const uint32_t blocks = n_tiles / 4 + 1 < 2048u ? n_tiles / 4 + 1 : 2048u;
     const _Float16* w = reinterpret_cast<const _Float16*>(weights_f16);
     float* o = out_f32;
-    const bool fast = x_rows_fast(n_in - pre.split, x_stride, vec_ok);
-    if (pre.a) {  // shared-prefix rows: aligned fp16 only, whole 8-column groups on either side, a tile inside one group
-        REQUIRE(x_is_f16 && fast && pre.split % 8 == 0 && pre.split < n_in && pre.a_stride >= pre.split && pre.a_stride % 8 == 0);
-        REQUIRE(pre.rows_per_a >= 16 && pre.rows_per_a % 16 == 0 && (reinterpret_cast<uintptr_t>(pre.a) & 15u) == 0);
-    }
 #define LAUNCH(S, H, XF, FA)                                                                                                   \
     hipLaunchKernelGGL((k_mlp_fwd<S, H, XF, FA>), dim3(blocks), dim3(kBlock), 0, stream, x, M, n_in, x_stride, w, in_cols, o, \
                        out_stride, vec_ok, pre, out_cols)

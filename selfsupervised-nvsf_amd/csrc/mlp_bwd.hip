@@ -144,12 +144,158 @@ __device__ __forceinline__ void relu_mask(float4_t (&gacc)[kHidTiles], const hal
             if (!(h[t >> 1][(t & 1) * 4 + r] > (_Float16)0.0f)) gacc[t][r] = 0.0f;
 }
 
+// ---- what the two kernels below share: arguments, operand fetch, MFMA layer loops, dX store ---------------------------------------
+// Everything a launch is given; the helpers read it.  The kernels themselves keep the fields as positional parameters (BWD_PARAMS) and
+// gather them into this struct in their first statement: as ONE by-value struct parameter the same fields cost the wave kernel's
+// aligned-row instances 20-28 more SGPR spills and 50-90 more instructions (profiles/mlp_bwd_factored_resources.txt), and the pointers
+// would lose their __restrict__.
+struct BwdArgs {
+    const void* x;  // rows [M, x_stride], fp16 or fp32 (X_F16); with `pre.a` the columns behind the shared prefix only
+    uint32_t M, n_in, x_stride;
+    const _Float16* weights;
+    uint32_t in_cols;
+    const float* grad_out;  // dL/dout [M, go_stride], n_out columns used (unused when gc.sigma)
+    uint32_t n_out, go_stride;
+    float grad_scale;
+    float* grad_x;  // nullptr: no input gradient
+    uint32_t gx_stride;
+    float* grad_w;
+    int vec_ok;
+    uint32_t gx_col0;   // first input column whose gradient is wanted
+    int gx_accumulate;  // bit 0: add into grad_x; bits 8..15: 0 = rows, 2 / 4 = column blocks (store_dx)
+    int go_vec;
+    XPrefix pre;
+    GoCompose gc;
+};
+
+#define BWD_PARAMS                                                                                                                        \
+    const void *__restrict__ x, uint32_t M, uint32_t n_in, uint32_t x_stride, const _Float16 *__restrict__ weights, uint32_t in_cols,     \
+        const float *__restrict__ grad_out, uint32_t n_out, uint32_t go_stride, float grad_scale, float *__restrict__ grad_x,             \
+        uint32_t gx_stride, float *__restrict__ grad_w, int vec_ok, uint32_t gx_col0, int gx_accumulate, int go_vec, XPrefix pre,         \
+        GoCompose gc
+// (BwdArgs is initialised positionally from this list: its order is the order of the struct's fields)
+#define BWD_ARGS x, M, n_in, x_stride, weights, in_cols, grad_out, n_out, go_stride, grad_scale, grad_x, gx_stride, grad_w, vec_ok, gx_col0, gx_accumulate, go_vec, pre, gc
+
+// operands of one 16-sample tile: the x fragments and the raw output gradients of this lane's sample
+template <int IN_STEPS, bool COMPOSE>
+struct BwdOperands {
+    half8_t xf[IN_STEPS];
+    float go[8];
+    float ex[COMPOSE ? 12 : 1];  // COMPOSE: the second head's row and the four scalars, as loaded
+    uint32_t m;
+    bool valid;
+};
+
+// Requests the operands of `tile`: LOADS ONLY (see GoCompose::issue); the kernels consume them an iteration later.
+template <int IN_STEPS, bool X_F16, bool FAST, bool COMPOSE>
+__device__ __forceinline__ void fetch_operands(const BwdArgs& a, const XTail& tail, uint32_t tile, uint32_t n_tiles, int g, int c,
+                                               BwdOperands<IN_STEPS, COMPOSE>& op) {
+    op.m = tile * 16 + (uint32_t)c;
+    op.valid = tile < n_tiles && op.m < a.M;
+    const size_t row = op.valid ? op.m : (a.M - 1);
+    const uint32_t tile_u = __builtin_amdgcn_readfirstlane(tile);
+    const _Float16* prow = a.pre.a ? a.pre.row_of((tile_u < n_tiles && tile_u * 16u < a.M) ? tile_u * 16u : a.M - 1u) : nullptr;
+    issue_x_row<IN_STEPS, X_F16, FAST>(op.xf, a.x, row, a.x_stride, g, (int)a.n_in, (int)a.in_cols, a.vec_ok != 0, tail, prow, a.pre.split);
+    const float* go_row = a.grad_out + row * a.go_stride;
+    if constexpr (COMPOSE) {  // density network: the logit gradient composed from (grad_sigma, sigma, geometry gradient rows)
+        a.gc.issue(row, g, op.go, op.ex);
+    } else if (a.go_vec) {  // 16 outputs, 16-byte aligned rows: two 16-byte loads for the lanes that hold outputs (g < 2)
+        const float4* p = reinterpret_cast<const float4*>(go_row) + 2 * (g & 1);
+        const float4 lo = p[0], hi = p[1];
+        op.go[0] = lo.x; op.go[1] = lo.y; op.go[2] = lo.z; op.go[3] = lo.w;
+        op.go[4] = hi.x; op.go[5] = hi.y; op.go[6] = hi.z; op.go[7] = hi.w;
+    } else {  // element loads with the column clamped into the row, issued back to back
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t o = 8 * (g & 1) + j;
+            op.go[j] = go_row[o < a.n_out ? o : a.n_out - 1];
+        }
+    }
+}
+
+// One 16-row output tile of a layer for one sample tile: sum_s frag[base + s] b[s].
+template <int STEPS>
+__device__ __forceinline__ float4_t tile_acc(const half8_t* frag, int base, const half8_t (&b)[STEPS]) {
+    float4_t a = {0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) a = mfma16(frag[(base + s) * kWave], b[s], a);
+    return a;
+}
+// The four output tiles of a layer whose fragments lie [t][s] from `base`, for NT sample tiles.  Fragment loop outside, tile loop inside:
+// every weight fragment read from LDS feeds all NT tiles (NT = 1 staged, 2 wave).
+template <int NT, int STEPS>
+__device__ __forceinline__ void layer_tiles(const half8_t* frag, int base, const half8_t (&b)[NT][STEPS], float4_t (&acc)[NT][kHidTiles]) {
+#pragma unroll
+    for (int t = 0; t < kHidTiles; ++t)
+#pragma unroll
+        for (int u = 0; u < NT; ++u) acc[u][t] = tile_acc<STEPS>(frag, base + t * STEPS, b[u]);
+}
+
+// Forward recompute (sample on the lane): the hidden activations as the next layer's B fragments; h1 only with two hidden layers.
+template <int IN_STEPS, int N_HIDDEN, int NT>
+__device__ __forceinline__ void forward_recompute(const half8_t* frag, const half8_t (&xf)[NT][IN_STEPS], half8_t (&h0)[NT][kHidSteps],
+                                                  half8_t (&h1)[NT][kHidSteps]) {
+    using FR = BwdFrags<IN_STEPS, N_HIDDEN>;
+    float4_t acc[NT][kHidTiles];
+    layer_tiles<NT, IN_STEPS>(frag, FR::kF0, xf, acc);
+#pragma unroll
+    for (int u = 0; u < NT; ++u) pack_hidden(acc[u], h0[u]);
+    if constexpr (N_HIDDEN == 2) {
+        layer_tiles<NT, kHidSteps>(frag, FR::kF1, h0, acc);
+#pragma unroll
+        for (int u = 0; u < NT; ++u) pack_hidden(acc[u], h1[u]);
+    }
+}
+
+// This lane's four columns k0 .. k0 + 3 of dL/dx of sample m, in every layout of the destination.
+template <bool FAST>
+__device__ __forceinline__ void store_dx(const BwdArgs& a, float4_t acc, uint32_t m, bool valid, uint32_t k0, float inv_scale) {
+    float* row_x = a.grad_x + (size_t)m * a.gx_stride;
+    if constexpr (FAST) {  // 16-byte aligned window: this lane's four columns as one store (the last group may
+                           // reach into the row's alignment padding)
+        const uint32_t blk = ((uint32_t)a.gx_accumulate >> 8) & 0xFFu;  // 0: rows; 2 / 4: column blocks (below)
+        if (blk == 0u) {
+            if (valid && k0 >= a.gx_col0 && k0 < a.n_in) {
+                float4_t* p = reinterpret_cast<float4_t*>(row_x + (k0 - a.gx_col0));
+                float4_t v = acc * inv_scale;
+                if (a.gx_accumulate & 1) v += *p;
+                *p = v;
+            }
+        } else if (valid && k0 < a.n_in) {
+            // block-major dX: [n_in / blk][M][blk] -- the gradient of a hash grid's features, level by level, so that the
+            // table scatter reads a level's column as one stream (a row-major [M, 32] costs it a 128-byte line per 8 bytes
+            // and level: hashgrid.hip).  16 consecutive samples of a level are 16 * blk * 4 contiguous bytes.
+            float4_t v = acc * inv_scale;
+            if (blk == 4u) {
+                float4_t* p = reinterpret_cast<float4_t*>(a.grad_x + ((size_t)(k0 >> 2) * a.M + m) * 4);
+                if (a.gx_accumulate & 1) v += *p;
+                *p = v;
+            } else {
+                float2* p0 = reinterpret_cast<float2*>(a.grad_x + ((size_t)(k0 >> 1) * a.M + m) * 2);
+                float2* p1 = reinterpret_cast<float2*>(a.grad_x + ((size_t)((k0 >> 1) + 1u) * a.M + m) * 2);
+                float2 v0 = make_float2(v[0], v[1]), v1 = make_float2(v[2], v[3]);
+                if (a.gx_accumulate & 1) { v0.x += p0->x; v0.y += p0->y; v1.x += p1->x; v1.y += p1->y; }
+                *p0 = v0;
+                *p1 = v1;
+            }
+        }
+    } else if (valid) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const uint32_t k = k0 + r;
+            if (k < a.n_in && k >= a.gx_col0) {
+                const float v = acc[r] * inv_scale;
+                row_x[k - a.gx_col0] = (a.gx_accumulate & 1) ? row_x[k - a.gx_col0] + v : v;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// LDS-staged form: production for the 32-64-16 density network, the test reference for every other shape.
 template <int IN_STEPS, int N_HIDDEN, bool X_F16, bool FAST, bool COMPOSE>
-__global__ __launch_bounds__(kBlock) void k_mlp_bwd(const void* __restrict__ x, uint32_t M, uint32_t n_in, uint32_t x_stride,
-                                                    const _Float16* __restrict__ weights, uint32_t in_cols,
-                                                    const float* __restrict__ grad_out, uint32_t n_out, uint32_t go_stride, float grad_scale,
-                                                    float* __restrict__ grad_x, uint32_t gx_stride, float* __restrict__ grad_w, int vec_ok,
-                                                    uint32_t gx_col0, int gx_accumulate, int go_vec, XPrefix pre, GoCompose gc) {
+__global__ __launch_bounds__(kBlock) void k_mlp_bwd(BWD_PARAMS) {
+    const BwdArgs args = {BWD_ARGS};
     using FR = BwdFrags<IN_STEPS, N_HIDDEN>;
     constexpr int IN_TILES = FR::IN_TILES;
     __shared__ half8_t s_frag[FR::kCount * kWave];
@@ -169,7 +315,7 @@ __global__ __launch_bounds__(kBlock) void k_mlp_bwd(const void* __restrict__ x, 
     for (int i = 0; i < kHidTiles; ++i) dw1[i] = float4_t{0, 0, 0, 0};
     dwo = float4_t{0, 0, 0, 0};
 
-    const uint32_t n_tiles = (M + 15) / 16;
+    const uint32_t n_tiles = (args.M + 15) / 16;
     const uint32_t tiles_per_iter = gridDim.x * kWavesPerBlock;
     const uint32_t n_iters = (n_tiles + tiles_per_iter - 1) / tiles_per_iter;
     const int col = 16 * w + c;  // this lane's sample column in the staging arrays
@@ -179,41 +325,13 @@ __global__ __launch_bounds__(kBlock) void k_mlp_bwd(const void* __restrict__ x, 
         return *reinterpret_cast<const half8_t*>(arr + (size_t)(row0 + c) * kPitch + 32 * ks + 8 * g);
     };
 
-    // operands of one iteration: the x fragments and the raw output gradients of this lane's sample.  Those of iteration
-    // it + 1 are requested before iteration it computes (two resident workgroups per CU cannot hide a dependent global
-    // load per iteration by themselves).
+    // The operands of iteration it + 1 are requested before iteration it computes (two resident workgroups per CU cannot hide a
+    // dependent global load per iteration by themselves).
     XTail tail;
     if constexpr (FAST) tail.init(32 * (IN_STEPS - 1) + 8 * g, (int)n_in, (int)in_cols);
-    struct Operands {
-        half8_t xf[IN_STEPS];
-        float go[8];
-        float ex[COMPOSE ? 12 : 1];  // COMPOSE: the second head's row and the four scalars, as loaded
-        uint32_t m;
-        bool valid;
-    };
+    using Operands = BwdOperands<IN_STEPS, COMPOSE>;
     auto fetch = [&](uint32_t it, Operands& op) __attribute__((always_inline)) {
-        const uint32_t tile = (it * gridDim.x + blockIdx.x) * kWavesPerBlock + (uint32_t)w;
-        op.m = tile * 16 + (uint32_t)c;
-        op.valid = tile < n_tiles && op.m < M;
-        const size_t row = op.valid ? op.m : (M - 1);
-        const uint32_t tile_u = __builtin_amdgcn_readfirstlane(tile);
-        const _Float16* prow = pre.a ? pre.row_of((tile_u < n_tiles && tile_u * 16u < M) ? tile_u * 16u : M - 1u) : nullptr;
-        issue_x_row<IN_STEPS, X_F16, FAST>(op.xf, x, row, x_stride, g, (int)n_in, (int)in_cols, vec_ok != 0, tail, prow, pre.split);
-        const float* go_row = grad_out + row * go_stride;
-        if constexpr (COMPOSE) {  // density network: the logit gradient composed from (grad_sigma, sigma, geometry gradient rows)
-            gc.issue(row, g, op.go, op.ex);
-        } else if (go_vec) {  // 16 outputs, 16-byte aligned rows: two 16-byte loads for the lanes that hold outputs (g < 2)
-            const float4* p = reinterpret_cast<const float4*>(go_row) + 2 * (g & 1);
-            const float4 a = p[0], b = p[1];
-            op.go[0] = a.x; op.go[1] = a.y; op.go[2] = a.z; op.go[3] = a.w;
-            op.go[4] = b.x; op.go[5] = b.y; op.go[6] = b.z; op.go[7] = b.w;
-        } else {  // element loads with the column clamped into the row, issued back to back
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const uint32_t o = 8 * (g & 1) + j;
-                op.go[j] = go_row[o < n_out ? o : n_out - 1];
-            }
-        }
+        fetch_operands<IN_STEPS, X_F16, FAST, COMPOSE>(args, tail, (it * gridDim.x + blockIdx.x) * kWavesPerBlock + (uint32_t)w, n_tiles, g, c, op);
     };
     // the wide variants have no registers to spare for a second set of operands at two waves per SIMD: they fetch in place
     constexpr bool kPrefetch = FAST || IN_STEPS <= 2;
@@ -226,32 +344,15 @@ __global__ __launch_bounds__(kBlock) void k_mlp_bwd(const void* __restrict__ x, 
         if (kPrefetch && it + 1 < n_iters) fetch(it + 1, next);
         const uint32_t m = cur.m;
         const bool valid = cur.valid;
-        half8_t xf[IN_STEPS];
+        half8_t xf[1][IN_STEPS];  // (one-tile arrays: forward_recompute's NT = 1)
 #pragma unroll
-        for (int s = 0; s < IN_STEPS; ++s) xf[s] = cur.xf[s];
-        if constexpr (FAST) xf[IN_STEPS - 1] = tail.apply(xf[IN_STEPS - 1]);
+        for (int s = 0; s < IN_STEPS; ++s) xf[0][s] = cur.xf[s];
+        if constexpr (FAST) xf[0][IN_STEPS - 1] = tail.apply(xf[0][IN_STEPS - 1]);
         // ---- forward recompute
-        float4_t acc[kHidTiles];
-#pragma unroll
-        for (int t = 0; t < kHidTiles; ++t) {
-            float4_t a = {0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < IN_STEPS; ++s) a = mfma16(frag[(FR::kF0 + t * IN_STEPS + s) * kWave], xf[s], a);
-            acc[t] = a;
-        }
-        half8_t h0[kHidSteps], h1[kHidSteps];
-        pack_hidden(acc, h0);
-        if constexpr (N_HIDDEN == 2) {
-#pragma unroll
-            for (int t = 0; t < kHidTiles; ++t) {
-                float4_t a = {0, 0, 0, 0};
-#pragma unroll
-                for (int s = 0; s < kHidSteps; ++s) a = mfma16(frag[(FR::kF1 + 2 * t + s) * kWave], h0[s], a);
-                acc[t] = a;
-            }
-            pack_hidden(acc, h1);
-        }
-        const half8_t(&h_last)[kHidSteps] = N_HIDDEN == 2 ? h1 : h0;
+        half8_t h0a[1][kHidSteps], h1a[1][kHidSteps];
+        forward_recompute<IN_STEPS, N_HIDDEN, 1>(frag, xf, h0a, h1a);
+        const half8_t(&h0)[kHidSteps] = h0a[0];
+        const half8_t(&h_last)[kHidSteps] = N_HIDDEN == 2 ? h1a[0] : h0a[0];
         // ---- output gradient -> B fragment (natural order of the 16 outputs, zero beyond n_out, scaled)
         half8_t go;
         float gov[8];
@@ -293,46 +394,7 @@ __global__ __launch_bounds__(kBlock) void k_mlp_bwd(const void* __restrict__ x, 
                     float4_t a = {0, 0, 0, 0};
 #pragma unroll
                     for (int s = 0; s < kHidSteps; ++s) a = mfma16(frag[(FR::kB0 + 2 * ti + s) * kWave], gp0[s], a);
-                    const uint32_t k0 = 16 * ti + 4 * g;
-                    float* row_x = grad_x + (size_t)m * gx_stride;
-                    if constexpr (FAST) {  // 16-byte aligned window: this lane's four columns as one store (the last group may
-                                           // reach into the row's alignment padding)
-                        const uint32_t blk = ((uint32_t)gx_accumulate >> 8) & 0xFFu;  // 0: rows; 2 / 4: column blocks (below)
-                        if (blk == 0u) {
-                            if (valid && k0 >= gx_col0 && k0 < n_in) {
-                                float4_t* p = reinterpret_cast<float4_t*>(row_x + (k0 - gx_col0));
-                                float4_t v = a * inv_scale;
-                                if (gx_accumulate & 1) v += *p;
-                                *p = v;
-                            }
-                        } else if (valid && k0 < n_in) {
-                            // block-major dX: [n_in / blk][M][blk] -- the gradient of a hash grid's features, level by level, so that the
-                            // table scatter reads a level's column as one stream (a row-major [M, 32] costs it a 128-byte line per 8 bytes
-                            // and level: hashgrid.hip).  16 consecutive samples of a level are 16 * blk * 4 contiguous bytes.
-                            float4_t v = a * inv_scale;
-                            if (blk == 4u) {
-                                float4_t* p = reinterpret_cast<float4_t*>(grad_x + ((size_t)(k0 >> 2) * M + m) * 4);
-                                if (gx_accumulate & 1) v += *p;
-                                *p = v;
-                            } else {
-                                float2* p0 = reinterpret_cast<float2*>(grad_x + ((size_t)(k0 >> 1) * M + m) * 2);
-                                float2* p1 = reinterpret_cast<float2*>(grad_x + ((size_t)((k0 >> 1) + 1u) * M + m) * 2);
-                                float2 v0 = make_float2(v[0], v[1]), v1 = make_float2(v[2], v[3]);
-                                if (gx_accumulate & 1) { v0.x += p0->x; v0.y += p0->y; v1.x += p1->x; v1.y += p1->y; }
-                                *p0 = v0;
-                                *p1 = v1;
-                            }
-                        }
-                    } else if (valid) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const uint32_t k = k0 + r;
-                            if (k < n_in && k >= gx_col0) {
-                                const float v = a[r] * inv_scale;
-                                row_x[k - gx_col0] = (gx_accumulate & 1) ? row_x[k - gx_col0] + v : v;
-                            }
-                        }
-                    }
+                    store_dx<FAST>(args, a, m, valid, 16 * ti + 4 * g, inv_scale);
                 }
             }
         }
@@ -376,7 +438,7 @@ __global__ __launch_bounds__(kBlock) void k_mlp_bwd(const void* __restrict__ x, 
 #pragma unroll
         for (int s = 0; s < IN_STEPS; ++s)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) s_a[(size_t)(32 * s + 8 * g + j) * kPitch + col] = xf[s][j];
+            for (int j = 0; j < 8; ++j) s_a[(size_t)(32 * s + 8 * g + j) * kPitch + col] = xf[0][s][j];
         lds_barrier();
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -387,15 +449,15 @@ __global__ __launch_bounds__(kBlock) void k_mlp_bwd(const void* __restrict__ x, 
         lds_barrier();
     }
     // ---- flush: accumulator element (row 4g + r, column c) of tile (to, tk)
-    float* gw0 = grad_w;
-    float* gw1 = grad_w + (size_t)kHidden * in_cols;
+    float* gw0 = args.grad_w;
+    float* gw1 = args.grad_w + (size_t)kHidden * args.in_cols;
     float* gwo = gw1 + (N_HIDDEN == 2 ? kHidden * kHidden : 0);
 #pragma unroll
     for (int tk = 0; tk < IN_TILES; ++tk) {
         const uint32_t k = 16 * tk + c;
-        if (k < in_cols) {
+        if (k < args.in_cols) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) atomicAdd(gw0 + (size_t)(16 * w + 4 * g + r) * in_cols + k, dw0[tk][r] * inv_scale);
+            for (int r = 0; r < 4; ++r) atomicAdd(gw0 + (size_t)(16 * w + 4 * g + r) * args.in_cols + k, dw0[tk][r] * inv_scale);
         }
     }
     if constexpr (N_HIDDEN == 2) {
@@ -435,10 +497,8 @@ __device__ __forceinline__ void mfma16_agpr(float4_t& acc, half8_t a, half8_t b)
 }
 
 template <int IN_STEPS, int N_HIDDEN, bool X_F16, bool FAST, bool COMPOSE>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_mlp_bwd_wave(
-    const void* __restrict__ x, uint32_t M, uint32_t n_in, uint32_t x_stride, const _Float16* __restrict__ weights, uint32_t in_cols,
-    const float* __restrict__ grad_out, uint32_t n_out, uint32_t go_stride, float grad_scale, float* __restrict__ grad_x, uint32_t gx_stride,
-    float* __restrict__ grad_w, int vec_ok, uint32_t gx_col0, int gx_accumulate, int go_vec, XPrefix pre, GoCompose gc) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_mlp_bwd_wave(BWD_PARAMS) {
+    const BwdArgs args = {BWD_ARGS};
     using FR = BwdFrags<IN_STEPS, N_HIDDEN>;
     constexpr int IN_TILES = FR::IN_TILES;
     constexpr int kDwMax = kHidden * 32 * IN_STEPS + (N_HIDDEN == 2 ? kHidden * kHidden : 0) + 16 * kHidden;
@@ -462,6 +522,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
         }
     // 16 x 16 block of fragment v, transposed: lane (unit c, g) gets the samples 4g .. 4g + 3
     auto tr = [&](half8_t v, half8_t sel) { return mfma16(v, sel, float4_t{0, 0, 0, 0}); };
+    // the same block of both tiles of the pair: one K = 32 dW operand
+    auto tr2 = [&](half8_t v0, half8_t v1, half8_t sel) { return plain_pack(tr(v0, sel), tr(v1, sel)); };
 
     float4_t dw0[kHidTiles][IN_TILES], dw1[kHidTiles][kHidTiles], dwo[kHidTiles];
 #pragma unroll
@@ -473,52 +535,28 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
         dwo[to] = float4_t{0, 0, 0, 0};
     }
 
-    const uint32_t n_tiles = (M + 15) / 16;
+    const uint32_t n_tiles = (args.M + 15) / 16;
     const uint32_t n_pairs = (n_tiles + 1) / 2;
     const uint32_t pairs_per_iter = gridDim.x * kWavesPerBlock;
     const uint32_t n_iters = (n_pairs + pairs_per_iter - 1) / pairs_per_iter;
 
     XTail tail;
     if constexpr (FAST) tail.init(32 * (IN_STEPS - 1) + 8 * g, (int)n_in, (int)in_cols);
-    struct Operands {
-        half8_t xf[IN_STEPS];
-        float go[8];
-        float ex[COMPOSE ? 12 : 1];  // COMPOSE: the second head's row and the four scalars, as loaded
-        uint32_t m;
-        bool valid;
-    };
-    auto fetch = [&](uint32_t it, int u, Operands& op) __attribute__((always_inline)) {
-        const uint32_t tile = 2u * ((it * gridDim.x + blockIdx.x) * kWavesPerBlock + (uint32_t)w) + (uint32_t)u;
-        op.m = tile * 16 + (uint32_t)c;
-        op.valid = tile < n_tiles && op.m < M;
-        const size_t row = op.valid ? op.m : (M - 1);
-        const uint32_t tile_u = __builtin_amdgcn_readfirstlane(tile);
-        const _Float16* prow = pre.a ? pre.row_of((tile_u < n_tiles && tile_u * 16u < M) ? tile_u * 16u : M - 1u) : nullptr;
-        issue_x_row<IN_STEPS, X_F16, FAST>(op.xf, x, row, x_stride, g, (int)n_in, (int)in_cols, vec_ok != 0, tail, prow, pre.split);
-        const float* go_row = grad_out + row * go_stride;
-        if constexpr (COMPOSE) {
-            gc.issue(row, g, op.go, op.ex);
-        } else if (go_vec) {
-            const float4* p = reinterpret_cast<const float4*>(go_row) + 2 * (g & 1);
-            const float4 a = p[0], b = p[1];
-            op.go[0] = a.x; op.go[1] = a.y; op.go[2] = a.z; op.go[3] = a.w;
-            op.go[4] = b.x; op.go[5] = b.y; op.go[6] = b.z; op.go[7] = b.w;
-        } else {
+    using Operands = BwdOperands<IN_STEPS, COMPOSE>;
+    auto fetch = [&](uint32_t it, Operands (&op)[2]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const uint32_t o = 8 * (g & 1) + j;
-                op.go[j] = go_row[o < n_out ? o : n_out - 1];
-            }
-        }
+        for (int u = 0; u < 2; ++u)
+            fetch_operands<IN_STEPS, X_F16, FAST, COMPOSE>(args, tail, 2u * ((it * gridDim.x + blockIdx.x) * kWavesPerBlock + (uint32_t)w) + (uint32_t)u,
+                                                           n_tiles, g, c, op[u]);
     };
     constexpr bool kPrefetch = FAST && X_F16;  // the next pair's operands are requested before this pair is worked on
     Operands next[2];
-    if (kPrefetch && n_iters) { fetch(0, 0, next[0]); fetch(0, 1, next[1]); }
+    if (kPrefetch && n_iters) fetch(0, next);
 
     for (uint32_t it = 0; it < n_iters; ++it) {
-        if (!kPrefetch) { fetch(it, 0, next[0]); fetch(it, 1, next[1]); }
-        half8_t xf[2][IN_STEPS];
-        float gor[2][8];
+        if (!kPrefetch) fetch(it, next);
+        half8_t xf[2][IN_STEPS], go[2];
+        float gov[2][8];
         uint32_t m[2];
         bool valid[2];
 #pragma unroll
@@ -526,51 +564,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
 #pragma unroll
             for (int s = 0; s < IN_STEPS; ++s) xf[u][s] = next[u].xf[s];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) gor[u][j] = next[u].go[j];
-            if constexpr (COMPOSE) gc.compose(g, next[u].go, next[u].ex, gor[u]);
+            for (int j = 0; j < 8; ++j) gov[u][j] = next[u].go[j];
+            if constexpr (COMPOSE) gc.compose(g, next[u].go, next[u].ex, gov[u]);
             m[u] = next[u].m;
             valid[u] = next[u].valid;
             if constexpr (FAST) xf[u][IN_STEPS - 1] = tail.apply(xf[u][IN_STEPS - 1]);
         }
-        if (kPrefetch && it + 1 < n_iters) { fetch(it + 1, 0, next[0]); fetch(it + 1, 1, next[1]); }
+        if (kPrefetch && it + 1 < n_iters) fetch(it + 1, next);
         // ---- forward recompute (sample on the lane)
-        half8_t h0[2][kHidSteps], h1[2][kHidSteps];
-        {
-            float4_t acc[2][kHidTiles];
-#pragma unroll
-            for (int t = 0; t < kHidTiles; ++t)
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    float4_t a = {0, 0, 0, 0};
-#pragma unroll
-                    for (int s = 0; s < IN_STEPS; ++s) a = mfma16(frag[(FR::kF0 + t * IN_STEPS + s) * kWave], xf[u][s], a);
-                    acc[u][t] = a;
-                }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) pack_hidden(acc[u], h0[u]);
-            if constexpr (N_HIDDEN == 2) {
-#pragma unroll
-                for (int t = 0; t < kHidTiles; ++t)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        float4_t a = {0, 0, 0, 0};
-#pragma unroll
-                        for (int s = 0; s < kHidSteps; ++s) a = mfma16(frag[(FR::kF1 + 2 * t + s) * kWave], h0[u][s], a);
-                        acc[u][t] = a;
-                    }
-#pragma unroll
-                for (int u = 0; u < 2; ++u) pack_hidden(acc[u], h1[u]);
-            }
-        }
+        half8_t h0[2][kHidSteps], h1[2][kHidSteps], gp_last[2][kHidSteps], gp0[2][kHidSteps];
+        forward_recompute<IN_STEPS, N_HIDDEN, 2>(frag, xf, h0, h1);
         const half8_t(&h_last)[2][kHidSteps] = N_HIDDEN == 2 ? h1 : h0;
         // ---- output gradient -> B fragment (natural order of the 16 outputs, zero beyond n_out, scaled)
-        half8_t go[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) go[u][j] = (valid[u] && g < 2 && 8u * g + j < n_out) ? (_Float16)(gor[u][j] * grad_scale) : (_Float16)0.0f;
+            for (int j = 0; j < 8; ++j) go[u][j] = (valid[u] && g < 2 && 8u * g + j < n_out) ? (_Float16)(gov[u][j] * grad_scale) : (_Float16)0.0f;
         // ---- output layer: data path, then its weight gradient  dW_out[o][k] = sum_s dOut[s][o] h_last[s][k]
-        half8_t gp_last[2][kHidSteps], gp0[2][kHidSteps];
         {
             float4_t gacc[2][kHidTiles];
 #pragma unroll
@@ -585,10 +595,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
             }
         }
         {
-            const half8_t go_n = plain_pack(tr(go[0], Q[0]), tr(go[1], Q[0]));
+            const half8_t go_n = tr2(go[0], go[1], Q[0]);
 #pragma unroll
-            for (int tk = 0; tk < kHidTiles; ++tk)
-                mfma16_agpr(dwo[tk], go_n, plain_pack(tr(h_last[0][tk >> 1], P[tk & 1]), tr(h_last[1][tk >> 1], P[tk & 1])));
+            for (int tk = 0; tk < kHidTiles; ++tk) mfma16_agpr(dwo[tk], go_n, tr2(h_last[0][tk >> 1], h_last[1][tk >> 1], P[tk & 1]));
         }
         // ---- hidden layer: dP0 and  dW1[o][k] = sum_s dP1[s][o] h0[s][k]
         if constexpr (N_HIDDEN == 2) {
@@ -610,10 +619,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
             }
             half8_t h0n[kHidTiles];
 #pragma unroll
-            for (int tk = 0; tk < kHidTiles; ++tk) h0n[tk] = plain_pack(tr(h0[0][tk >> 1], P[tk & 1]), tr(h0[1][tk >> 1], P[tk & 1]));
+            for (int tk = 0; tk < kHidTiles; ++tk) h0n[tk] = tr2(h0[0][tk >> 1], h0[1][tk >> 1], P[tk & 1]);
 #pragma unroll
             for (int to = 0; to < kHidTiles; ++to) {
-                const half8_t gn = plain_pack(tr(gp_last[0][to >> 1], P[to & 1]), tr(gp_last[1][to >> 1], P[to & 1]));
+                const half8_t gn = tr2(gp_last[0][to >> 1], gp_last[1][to >> 1], P[to & 1]);
 #pragma unroll
                 for (int tk = 0; tk < kHidTiles; ++tk) mfma16_agpr(dw1[to][tk], gn, h0n[tk]);
             }
@@ -633,42 +642,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
                         float4_t a = {0, 0, 0, 0};
 #pragma unroll
                         for (int s = 0; s < kHidSteps; ++s) a = mfma16(frag[(FR::kB0 + 2 * ti + s) * kWave], gp0[u][s], a);
-                        const uint32_t k0 = 16 * ti + 4 * g;
-                        float* row_x = grad_x + (size_t)m[u] * gx_stride;
-                        if constexpr (FAST) {
-                            const uint32_t blk = ((uint32_t)gx_accumulate >> 8) & 0xFFu;  // 0: rows; 2 / 4: column blocks
-                            if (blk == 0u) {
-                                if (valid[u] && k0 >= gx_col0 && k0 < n_in) {
-                                    float4_t* p = reinterpret_cast<float4_t*>(row_x + (k0 - gx_col0));
-                                    float4_t v = a * inv_scale;
-                                    if (gx_accumulate & 1) v += *p;
-                                    *p = v;
-                                }
-                            } else if (valid[u] && k0 < n_in) {
-                                float4_t v = a * inv_scale;
-                                if (blk == 4u) {
-                                    float4_t* p = reinterpret_cast<float4_t*>(grad_x + ((size_t)(k0 >> 2) * M + m[u]) * 4);
-                                    if (gx_accumulate & 1) v += *p;
-                                    *p = v;
-                                } else {
-                                    float2* p0 = reinterpret_cast<float2*>(grad_x + ((size_t)(k0 >> 1) * M + m[u]) * 2);
-                                    float2* p1 = reinterpret_cast<float2*>(grad_x + ((size_t)((k0 >> 1) + 1u) * M + m[u]) * 2);
-                                    float2 v0 = make_float2(v[0], v[1]), v1 = make_float2(v[2], v[3]);
-                                    if (gx_accumulate & 1) { v0.x += p0->x; v0.y += p0->y; v1.x += p1->x; v1.y += p1->y; }
-                                    *p0 = v0;
-                                    *p1 = v1;
-                                }
-                            }
-                        } else if (valid[u]) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const uint32_t k = k0 + r;
-                                if (k < n_in && k >= gx_col0) {
-                                    const float v = a[r] * inv_scale;
-                                    row_x[k - gx_col0] = (gx_accumulate & 1) ? row_x[k - gx_col0] + v : v;
-                                }
-                            }
-                        }
+                        store_dx<FAST>(args, a, m[u], valid[u], 16 * ti + 4 * g, inv_scale);
                     }
                 }
             }
@@ -677,10 +651,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
         {
             half8_t gn[kHidTiles];
 #pragma unroll
-            for (int to = 0; to < kHidTiles; ++to) gn[to] = plain_pack(tr(gp0[0][to >> 1], P[to & 1]), tr(gp0[1][to >> 1], P[to & 1]));
+            for (int to = 0; to < kHidTiles; ++to) gn[to] = tr2(gp0[0][to >> 1], gp0[1][to >> 1], P[to & 1]);
 #pragma unroll
             for (int ti = 0; ti < IN_TILES; ++ti) {
-                const half8_t xn = plain_pack(tr(xf[0][ti >> 1], Q[ti & 1]), tr(xf[1][ti >> 1], Q[ti & 1]));
+                const half8_t xn = tr2(xf[0][ti >> 1], xf[1][ti >> 1], Q[ti & 1]);
 #pragma unroll
                 for (int to = 0; to < kHidTiles; ++to) mfma16_agpr(dw0[to][ti], gn[to], xn);
             }
@@ -716,7 +690,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
     }
     for (uint32_t i = threadIdx.x; i < n_w; i += kBlock) {
         const float v = s_dw[i] * inv_scale;
-        if (v != 0.0f) atomicAdd(grad_w + i, v);
+        if (v != 0.0f) atomicAdd(args.grad_w + i, v);
     }
 }
 }  // namespace
@@ -727,16 +701,10 @@ static int mlp_bwd_impl(const void* x, int x_is_f16, uint32_t M, uint32_t n_in, 
                         uint32_t gx_col0, int gx_accumulate, XPrefix pre, GoCompose gc, hipStream_t stream) {
     if (M == 0) return NVSF_OK;
     REQUIRE(x && weights_f16 && (grad_out || gc.sigma) && grad_weights_f32);
-    REQUIRE(n_in >= 1 && n_in <= in_cols && in_cols % 16 == 0 && x_stride >= n_in - pre.split);
     REQUIRE(n_out >= 1 && n_out <= 16 && go_stride >= n_out && grad_scale > 0.0f);
     const uint32_t gx_blk = ((uint32_t)gx_accumulate >> 8) & 0xFFu;
     REQUIRE(!grad_x || gx_blk || (gx_col0 < n_in && gx_stride >= n_in - gx_col0));
     REQUIRE(!gx_blk || (grad_x && (gx_blk == 2u || gx_blk == 4u) && gx_col0 == 0 && n_in % 4 == 0 && (reinterpret_cast<uintptr_t>(grad_x) & 15u) == 0));
-    REQUIRE((reinterpret_cast<uintptr_t>(weights_f16) & 15u) == 0);
-    if (hidden != (uint32_t)kHidden || out_cols != 16 || n_hidden < 1 || n_hidden > 2 || in_cols > 128) return NVSF_ERR_UNSUPPORTED;
-    const int in_steps = (int)((in_cols + 31) / 32);
-    const size_t esz = x_is_f16 ? 2 : 4;
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(x) & 15u) == 0) && ((x_stride * esz) % 16 == 0);
     const int go_vec = n_out == 16 && go_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0;
     const uint32_t n_tiles = (M + 15) / 16;
     uint32_t blocks = (n_tiles + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -754,12 +722,15 @@ static int mlp_bwd_impl(const void* x, int x_is_f16, uint32_t M, uint32_t n_in, 
     // enough for the last group of four)
     const bool gx_vec = !grad_x || gx_blk || (gx_col0 % 4 == 0 && gx_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(grad_x) & 15u) == 0 &&
                                               (n_in - gx_col0 + 3u) / 4u * 4u <= gx_stride);
-    const bool fast = x_rows_fast(n_in - pre.split, x_stride, vec_ok) && gx_vec;
+    // rows.fast = the x rows allow 16-byte loads AND gx_vec (the dX destination allows 16-byte stores); the shared-prefix rows
+    // (mlp_device.h: XPrefix) are checked there too
+    XRowsPlan rows;
+    const int rc = plan_x_rows(x, x_is_f16, n_in, x_stride, weights_f16, in_cols, pre, hidden == (uint32_t)kHidden && out_cols == 16 && n_hidden >= 1 && n_hidden <= 2,
+                               gx_vec, rows);
+    if (rc != NVSF_OK) return rc;
+    const int in_steps = rows.in_steps, vec_ok = rows.vec_ok;
+    const bool fast = rows.fast;
     REQUIRE(!gx_blk || fast);  // column blocks: the aligned-row form of the kernel only
-    if (pre.a) {  // shared-prefix rows (mlp_device.h: XPrefix): aligned fp16 only, whole 8-column groups, a tile inside one group
-        REQUIRE(x_is_f16 && fast && pre.split % 8 == 0 && pre.split < n_in && pre.a_stride >= pre.split && pre.a_stride % 8 == 0);
-        REQUIRE(pre.rows_per_a >= 16 && pre.rows_per_a % 16 == 0 && (reinterpret_cast<uintptr_t>(pre.a) & 15u) == 0);
-    }
     // production: the wave-independent kernel, one workgroup per compute unit; nvsf_test_variant("mlp_bwd", 1): the LDS-staged kernel
     // The 32-wide one-hidden-layer network (the density MLP: 256 B of rows per sample for 18 432 FLOP = 72 FLOP/B, far below the ridge of
     // 312) is bound by its row traffic, which one wave per SIMD cannot keep in flight (measured 0.30 ms against 0.19 ms at 3.1 M rows):
@@ -771,16 +742,12 @@ static int mlp_bwd_impl(const void* x, int x_is_f16, uint32_t M, uint32_t n_in, 
         blocks = (n_pairs + kWavesPerBlock - 1) / kWavesPerBlock;
         if (blocks > cus) blocks = cus;
     }
-#define LAUNCH(S, H, XF, FA, CO)                                                                                                           \
-    do {                                                                                                                                   \
-        if (staged)                                                                                                                        \
-            hipLaunchKernelGGL((k_mlp_bwd<S, H, XF, FA, CO>), dim3(blocks), dim3(kBlock), 0, stream, x, M, n_in, x_stride, w, in_cols,    \
-                               grad_out, n_out, go_stride, grad_scale, grad_x, gx_stride, grad_weights_f32, vec_ok, gx_col0,              \
-                               gx_accumulate, go_vec, pre, gc);                                                                            \
-        else                                                                                                                               \
-            hipLaunchKernelGGL((k_mlp_bwd_wave<S, H, XF, FA, CO>), dim3(blocks), dim3(kBlock), 0, stream, x, M, n_in, x_stride, w,        \
-                               in_cols, grad_out, n_out, go_stride, grad_scale, grad_x, gx_stride, grad_weights_f32, vec_ok, gx_col0,     \
-                               gx_accumulate, go_vec, pre, gc);                                                                            \
+    const _Float16* weights = w;
+    float* grad_w = grad_weights_f32;
+#define LAUNCH(S, H, XF, FA, CO)                                                                                      \
+    do {                                                                                                              \
+        void (*kernel)(BWD_PARAMS) = staged ? k_mlp_bwd<S, H, XF, FA, CO> : k_mlp_bwd_wave<S, H, XF, FA, CO>;         \
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, stream, BWD_ARGS);                                  \
     } while (0)
 // the composed operand fetch is built for the density networks' shape only: ONE hidden layer (sigma_net, network_dynamic.py:125-135)
 #define BY_C1(S, XF, FA) do { if (gc.sigma) LAUNCH(S, 1, XF, FA, true); else LAUNCH(S, 1, XF, FA, false); } while (0)

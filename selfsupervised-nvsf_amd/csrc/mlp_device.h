@@ -138,6 +138,28 @@ struct XPrefix {
     }
 };
 
+// Host side: what nvsf_mlp_fwd* and nvsf_mlp_bwd* check and derive alike from their x rows, weights and shared prefix.  `shape_ok`: the
+// caller's own limits on hidden / n_hidden / out_cols; `dst_fast`: whether the caller's destination allows the FAST form of its kernel.
+struct XRowsPlan {
+    int in_steps, vec_ok;
+    bool fast;
+};
+static inline int plan_x_rows(const void* x, int x_is_f16, uint32_t n_in, uint32_t x_stride, const void* weights_f16, uint32_t in_cols,
+                              const XPrefix& pre, bool shape_ok, bool dst_fast, XRowsPlan& p) {
+    REQUIRE(n_in >= 1 && n_in <= in_cols && in_cols % 16 == 0 && x_stride >= n_in - pre.split);
+    REQUIRE((reinterpret_cast<uintptr_t>(weights_f16) & 15u) == 0);
+    if (!shape_ok || in_cols > 128) return NVSF_ERR_UNSUPPORTED;
+    p.in_steps = (int)((in_cols + 31) / 32);
+    const size_t esz = x_is_f16 ? 2 : 4;
+    p.vec_ok = ((reinterpret_cast<uintptr_t>(x) & 15u) == 0) && ((x_stride * esz) % 16 == 0);
+    p.fast = x_rows_fast(n_in - pre.split, x_stride, p.vec_ok) && dst_fast;
+    if (pre.a) {  // shared-prefix rows: aligned fp16 only, whole 8-column groups on either side, a tile inside one group
+        REQUIRE(x_is_f16 && p.fast && pre.split % 8 == 0 && pre.split < n_in && pre.a_stride >= pre.split && pre.a_stride % 8 == 0);
+        REQUIRE(pre.rows_per_a >= 16 && pre.rows_per_a % 16 == 0 && (reinterpret_cast<uintptr_t>(pre.a) & 15u) == 0);
+    }
+    return NVSF_OK;
+}
+
 template <int IN_STEPS, bool X_F16, bool FAST>
 __device__ __forceinline__ void issue_x_row(half8_t (&xf)[IN_STEPS], const void* __restrict__ x, size_t row, uint32_t x_stride, int g, int n_in,
                                             int in_cols, bool vec_ok, const XTail& tail, const _Float16* __restrict__ prefix_row = nullptr,

@@ -342,49 +342,38 @@ def mlp_backward(x, weights_f16, spec, grad_out, need_grad_x=True, grad_scale=ML
     M = x.shape[0]
     grad_w = torch.zeros(spec.n_params, dtype=torch.float32, device=x.device)
     mode = (1 if accumulate else 0) | (int(grad_x_blocks) << 8)
-    if density_grad is not None:
-        g_sigma, sigma, geo_a, geo_b, n_geo, lo, hi = density_grad
-        assert prefix is None and spec.n_out == 1 + n_geo
-        if grad_x_blocks:
-            assert need_grad_x and gx_col0 == 0 and spec.n_in % grad_x_blocks == 0
-            if grad_x is None:
-                grad_x = torch.empty(spec.n_in // grad_x_blocks, M, grad_x_blocks, dtype=torch.float32, device=x.device)
-            gx_ptr, gx_stride = _hip.ptr(grad_x), grad_x_blocks
-        else:
-            if grad_x is None and need_grad_x:
-                n_gx = spec.n_in - gx_col0
-                grad_x = torch.empty(M, (n_gx + 3) // 4 * 4, dtype=torch.float32, device=x.device)[:, :n_gx]
-            gx_ptr, gx_stride = (None, 0) if grad_x is None else (_hip.ptr_rows(grad_x), grad_x.stride(0))
-        _hip.call("nvsf_mlp_bwd_density", _hip.ptr_rows(x), 1 if x.dtype == torch.float16 else 0, M, spec.n_in, x.stride(0), _hip.ptr(weights_f16),
-                  spec.in_cols, spec.hidden, spec.n_hidden, spec.out_cols, None if g_sigma is None else _hip.ptr(g_sigma), _hip.ptr(sigma),
-                  _hip.ptr_rows(geo_a), None if geo_b is None else _hip.ptr_rows(geo_b), geo_a.stride(0), n_geo, lo, hi, float(grad_scale),
-                  gx_ptr, gx_stride, _hip.ptr(grad_w), int(gx_col0), mode)
-        return grad_x, grad_w
-    grad_out = grad_out.float()
-    if grad_out.dim() != 2 or (grad_out.shape[1] > 1 and grad_out.stride(1) != 1):
-        grad_out = grad_out.contiguous()
+    # the dX buffer and its (pointer, stride), decided once for the three entry points
     if grad_x_blocks:  # dL/dx as column blocks [n_in / B, M, B] (the gradient of a hash grid's features, level by level)
         assert need_grad_x and gx_col0 == 0 and spec.n_in % grad_x_blocks == 0 and prefix is None
         if grad_x is None:
             grad_x = torch.empty(spec.n_in // grad_x_blocks, M, grad_x_blocks, dtype=torch.float32, device=x.device)
-        _hip.call("nvsf_mlp_bwd", _hip.ptr_rows(x), 1 if x.dtype == torch.float16 else 0, M, spec.n_in, x.stride(0), _hip.ptr(weights_f16),
-                  spec.in_cols, spec.hidden, spec.n_hidden, spec.out_cols, _hip.ptr_rows(grad_out), grad_out.shape[1], grad_out.stride(0),
-                  float(grad_scale), _hip.ptr(grad_x), grad_x_blocks, _hip.ptr(grad_w), 0, mode)
-        return grad_x, grad_w
-    if grad_x is None and need_grad_x:
-        n_gx = spec.n_in - gx_col0  # rows padded to four floats: the kernel then stores 16 bytes per lane
-        grad_x = torch.empty(M, (n_gx + 3) // 4 * 4, dtype=torch.float32, device=x.device)[:, :n_gx]
-    if prefix is not None:  # rows with a shared prefix (see mlp_forward)
-        rows, per, n_cols = prefix
-        _hip.call("nvsf_mlp_bwd_prefix", _hip.ptr_rows(rows), rows.stride(0), int(per), int(n_cols), _hip.ptr_rows(x), M, spec.n_in, x.stride(0),
-                  _hip.ptr(weights_f16), spec.in_cols, spec.hidden, spec.n_hidden, spec.out_cols, _hip.ptr_rows(grad_out), grad_out.shape[1],
-                  grad_out.stride(0), float(grad_scale), None if grad_x is None else _hip.ptr_rows(grad_x), 0 if grad_x is None else grad_x.stride(0),
-                  _hip.ptr(grad_w), int(gx_col0), 1 if accumulate else 0)
-        return grad_x, grad_w
-    _hip.call("nvsf_mlp_bwd", _hip.ptr_rows(x), 1 if x.dtype == torch.float16 else 0, M, spec.n_in, x.stride(0), _hip.ptr(weights_f16),
-              spec.in_cols, spec.hidden, spec.n_hidden, spec.out_cols, _hip.ptr_rows(grad_out), grad_out.shape[1], grad_out.stride(0),
-              float(grad_scale), None if grad_x is None else _hip.ptr_rows(grad_x), 0 if grad_x is None else grad_x.stride(0),
-              _hip.ptr(grad_w), int(gx_col0), 1 if accumulate else 0)
+        gx_ptr, gx_stride = _hip.ptr(grad_x), grad_x_blocks
+    else:
+        if grad_x is None and need_grad_x:
+            n_gx = spec.n_in - gx_col0  # rows padded to four floats: the kernel then stores 16 bytes per lane
+            grad_x = torch.empty(M, (n_gx + 3) // 4 * 4, dtype=torch.float32, device=x.device)[:, :n_gx]
+        gx_ptr, gx_stride = (None, 0) if grad_x is None else (_hip.ptr_rows(grad_x), grad_x.stride(0))
+    net = (_hip.ptr(weights_f16), spec.in_cols, spec.hidden, spec.n_hidden, spec.out_cols)
+    rows_x = (M, spec.n_in, x.stride(0))
+    typed_x = (_hip.ptr_rows(x), 1 if x.dtype == torch.float16 else 0) + rows_x  # (x, x_is_f16, M, n_in, x_stride)
+    tail = (float(grad_scale), gx_ptr, gx_stride, _hip.ptr(grad_w), int(gx_col0), mode)
+    if density_grad is not None:
+        g_sigma, sigma, geo_a, geo_b, n_geo, lo, hi = density_grad
+        assert prefix is None and spec.n_out == 1 + n_geo
+        entry, head = "nvsf_mlp_bwd_density", typed_x
+        grad = (None if g_sigma is None else _hip.ptr(g_sigma), _hip.ptr(sigma), _hip.ptr_rows(geo_a),
+                None if geo_b is None else _hip.ptr_rows(geo_b), geo_a.stride(0), n_geo, lo, hi)
+    else:
+        grad_out = grad_out.float()
+        if grad_out.dim() != 2 or (grad_out.shape[1] > 1 and grad_out.stride(1) != 1):
+            grad_out = grad_out.contiguous()
+        grad = (_hip.ptr_rows(grad_out), grad_out.shape[1], grad_out.stride(0))
+        if prefix is not None:  # rows with a shared prefix (see mlp_forward)
+            rows, per, n_cols = prefix
+            entry, head = "nvsf_mlp_bwd_prefix", (_hip.ptr_rows(rows), rows.stride(0), int(per), int(n_cols), _hip.ptr_rows(x)) + rows_x  # fp16 rows only
+        else:
+            entry, head = "nvsf_mlp_bwd", typed_x
+    _hip.call(entry, *head, *net, *grad, *tail)
     return grad_x, grad_w
 
 

@@ -155,6 +155,44 @@ def test_mlp_bwd_column_window_accumulate_and_aligned_rows(dev, n_enc, n_geo, n_
     assert np.array_equal(grad_geo.cpu().numpy(), gx_sum[:, n_enc:].astype(np.float32))
 
 
+@pytest.mark.parametrize("kernel", ["wave", "staged"])
+@pytest.mark.parametrize("n_in,n_out,split", [(87, 1, 72), (31, 3, 16)])
+def test_mlp_bwd_shared_prefix_rows(dev, n_in, n_out, split, kernel, variants):
+    """nvsf_mlp_bwd_prefix straight through ops.mlp_backward(prefix=...): the first `split` input columns once per ray, the rest per
+    sample, dL/dx of the per-sample columns written and then accumulated into an aligned window.  Exact small-integer case against
+    _numpy_backward on the assembled rows.  5 rays x 48 samples = 15 tiles: a ragged last iteration of the staged kernel (4 tiles per
+    workgroup) and a half-empty last pair of the wave kernel."""
+    from nvsf import field_ops as ops
+    variants.set(mlp_bwd=kernel)
+    N, T = 5, 48
+    M = N * T
+    spec = ops.MlpSpec(n_in, n_out, 64, 2)
+    rng = np.random.default_rng(n_in + M)
+    mats = []
+    for a, b in spec.shapes:
+        W = rng.integers(-2, 3, size=(a, b)).astype(np.float32)
+        W[rng.random((a, b)) < 0.8] = 0
+        mats.append(W)
+    pre = rng.integers(-2, 3, size=(N, split)).astype(np.float32)
+    per_sample = rng.integers(-2, 3, size=(M, n_in - split)).astype(np.float32)
+    x = np.concatenate([np.repeat(pre, T, axis=0), per_sample], axis=1)
+    g_out = rng.integers(-2, 3, size=(M, n_out)).astype(np.float32)
+    w16 = _t(np.concatenate([m.reshape(-1) for m in mats]).astype(np.float16), dev)
+    gx_ref, gw_ref, peak = _numpy_backward(x.astype(np.float64), mats, g_out.astype(np.float64), n_in)
+    assert peak <= 2048 and np.abs(gw_ref).max() < 2 ** 24 and 2 * np.abs(gx_ref).max() < 2 ** 24  # fp16 operands / fp32 sums stay exact
+    rows = _t(pre.astype(np.float16), dev)
+    n_own = n_in - split  # 15 columns in 16-wide aligned rows; the padding column holds garbage on purpose
+    buf = torch.full((M, 16), 7.0, dtype=torch.float16, device=dev)
+    buf[:, :n_own] = _t(per_sample, dev).half()
+    window = torch.full((M, 16), -3.0, dtype=torch.float32, device=dev)[:, :n_own]
+    for accumulate in (False, True):
+        got_x, gw = ops.mlp_backward(buf[:, :n_own], w16, spec, _t(g_out, dev), grad_scale=1.0, grad_x=window, gx_col0=split,
+                                     accumulate=accumulate, prefix=(rows, T, split))
+        assert got_x is window
+        assert np.array_equal(gw.cpu().numpy(), gw_ref.astype(np.float32))
+        assert np.array_equal(window.cpu().numpy(), ((2 if accumulate else 1) * gx_ref[:, split:]).astype(np.float32))
+
+
 @pytest.mark.parametrize("lidar", [True, False])
 def test_heads_fn_equals_the_cat_formulation(dev, lidar):
     """ops.heads (aligned shared buffer, windowed + accumulated input gradient) against the reference's formulation
@@ -244,10 +282,12 @@ def test_glue_kernels_against_torch(dev):
             assert torch.equal(out, ref), (stride, use_gs, use_gg)
 
 
-def test_input_gradient_in_column_blocks(dev):
+@pytest.mark.parametrize("kernel", ["wave", "staged"])
+def test_input_gradient_in_column_blocks(dev, kernel, variants):
     """nvsf_mlp_bwd's column-block layout of dL/dx ([n_in / B][M][B], bits 8..15 of gx_accumulate): the same numbers as the row layout,
-    transposed, for B = 2 and 4, written and accumulated; M not a multiple of the tile."""
+    transposed, for B = 2 and 4, written and accumulated; M not a multiple of the tile.  Both kernels store through the same helper."""
     from nvsf import field_ops as ops
+    variants.set(mlp_bwd=kernel)
     spec = ops.MlpSpec(32, 16, 64, 1)
     g = torch.Generator().manual_seed(5)
     M = 3003
@@ -264,14 +304,17 @@ def test_input_gradient_in_column_blocks(dev):
         torch.testing.assert_close(twice.permute(1, 0, 2).reshape(M, 32), 2 * ref, rtol=1e-6, atol=0)
 
 
+@pytest.mark.parametrize("kernel", ["wave", "staged"])
 @pytest.mark.parametrize("n_in,two_heads,blocks", [(32, False, 0), (32, True, 2), (120, True, 0), (32, True, 0), (32, False, 4)])
-def test_density_logit_gradient_composed_in_the_kernel(dev, n_in, two_heads, blocks, variants):
+def test_density_logit_gradient_composed_in_the_kernel(dev, n_in, two_heads, blocks, kernel, variants):
     """nvsf_mlp_bwd_density (round 5): the density network's logit gradient [g_sigma clamp(sigma) | g_geo_a (+ g_geo_b)] formed while the
     operands are fetched == nvsf_sigma_geo_bwd (+ the sum of the two heads' rows) followed by nvsf_mlp_bwd: same dL/dx bit for bit (the
-    same fp32 values enter the same kernel), dL/dW up to the order of its per-workgroup float atomics.  32-64-16 = the LDS-staged kernel
-    (rows and level-major column blocks), 120-64-16 = the wave-independent kernel."""
+    same fp32 values enter the same kernel), dL/dW up to the order of its per-workgroup float atomics.  Both widths (rows and level-major
+    column blocks at 32) on both kernels: by shape 32-64-16 takes the LDS-staged kernel and 120-64-16 the wave-independent one, and the
+    composed fetch is one helper that serves both."""
     from nvsf import field_ops as ops, _hip
     from nvsf.nerf import activation
+    variants.set(mlp_bwd=kernel)
     M = 5000 + 37
     spec = ops.MlpSpec(n_in, 16, 64, 1)
     g = torch.Generator().manual_seed(n_in + int(two_heads))
