@@ -3,9 +3,10 @@
  * CPU restatement of the reference's Chamfer-distance extension
  *   /root/reference/nvsf/nerf/chamfer3D/chamfer3D.cu:9-138 (NmDistanceKernel: brute-force nearest neighbour,
  *   squared Euclidean distance, index of the nearest point) and :167-195 (NmDistanceGradKernel).
- * PARITY STATUS: "parity unpinned" against a compiled reference (CUDA source, unbuildable in this image, no tests in
- * the reference); pinned by the closed form below being checked against numpy (scipy.spatial cdist / argmin) in
- * tests/test_oracle_cpu.py.  Ties: the lowest index wins (a sequential scan with a strict '<').
+ * PARITY STATUS: pinned by the closed form below being checked against numpy (scipy.spatial cdist / argmin) in
+ * tests/test_oracle_cpu.py; the HIP kernels it checks are also compared with the reference's own kernels, compiled for gfx950
+ * by oracle/build_ref.py where the reference tree is present (tests/test_compiled_reference_gpu.py: indices equal, distances
+ * bit for bit).  Ties: the lowest index wins (a sequential scan with a strict '<'; the compiled reference agrees).
  */
 #include <stdint.h>
 #include <stddef.h>

@@ -8,13 +8,14 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library; the
  * product path (selfsupervised-nvsf_amd/) never links, imports or calls it.
  *
- * PARITY STATUS: "parity unpinned" against a *compiled* reference.  The reference is a
- * CUDA translation unit (needs nvcc + CUDA runtime + ATen CUDA headers) and therefore is
- * unbuildable in this image; it ships no tests and no golden vectors.  This restatement
- * is pinned instead by (i) closed-form known answers (slab test in fp64, bit-interleave
- * round trips, numpy.packbits), and (ii) cross-checks of the compositing recurrences
- * against the reference's importable PyTorch compositor (renderer_dynamic.py:181-224),
- * see tests/test_oracle_raymarching.py.
+ * PARITY STATUS: the reference ships no tests and no golden vectors.  This restatement is
+ * pinned by (i) closed-form known answers (slab test in fp64, bit-interleave round trips,
+ * numpy.packbits), and (ii) cross-checks of the compositing recurrences against the
+ * reference's importable PyTorch compositor (renderer_dynamic.py:181-224), see
+ * tests/test_oracle_cpu.py.  The HIP kernels it checks are ALSO compared with the
+ * reference's own kernels, compiled for gfx950 by oracle/build_ref.py where the reference
+ * tree is present (tests/test_compiled_reference_gpu.py: marcher bit for bit per ray,
+ * compositors to 1e-5), so a misreading shared by this file and the kernels shows there.
  *
  * Floating-point contract: every +,-,*,/ is an individually rounded IEEE fp32 operation
  * (build with -ffp-contract=off); the HIP kernels are built the same way so that the

@@ -3,7 +3,8 @@
   * uniform sampler / compositor restatement (oracle/field_oracle.c) against fixtures produced by the
     reference's own NeRFRenderer.run (tests/golden/renderer_uniform.npz, generator tests/golden/make_golden.py);
   * raymarching restatement (oracle/raymarching_oracle.c) against closed-form known answers and against the
-    reference's importable torch compositor formulas (the CUDA extension itself is unbuildable here);
+    reference's importable torch compositor formulas (the compiled CUDA extension is compared with the HIP kernels on
+    the GPU, tests/test_compiled_reference_gpu.py);
   * field operators against independent numpy / fp64 evaluations of the published formulas.
 """
 import os
