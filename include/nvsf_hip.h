@@ -924,6 +924,45 @@ int nvsf_unet_forward(const float* raydrop, const float* intensity, const float*
                       size_t n_packed, void* workspace, size_t ws_bytes, float thres, float* prob, float* gated_intensity,
                       float* gated_range, nvsf_stream_t stream);
 
+/* ---- 14. prediction export: range image -> point clouds, float planes -> uint8 ------------------------------------------------ */
+
+/* Contract as sections 10 to 13: status return, explicit stream, no allocation, caller-owned buffers, the workspace passed in and its
+ * size checked, NVSF_ERR_INVALID_ARG before any launch with outputs and workspace untouched. */
+
+/* ref: utils.get_pcd_bound_to_world, nvsf/nerf/utils.py:444-474, over convert.pano_to_lidar_with_intensities, nvsf/lib/convert.py:221-268,
+ * as Trainer.test calls it on a predicted frame (nvsf/nerf/trainer.py:1197-1204).  range [H, W] fp32 in scene units, payload [H, W] fp32 or NULL
+ * (device); geom: HOST pointer to four doubles (fov_up, fov, fov_hoz in degrees, scale), fov > 0, fov_hoz > 0, scale > 0; lidar2world:
+ * HOST pointer to 16 doubles, row-major 4 x 4 (the caller forms it as utils.py:466-467 does, on a copy of the pose), or NULL; both are
+ * read before the call returns.
+ *   Which pixels: pixel p gives a point iff range[p] != 0.0f -- -0.0 is dropped, NaN and negative ranges are kept, as np.where(pano != 0.0).
+ *   Order: row-major pixel order (numpy's).  Row k of both clouds belongs to the k-th kept pixel; two runs give the same bits.
+ *   cloud_lidar [capacity, 4] fp32, 16-byte aligned: the point of section 11 step 1 (the same device function) with every coordinate
+ *   then divided by (float)scale -- a true fp32 division -- and the payload (0 when payload is NULL) in column 3.
+ *   cloud_world [capacity, 4] fp64 or NULL (it needs lidar2world): ((m0 x + m1 y) + m2 z) + m3 per row of lidar2world, evaluated in fp64
+ *   on the fp32 point just written (np.column_stack with np.ones promotes the reference's cloud to float64), and (double)payload.
+ *   count uint32 [1] (device) = the TOTAL number of kept pixels, whatever the capacity.  Rows >= capacity are not written; rows >= count
+ *   are never touched.
+ * Ordered compaction without atomics and without any waiting between workgroups: per-workgroup counts by wave ballot + popcount (a
+ * workgroup owns 1024 consecutive pixels), an exclusive scan of the counts by one workgroup, placement with the ballots recomputed.
+ * workspace: 4 ceil(H W / 1024) bytes, 4-byte aligned.  1 <= H, W and H W <= 2^24.  Three launches (two when capacity is 0). */
+int nvsf_pano_to_cloud(const float* range, const float* payload, uint32_t H, uint32_t W, const double* geom, const double* lidar2world,
+                       void* workspace, size_t ws_bytes, float* cloud_lidar, double* cloud_world, uint32_t capacity, uint32_t* count,
+                       nvsf_stream_t stream);
+
+/* The sizes behind nvsf_pano_to_cloud at H x W.  sizes: HOST pointer to two uint64: the workspace bytes, and the consecutive pixels
+ * one workgroup of the compaction owns (nvsf/nerf/export.py: PIXELS_PER_WORKGROUP).  Launches nothing; the stream is not used. */
+int nvsf_pano_to_cloud_sizes(uint32_t H, uint32_t W, uint64_t* sizes, nvsf_stream_t stream);
+
+/* ref: `(pred * 255).astype(np.uint8)`, nvsf/nerf/trainer.py:1157-1158, 1190-1194, after utils.linear_to_srgb (nvsf/nerf/utils.py:31-36,
+ * applied at trainer.py:1149-1150) when srgb != 0.
+ * out[i] = (uint8)(x[i] * 255.0f): fp32 product, truncation toward zero.  Where numpy's cast is undefined the result saturates:
+ * product <= -1 -> 0, product >= 256 -> 255, NaN -> 0.  srgb: where(x < 0.0031308, 12.92 x, 1.055 x^0.41666 - 0.055) first, constants and
+ * operations in fp32, the power correctly rounded (formed in fp64).  n <= 2^30; n = 0 is a no-op.  One launch. */
+int nvsf_quantize_u8(const float* x, uint32_t n, int srgb, uint8_t* out, nvsf_stream_t stream);
+
+/* ref: utils.linear_to_srgb, nvsf/nerf/utils.py:31-36.  The colour transform of nvsf_quantize_u8 alone: out [n] fp32.  One launch. */
+int nvsf_linear_to_srgb(const float* x, uint32_t n, float* out, nvsf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,11 @@ SIGNATURES = {
     # section 13: U-Net ray-drop refinement
     "nvsf_unet_sizes": [_U, _U, _P],
     "nvsf_unet_forward": [_P, _P, _P, _U, _U, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _F, _P, _P, _P],
+    # section 14: prediction export
+    "nvsf_pano_to_cloud_sizes": [_U, _U, _P],
+    "nvsf_pano_to_cloud": [_P, _P, _U, _U, _P, _P, _P, ctypes.c_size_t, _P, _P, _U, _P],
+    "nvsf_quantize_u8": [_P, _U, _I, _P],
+    "nvsf_linear_to_srgb": [_P, _U, _P],
 }
 
 _lib = None

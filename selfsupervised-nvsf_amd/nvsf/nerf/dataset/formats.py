@@ -12,6 +12,7 @@
 
 Image decoding uses PIL (the reference uses cv2, absent here); decoded arrays can be passed directly instead.
 """
+import dataclasses
 import json
 import os
 
@@ -103,34 +104,140 @@ def gather_pixels(images, inds):
     return torch.gather(images.reshape(B, -1, C), 1, torch.stack(C * [inds], -1))
 
 
+def _triple(v):
+    return tuple(float(x) for x in v)
+
+
+@dataclasses.dataclass
+class SensorChange:
+    """The reference's novel-sensor arguments (main_nvsf.py:121-131 -> base_dataset.py:43-52), names and defaults as there; all zero =
+    the sensors of the recording.  delta_position (metres) / delta_orientation (degrees; roll, pitch, yaw) move the LiDAR in its own
+    frame; H_lidar_new = --V_lidar_ch, the vertical channels (the range image gets two more rows, "beams at extreme ends"),
+    W_lidar_new = --H_lidar_ch, its columns; intrinsics_lidar_new = (fov_up, fov), intrinsics_hoz_lidar_new = (fov_hoz_up, fov_hoz),
+    degrees, taken only when an entry is non-zero; delta_pos_camera / delta_orient_camera are given in the WORLD axis convention
+    (front, left, up) and mapped to the camera's (right, down, front); H_new, W_new: the camera image size."""
+    delta_position: tuple = (0.0, 0.0, 0.0)
+    delta_orientation: tuple = (0.0, 0.0, 0.0)
+    H_lidar_new: int = 0
+    W_lidar_new: int = 0
+    intrinsics_lidar_new: tuple = (0.0, 0.0)
+    intrinsics_hoz_lidar_new: tuple = (0.0, 0.0)
+    delta_pos_camera: tuple = (0.0, 0.0, 0.0)
+    delta_orient_camera: tuple = (0.0, 0.0, 0.0)
+    H_new: int = 0
+    W_new: int = 0
+
+    def is_trivial(self):
+        """base_dataset.py:170-180: nothing to change."""
+        return not any([np.any(self.delta_orientation), np.any(self.delta_position), self.H_lidar_new != 0, self.W_lidar_new != 0,
+                        np.any(self.intrinsics_lidar_new), np.any(self.intrinsics_hoz_lidar_new), np.any(self.delta_orient_camera),
+                        np.any(self.delta_pos_camera), self.H_new != 0, self.W_new != 0])
+
+
+def euler_xyz_matrix(angles_deg):
+    """scipy's Rotation.from_euler('xyz', angles, degrees=True).as_matrix(): extrinsic rotations about x, then y, then z,
+    R = Rz(c) Ry(b) Rx(a), float64."""
+    a, b, c = (np.deg2rad(float(v)) for v in angles_deg)
+    ca, sa, cb, sb, cc, sc = np.cos(a), np.sin(a), np.cos(b), np.sin(b), np.cos(c), np.sin(c)
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, ca, -sa], [0.0, sa, ca]])
+    ry = np.array([[cb, 0.0, sb], [0.0, 1.0, 0.0], [-sb, 0.0, cb]])
+    rz = np.array([[cc, -sc, 0.0], [sc, cc, 0.0], [0.0, 0.0, 1.0]])
+    return rz @ ry @ rx
+
+
+def world_to_camera_axes(v):
+    """hlpr_fn, base_dataset.py:198-203: (x, y, z) in (front, left, up) -> (-y, -z, x) in (right, down, front)."""
+    x, y, z = (float(c) for c in v)
+    return np.array([-y, -z, x], dtype=np.float64)
+
+
+def _delta_transform(angles_deg, position):
+    T = np.eye(4, dtype=np.float64)
+    T[:3, :3] = euler_xyz_matrix(angles_deg)
+    T[:3, 3] = np.asarray(position, dtype=np.float64)
+    return T
+
+
+def apply_sensor_change(poses, poses_lidar, intrinsics, H, W, H_lidar, W_lidar, intrinsics_lidar, intrinsics_hoz_lidar, scale, change):
+    """base_dataset.py:182-220 on the arrays a transforms file of this project holds.  poses / poses_lidar [F, 4, 4] fp32 (numpy or CPU
+    tensors) ALREADY IN SCENE UNITS (world = pose / scale + offset), so the position deltas, metres, are multiplied by `scale`: the
+    reference right-multiplies the metre pose and recentres afterwards, (R dp + t_m - offset) scale = R (dp scale) + t_scene.  The
+    product is formed in float64 from the stored fp32 pose and rounded once to fp32.  Returns a dict: poses, poses_lidar (fp32 numpy),
+    intrinsics [3, 3] float64 (a copy; cx, cy scaled by W_new / W, H_new / H, focal lengths as they are), H, W, H_lidar, W_lidar,
+    intrinsics_lidar, intrinsics_hoz_lidar.  A trivial change returns the inputs themselves.
+    Deviation: with only one of H_new / W_new given the reference sets the other size to 0 (:219-220); here it keeps its value."""
+    out = {"poses": poses, "poses_lidar": poses_lidar, "intrinsics": intrinsics, "H": H, "W": W, "H_lidar": H_lidar, "W_lidar": W_lidar,
+           "intrinsics_lidar": intrinsics_lidar, "intrinsics_hoz_lidar": intrinsics_hoz_lidar}
+    if change is None or change.is_trivial():
+        return out
+    as_np = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float32, copy=False)
+    scale = float(scale)
+    T_lidar = _delta_transform(change.delta_orientation, np.asarray(_triple(change.delta_position)) * scale)
+    out["poses_lidar"] = np.matmul(as_np(poses_lidar).astype(np.float64), T_lidar).astype(np.float32)
+    if change.H_lidar_new != 0:
+        out["H_lidar"] = int(change.H_lidar_new + 2)  # 2 for beams at extreme ends
+    if change.W_lidar_new != 0:
+        out["W_lidar"] = int(change.W_lidar_new)
+    if np.any(change.intrinsics_lidar_new):
+        out["intrinsics_lidar"] = tuple(float(v) for v in change.intrinsics_lidar_new)
+    if np.any(change.intrinsics_hoz_lidar_new):
+        out["intrinsics_hoz_lidar"] = tuple(float(v) for v in change.intrinsics_hoz_lidar_new)
+    T_cam = _delta_transform(world_to_camera_axes(change.delta_orient_camera), world_to_camera_axes(change.delta_pos_camera) * scale)
+    out["poses"] = np.matmul(as_np(poses).astype(np.float64), T_cam).astype(np.float32)
+    if change.H_new != 0 or change.W_new != 0:
+        K = np.array(intrinsics, dtype=np.float64, copy=True)
+        K[0, 2] *= change.W_new / W if change.W_new != 0 else 1
+        K[1, 2] *= change.H_new / H if change.H_new != 0 else 1
+        out["intrinsics"] = K
+        out["H"] = int(change.H_new) if change.H_new != 0 else H
+        out["W"] = int(change.W_new) if change.W_new != 0 else W
+    return out
+
+
 class FrameSet:
     """Frames of one split resident on the device + the per-step batch (`collate`) of the reference's loader."""
 
     def __init__(self, root_path, sequence_id, split, scale, intrinsics_lidar=(2.0, 26.9), intrinsics_hoz_lidar=(180.0, 360.0),
                  num_rays=4096, num_rays_lidar=4096, patch_size=1, patch_size_lidar=1, device="cuda", training=True,
-                 images=None, range_images=None, camera_depth=False, annotations=None, offset=(0.0, 0.0, 0.0)):
+                 images=None, range_images=None, camera_depth=False, annotations=None, offset=(0.0, 0.0, 0.0), sensor=None):
         """images / range_images: optional pre-decoded lists (skips file reads, e.g. synthetic data).  camera_depth: build
         `image_depths` [F, H, W], the LiDAR-projected camera depth map of every frame in metres (base_dataset.py:153-157), in one
         launch (nvsf/nerf/dataset/depth_image.py); `collate` / `train_batch` then carry it.  annotations: the 3-D boxes of the moving
         objects, per frame a list of {"class": str, "vertices": [8, 3] world frame, metres} -- a list with one entry per frame, or the
         path of a JSON sidecar keyed by frame id (nvsf/nerf/object_masks.py::load_annotations; a frame it does not name has no box);
         `collate` then adds "3d_annotation" (base_dataset.py:314).  offset: the reference's --offset, the recentring the poses went
-        through (world = pose / scale + offset), which the object masks need to bring the boxes into the sensor frames."""
+        through (world = pose / scale + offset), which the object masks need to bring the boxes into the sensor frames.
+        sensor: a SensorChange -- render the split from changed sensors (base_dataset.py:168-227).  Only with training=False; the poses,
+        sizes and intrinsics are those of apply_sensor_change, no image or range image is read (the reference's "Disable validation":
+        `images`, `images_lidar`, `image_depths` are None) and `collate` carries rays only.  None or an all-zero change: nothing differs."""
+        changed = sensor is not None and not sensor.is_trivial()
+        if changed and training:
+            raise ValueError("FrameSet: a sensor change applies to a test split only (training=False), as base_dataset.py:170")
         t = load_transforms(transforms_path(root_path, sequence_id, split))
+        if changed:
+            c = apply_sensor_change(t["poses"], t["poses_lidar"], t["intrinsics"], t["H"], t["W"], t["H_lidar"], t["W_lidar"],
+                                    intrinsics_lidar, intrinsics_hoz_lidar, scale, sensor)
+            t.update({k: c[k] for k in ("poses", "poses_lidar", "intrinsics", "H", "W", "H_lidar", "W_lidar")})
+            intrinsics_lidar, intrinsics_hoz_lidar = c["intrinsics_lidar"], c["intrinsics_hoz_lidar"]
+        self.sensor = sensor if changed else None
         self.meta, self.device, self.training, self.scale = t, torch.device(device), training, scale
         self.H, self.W, self.H_lidar, self.W_lidar = t["H"], t["W"], t["H_lidar"], t["W_lidar"]
         self.intrinsics, self.intrinsics_lidar, self.intrinsics_hoz_lidar = t["intrinsics"], intrinsics_lidar, intrinsics_hoz_lidar
         self.num_rays = num_rays if training else -1
         self.num_rays_lidar = num_rays_lidar if training else -1
         self.patch_size, self.patch_size_lidar = patch_size, patch_size_lidar
+        if changed:
+            images = range_images = ()
         if images is None:
             images = [load_image(os.path.join(root_path, f["file_path"]), self.H, self.W) for f in t["frames"]]
         if range_images is None:
             range_images = [np.load(os.path.join(root_path, f["lidar_file_path"])) for f in t["frames"]]
         dev = self.device
-        self.images = torch.from_numpy(np.stack(images, 0).astype(np.float32)).to(dev)
-        self.images_lidar = torch.from_numpy(np.stack([range_image_ground_truth(pc, scale, self.H_lidar, self.W_lidar) for pc in range_images],
-                                                      0).astype(np.float32)).to(dev)
+        self.images = self.images_lidar = None
+        if not changed:
+            self.images = torch.from_numpy(np.stack(images, 0).astype(np.float32)).to(dev)
+            self.images_lidar = torch.from_numpy(np.stack([range_image_ground_truth(pc, scale, self.H_lidar, self.W_lidar)
+                                                           for pc in range_images], 0).astype(np.float32)).to(dev)
         self.poses = torch.from_numpy(t["poses"]).to(dev)
         self.poses_lidar = torch.from_numpy(t["poses_lidar"]).to(dev)
         self.times = torch.from_numpy(t["times"].astype(np.float32)).view(-1, 1).to(dev)
@@ -150,7 +257,7 @@ class FrameSet:
             self.annotations = [[{"class": str(a.get("class", "")), "vertices": np.asarray(a["vertices"], dtype=np.float64).reshape(8, 3)}
                                  for a in frame] for frame in annotations]
         self.image_depths = None
-        if camera_depth:
+        if camera_depth and not changed:
             from nvsf.nerf.dataset import depth_image
             ranges = torch.from_numpy(np.stack([np.asarray(pc)[:, :, 2] for pc in range_images], 0).astype(np.float32)).to(dev)
             self.image_depths = depth_image.lidar_depth_images(ranges, self.poses, self.poses_lidar, self.intrinsics, self.H, self.W,
@@ -197,6 +304,10 @@ class FrameSet:
                                           self.num_rays_lidar, self.patch_size_lidar, em, use_error_map and em is not None)
         res.update({"H_lidar": self.H_lidar, "W_lidar": self.W_lidar, "rays_o_lidar": rl["rays_o"], "rays_d_lidar": rl["rays_d"],
                     "rays_pano_inds": rl["inds"], "poses_lidar": self.poses_lidar[idx]})
+        if self.images is None:  # changed sensors: no ground truth (no images, images_lidar, image_depths, pano_frame)
+            if self.annotations is not None:
+                res["3d_annotation"] = self.annotations[int(index[0])]
+            return res
         images, images_lidar = self.images[idx], self.images_lidar[idx]
         if self.training:
             images = gather_pixels(images, rays["inds"])

@@ -894,6 +894,52 @@ def eval_step(model, data, num_steps, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, al
     return out
 
 
+def test_step(model, data, num_steps, alpha_r=0.01, raydrop_thres=0.5, max_ray_batch=4096, split_rays=True, refiner=None, bg_color=None,
+              perturb=False, **render_kwargs):
+    """Predictions of one whole frame without ground truth, the reference's Trainer.test_step (nvsf/nerf/trainer.py:817-903): `data` =
+    FrameSet(..., training=False[, sensor=SensorChange(...)]).collate([i]).  Both modalities go through the staged render as in
+    eval_step (a frame's rays split over the ranks unless split_rays=False); with a `refiner` the ray-drop plane becomes the U-Net's
+    refined probability (:865-867); the mask `pred_raydrop > raydrop_thres` gates intensity and range only when alpha_r > 0 (:870-875);
+    `data["masks_lidar"]` [B, H_lidar, W_lidar] multiplies range, ray-drop and intensity, `data["masks"]` [B, H, W, 1] the image
+    (:876-879, 897-898).  bg_color None is the white background eval_step fixes; perturb jitters the samples.
+    Returns (pred_rgb [B, H, W, 3], pred_rgb_depth [B, H, W], pred_raydrop, pred_intensity, pred_depth [B, H_lidar, W_lidar])."""
+    from nvsf import frame_shard
+    if split_rays:
+        render = lambda *a, **k: frame_shard.render_sharded(model, *a, **k)
+    else:
+        render = lambda o, d, t, **k: model.render(o, d, t, staged=True, **k)
+    with torch.no_grad():
+        Hl, Wl = int(data["H_lidar"]), int(data["W_lidar"])
+        B = data["rays_o_lidar"].shape[0]
+        o = render(data["rays_o_lidar"], data["rays_d_lidar"], data["time"], cal_lidar_color=True, num_steps=num_steps,
+                   max_ray_batch=max_ray_batch, perturb=perturb, **render_kwargs)
+        img = o["image_lidar"].reshape(B, Hl, Wl, 2)
+        pred_raydrop, pred_intensity, pred_depth = img[..., 0], img[..., 1], o["depth_lidar"].reshape(B, Hl, Wl)
+        if refiner is not None:
+            refined = [refiner(pred_raydrop[b].float(), pred_intensity[b].float(), pred_depth[b].float(),
+                               thres=raydrop_thres if alpha_r > 0 else None) for b in range(B)]
+            if alpha_r > 0:  # the U-Net's last kernel wrote the gated planes
+                pred_raydrop, pred_intensity, pred_depth = (torch.stack([f[k] for f in refined]) for k in range(3))
+            else:
+                pred_raydrop = torch.stack(refined)
+        elif alpha_r > 0:
+            mask = (pred_raydrop > raydrop_thres).to(pred_depth.dtype)
+            pred_intensity, pred_depth = pred_intensity * mask, pred_depth * mask
+        if "masks_lidar" in data:
+            m = data["masks_lidar"].reshape(-1, Hl, Wl)
+            pred_depth, pred_raydrop, pred_intensity = pred_depth * m, pred_raydrop * m, pred_intensity * m
+        H, W = int(data["H"]), int(data["W"])
+        c = render(data["rays_o"], data["rays_d"], data["time"], num_steps=num_steps, max_ray_batch=max_ray_batch,
+                   bg_color=1 if bg_color is None else bg_color, perturb=perturb, **render_kwargs)
+        pred_rgb, pred_rgb_depth = c["image"].reshape(B, H, W, 3), c["depth"].reshape(B, H, W)
+        if "masks" in data:
+            pred_rgb = pred_rgb * data["masks"].reshape(B, H, W, 1)
+    return pred_rgb, pred_rgb_depth, pred_raydrop, pred_intensity, pred_depth
+
+
+test_step.__test__ = False  # a library function, not a test
+
+
 def evaluate_frames(model, frames, num_steps, indices=None, ema=None, shard="rays", meters=None, intensity_inv_scale=1, refiner=None,
                     **eval_kwargs):
     """The metric half of the reference's evaluate_one_epoch (trainer.py:1458-1560) over a FrameSet opened with training=False:

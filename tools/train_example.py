@@ -4,6 +4,9 @@
                                   [--export-mesh out.ply --mesh-res 256 256 256 --mesh-threshold 10] [--dynamic --flow-loss]
                                   [--eval-table] [--rgbd-loss] [--annotations boxes.json [--offset X Y Z]]
                                   [--refine [--refine-iterations N]]
+                                  [--test-export DIR [--delta-position X Y Z] [--delta-orientation R P Y] [--lidar-channels V] [--lidar-columns N]
+                                   [--intrinsics-lidar-new UP FOV] [--intrinsics-hoz-lidar-new UP FOV] [--delta-pos-camera X Y Z]
+                                   [--delta-orient-camera R P Y] [--height-new H] [--width-new W]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 tools/train_example.py ...
 
 Data: the reference's on-disk formats (transforms_{seq}_{split}.json + range-image .npy + images; nvsf/nerf/dataset/formats.py).
@@ -28,6 +31,13 @@ also printed over the static background and over the boxes (trainer.py:1545-1626
 training frames (Trainer.refine, trainer.py:905-1017; nvsf/nerf/refine.py, --refine-iterations steps, the reference's 1000) and the
 evaluation is reported twice, without and with it, as the reference logs both; the refined evaluation runs the U-Net's HIP forward
 (csrc/unet.hip) once per frame.
+--test-export DIR (the reference's Trainer.test, trainer.py:1109-1283): after training, every frame of the split is rendered without
+ground truth (train_step.test_step) and written out as the simulated LiDAR sweep -- text clouds in the world and the LiDAR frame, a PCD
+file -- and as PNGs of the ray-drop mask / intensity / range stack, the camera image and its depth (nvsf/nerf/export.py; clouds and
+uint8 planes built on the device, csrc/export.hip).  The sensor flags (main_nvsf.py:121-131; base_dataset.py:168-227) render it from a
+NOVEL sensor: the LiDAR moved by --delta-position (metres) / --delta-orientation (degrees), with --lidar-channels beams (the range image
+gets two more rows) and --lidar-columns columns, other fields of view; the camera moved and resized likewise.  With --refine the
+exported ray-drop plane is the U-Net's.
 """
 import argparse
 import os
@@ -96,12 +106,31 @@ def main():
     ap.add_argument("--refine", action="store_true", help="fit the ray-drop refinement U-Net after training and evaluate with it as well "
                     "(nvsf/nerf/refine.py; HIP forward csrc/unet.hip)")
     ap.add_argument("--refine-iterations", type=int, default=1000, help="optimisation steps of the U-Net fit (the reference's 1000)")
+    ap.add_argument("--test-export", default=None, metavar="DIR", help="after training, render every frame without ground truth and write the "
+                    "predicted point clouds (world / LiDAR frame .txt, .pcd) and PNGs there (nvsf/nerf/export.py)")
+    ap.add_argument("--delta-position", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"), help="move the LiDAR, metres, its own frame")
+    ap.add_argument("--delta-orientation", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("R", "P", "Y"), help="turn the LiDAR, degrees")
+    ap.add_argument("--lidar-channels", type=int, default=0, metavar="V", help="vertical channels of the new LiDAR (0: unchanged)")
+    ap.add_argument("--lidar-columns", type=int, default=0, metavar="N", help="columns of the new range image (0: unchanged)")
+    ap.add_argument("--intrinsics-lidar-new", type=float, nargs=2, default=[0.0, 0.0], metavar=("UP", "FOV"), help="new vertical field of view, degrees")
+    ap.add_argument("--intrinsics-hoz-lidar-new", type=float, nargs=2, default=[0.0, 0.0], metavar=("UP", "FOV"), help="new horizontal field of view")
+    ap.add_argument("--delta-pos-camera", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"), help="move the camera (front, left, up), metres")
+    ap.add_argument("--delta-orient-camera", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("R", "P", "Y"), help="turn the camera, degrees")
+    ap.add_argument("--height-new", type=int, default=0, metavar="H", help="height of the new camera image (0: unchanged)")
+    ap.add_argument("--width-new", type=int, default=0, metavar="W", help="width of the new camera image (0: unchanged)")
     ap.add_argument("--offset", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"), help="world = pose / scale + offset")
     args = ap.parse_args()
     if args.annotations and not args.eval_table:
         ap.error("--annotations splits the evaluation table: add --eval-table")
     if args.flow_loss and not args.dynamic:
         ap.error("--flow-loss supervises the flow head of the space-time model: add --dynamic")
+    from nvsf.nerf.dataset.formats import SensorChange
+    sensor = SensorChange(delta_position=tuple(args.delta_position), delta_orientation=tuple(args.delta_orientation), H_lidar_new=args.lidar_channels,
+                          W_lidar_new=args.lidar_columns, intrinsics_lidar_new=tuple(args.intrinsics_lidar_new),
+                          intrinsics_hoz_lidar_new=tuple(args.intrinsics_hoz_lidar_new), delta_pos_camera=tuple(args.delta_pos_camera),
+                          delta_orient_camera=tuple(args.delta_orient_camera), H_new=args.height_new, W_new=args.width_new)
+    if not sensor.is_trivial() and not args.test_export:
+        ap.error("the sensor flags change the sensors of the exported test render: add --test-export DIR")
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -192,6 +221,18 @@ def main():
             if args.eval_table:
                 from nvsf.nerf.meters import table_report
                 print("\n".join(table_report(res)), flush=True)
+    if args.test_export:  # every rank renders its share of each frame's rays; rank 0 writes
+        import time
+        from nvsf.nerf.export import export_frames
+        novel = FrameSet(root, args.sequence, "train", scale, device=dev, training=False, offset=args.offset, sensor=sensor)
+        t0 = time.perf_counter()
+        counts = export_frames(model, novel, args.test_export, f"{args.sequence}_ep{args.epochs:04d}", args.num_steps, refiner=refiner, ema=trainer.ema,
+                               write=(rank == 0))
+        torch.cuda.synchronize()
+        if rank == 0:
+            what = "changed sensors" if novel.sensor is not None else "the recording's sensors"
+            print(f"test export ({what}: range image {novel.H_lidar} x {novel.W_lidar}, camera {novel.H} x {novel.W}): {len(counts)} frames, "
+                  f"{counts} points, in {time.perf_counter() - t0:.2f} s -> {args.test_export}", flush=True)
     if args.export_mesh and rank == 0:
         from nvsf.nerf.mesh import export_mesh_density
         t_first = float(whole.collate([0])["time"].reshape(-1)[0])
