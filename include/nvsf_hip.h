@@ -912,6 +912,15 @@ int nvsf_box_mask_image(const int32_t* boxes, uint32_t B, uint32_t H, uint32_t W
  * of nvsf_unet_forward at H x W and the length of the packed weights in floats.  Launches nothing; the stream is not used. */
 int nvsf_unet_sizes(uint32_t H, uint32_t W, uint64_t* sizes, nvsf_stream_t stream);
 
+/* ref: the tensors UNet.forward names, nvsf/nerf/models/unet.py:158-171.  layout: HOST pointer to 13 x 4 uint64, one row {offset in
+ * floats, C, H, W} per tensor that nvsf_unet_forward leaves in its workspace at H x W, each a dense [C, H, W] block, in the order
+ * x0 .. x4 (inc, down1 .. down4), mid, qkv, att (the attention result after the reinterpretation), x4a (the attention block's output),
+ * u0 .. u3 (up1 .. up4).  `mid` is shared by the first convolutions of every Down and Up; the row gives what the last of them,
+ * up4's, leaves there: [64, H, W].  Offsets ascend and are multiples of 64 floats; the rows come from the plan nvsf_unet_forward
+ * itself uses.  Read-only: for tests and debugging.  Launches nothing; the stream is not used; NVSF_ERR_INVALID_ARG (layout
+ * untouched) where nvsf_unet_sizes rejects the shape. */
+int nvsf_unet_layout(uint32_t H, uint32_t W, uint64_t* layout, nvsf_stream_t stream);
+
 /* ref: UNet.forward in evaluation mode, nvsf/nerf/models/unet.py:158-171, on the input the evaluation builds at
  * nvsf/nerf/trainer.py:721-733: raydrop, intensity, range [H, W] fp32 planes of one frame; prob [H, W] fp32 = the refined ray-drop
  * probability.  With gated_intensity and gated_range (both or neither) the last kernel also writes intensity * m and range * m,

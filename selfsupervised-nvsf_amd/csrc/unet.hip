@@ -367,6 +367,21 @@ NVSF_API int nvsf_unet_sizes(uint32_t H, uint32_t W, uint64_t* sizes, hipStream_
     return NVSF_OK;
 }
 
+NVSF_API int nvsf_unet_layout(uint32_t H, uint32_t W, uint64_t* layout, hipStream_t) {
+    REQUIRE(layout);
+    Plan p;
+    REQUIRE(make_plan(H, W, p));
+    uint64_t* row = layout;
+    auto put = [&](size_t off, int c, int l) { row[0] = off; row[1] = (uint64_t)c; row[2] = (uint64_t)p.H[l]; row[3] = (uint64_t)p.W[l]; row += 4; };
+    for (int l = 0; l < 5; ++l) put(p.x[l], kC[l], l);
+    put(p.mid, kLayers[17].cout, 0);  // what up4's first convolution, the last launch that writes `mid`, leaves there
+    put(p.qkv, 768, 4);
+    put(p.att, 256, 4);
+    put(p.x4a, 256, 4);
+    for (int i = 0; i < 4; ++i) put(p.u[i], kUpOut[i], 3 - i);
+    return NVSF_OK;
+}
+
 NVSF_API int nvsf_unet_forward(const float* raydrop, const float* intensity, const float* range, uint32_t H, uint32_t W, const float* packed,
                                size_t n_packed, void* workspace, size_t ws_bytes, float thres, float* prob, float* gated_intensity,
                                float* gated_range, hipStream_t stream) {

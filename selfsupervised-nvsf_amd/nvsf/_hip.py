@@ -124,6 +124,7 @@ SIGNATURES = {
     "nvsf_box_mask_image": [_P, _U, _U, _U, _P],
     # section 13: U-Net ray-drop refinement
     "nvsf_unet_sizes": [_U, _U, _P],
+    "nvsf_unet_layout": [_U, _U, _P],
     "nvsf_unet_forward": [_P, _P, _P, _U, _U, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _F, _P, _P, _P],
     # section 14: prediction export
     "nvsf_pano_to_cloud_sizes": [_U, _U, _P],

@@ -117,12 +117,7 @@ class RaydropRefiner:
         if self._packed is None:
             self.repack()
         planes = [t.contiguous() for t in planes]
-        ws = self._ws.get((H, W))
-        if ws is None:
-            sizes = np.zeros(2, dtype=np.uint64)
-            _hip.call("nvsf_unet_sizes", H, W, sizes.ctypes.data)
-            assert int(sizes[1]) == self._packed.numel(), "packed layout disagrees with the library"
-            ws = self._ws[(H, W)] = torch.empty(int(sizes[0]) // 4, dtype=torch.float32, device=self.device)
+        ws = self._workspace(H, W)
         prob = torch.empty(H, W, dtype=torch.float32, device=self.device)
         gi = gd = None
         if thres is not None:
@@ -133,6 +128,28 @@ class RaydropRefiner:
         if thres is None:
             return prob.reshape(raydrop.shape)
         return prob.reshape(raydrop.shape), gi.reshape(intensity.shape), gd.reshape(depth.shape)
+
+    def _workspace(self, H, W):
+        ws = self._ws.get((H, W))
+        if ws is None:
+            if self._packed is None:
+                self.repack()
+            sizes = np.zeros(2, dtype=np.uint64)
+            _hip.call("nvsf_unet_sizes", H, W, sizes.ctypes.data)
+            assert int(sizes[1]) == self._packed.numel(), "packed layout disagrees with the library"
+            ws = self._ws[(H, W)] = torch.empty(int(sizes[0]) // 4, dtype=torch.float32, device=self.device)
+        return ws
+
+    STAGES = ("x0", "x1", "x2", "x3", "x4", "mid", "qkv", "att", "x4a", "u0", "u1", "u2", "u3")
+
+    def stage_views(self, H, W):
+        """{name: [C, H_l, W_l] view} of the 13 tensors the HIP forward leaves in its H x W workspace (nvsf_unet_layout: x0 .. x4 =
+        inc, down1 .. down4; mid = up4's first convolution; qkv, att, x4a = the attention block; u0 .. u3 = up1 .. up4).  The views
+        alias the workspace: valid after a forward at this shape and overwritten by the next one."""
+        ws = self._workspace(H, W)
+        layout = np.zeros((len(self.STAGES), 4), dtype=np.uint64)
+        _hip.call("nvsf_unet_layout", H, W, layout.ctypes.data)
+        return {name: ws[int(o):int(o) + int(c) * int(h) * int(w)].view(int(c), int(h), int(w)) for name, (o, c, h, w) in zip(self.STAGES, layout)}
 
     def torch_forward(self, raydrop, intensity, depth, thres=None):
         """The same through the torch module in evaluation mode, on whatever device the module lives."""

@@ -92,6 +92,69 @@ def test_packed_weights_have_the_documented_layout(net):
     assert torch.equal(w[5, 7], net.down1.conv.double_conv[3].weight.detach()[:, 5, 2, 1])
 
 
+LAYOUT_SHAPES = ((16, 16), (31, 47), (34, 70), (66, 1030), (2048, 16), (1448, 1448))
+
+
+@pytest.mark.parametrize("shape", LAYOUT_SHAPES)
+def test_workspace_layout_rows(hip_lib, shape):
+    """nvsf_unet_layout: 13 rows {offset in floats, C, H, W} in the order x0 .. x4, mid, qkv, att, x4a, u0 .. u3; host-only, no launch."""
+    H, W = shape
+    sizes, layout = np.zeros(2, np.uint64), np.full((13, 4), 2 ** 63 + 5, np.uint64)
+    assert hip_lib.nvsf_unet_sizes(H, W, sizes.ctypes.data, None) == 0
+    assert hip_lib.nvsf_unet_layout(H, W, layout.ctypes.data, None) == 0
+    rows = [tuple(int(v) for v in r) for r in layout]
+    hs, ws = [H], [W]
+    for _ in range(4):  # MaxPool2d(2): floor
+        hs.append(hs[-1] // 2)
+        ws.append(ws[-1] // 2)
+    level = [0, 1, 2, 3, 4, 0, 4, 4, 4, 3, 2, 1, 0]
+    chans = [32, 64, 128, 256, 256, 64, 768, 256, 256, 128, 64, 32, 32]
+    assert [r[1:] for r in rows] == [(c, hs[l], ws[l]) for c, l in zip(chans, level)]
+    end = 0
+    for off, c, h, w in rows:
+        assert off % 64 == 0 and off >= end  # ascending, no overlap
+        end = off + c * h * w
+    assert rows[0][0] == 0 and end <= int(sizes[0]) // 4 and int(sizes[0]) % 4 == 0
+    # `mid` is the scratch of every Down's and Up's first convolution: the next row starts behind the largest of them
+    largest = max(64 * hs[0] * ws[0], 128 * hs[1] * ws[1], 256 * hs[2] * ws[2], 512 * hs[3] * ws[3], 256 * hs[4] * ws[4])
+    assert rows[6][0] - rows[5][0] >= largest
+
+
+@pytest.mark.parametrize("shape", [(15, 70), (70, 15), (387, 5419)])  # 387 x 5419 = 2^21 + 1 pixels
+def test_workspace_layout_rejects_what_the_forward_rejects(hip_lib, shape):
+    layout, sizes = np.full((13, 4), 77, np.uint64), np.full(2, 77, np.uint64)
+    assert hip_lib.nvsf_unet_layout(*shape, layout.ctypes.data, None) == -1
+    assert hip_lib.nvsf_unet_sizes(*shape, sizes.ctypes.data, None) == -1
+    assert bool((layout == 77).all()) and bool((sizes == 77).all())
+    assert hip_lib.nvsf_unet_layout(16, 16, None, None) == -1
+
+
+def test_stage_oracle_captures_the_module_and_its_logit_band_keeps_enough_pixels():
+    """tests/unet_stage_oracle.py, the reference of test_unet_stages_gpu.py: its hooks leave the module's output what it was, its stages
+    have the shapes of the workspace rows, and the band 0.02 < p < 0.98 of the fp64 reference alone keeps at least 40 % of the pixels at
+    every shape and weight draw of the logit comparison (a condition on the reference, checked before any kernel is involved)."""
+    import unet_stage_oracle as O
+    m = UNet().eval()
+    P.load_into(m, 1)
+    with torch.no_grad():
+        want = m(torch.from_numpy(P.unet_input(31, 47, O.INPUT_SEED))[None])[0]
+    got = O.run_stages(31, 47, 1, O.INPUT_SEED, torch.float32)
+    assert torch.equal(got["prob"], want) and torch.equal(torch.sigmoid(got["logit"]), want)
+    chans = dict(zip(O.STAGES, (32, 64, 128, 256, 256, 64, 768, 256, 256, 128, 64, 32, 32)))
+    level = dict(zip(O.STAGES, (0, 1, 2, 3, 4, 0, 4, 4, 4, 3, 2, 1, 0)))
+    for name in O.STAGES:
+        assert got[name].shape == (chans[name], 31 >> level[name], 47 >> level[name]) and got[name].is_contiguous(), name
+    # att is the tensor the projection reads (a dense copy of attend's permuted view): a mis-ordered capture is off by O(1), a
+    # convolution of the copy instead of the view by a few ulp of values up to 4
+    assert float((got["x4a"] - (got["x4"] + m.attn.proj(got["att"][None])[0].detach())).abs().max()) <= 64 * float(np.finfo(np.float32).eps)
+    for shape in O.SHAPES:
+        for seed in O.LOGIT_WEIGHT_SEEDS:
+            p = O.run_stages(*shape, seed, O.INPUT_SEED, torch.float64)["prob"]
+            kept = float(((p > O.LOGIT_BAND[0]) & (p < O.LOGIT_BAND[1])).double().mean())
+            print(f"{shape}, weight draw {seed}: {100 * kept:.1f} % of the pixels inside the band")
+            assert kept >= O.BAND_MIN_KEPT, (shape, seed)
+
+
 def test_augmentation_boxes_stay_within_the_reference_bounds():
     H, W = 66, 1030
     g = torch.Generator().manual_seed(11)
