@@ -180,7 +180,7 @@ def export_frames(model, frames, out_dir, name, num_steps, refiner=None, color_s
     the QUANTISED intensity as a float, as the reference passes `img_intensity_pred` (trainer.py:1197-1204).  `ema`: evaluate under the averaged weights, as evaluate_frames.
     Across ranks every rank calls this (test_step splits a frame's rays over them); `write=False` on all but one keeps the files single.
     Returns the per-frame point counts."""
-    from nvsf.nerf.train_step import test_step
+    from nvsf.nerf.evaluate import test_step
     if color_space not in ("srgb", "linear"):
         raise ValueError("color_space: 'srgb' or 'linear'")
     if write:

@@ -391,7 +391,7 @@ class SSIMMeter(_DeviceMeter):
 
 
 def table_meters(scale, intensity_inv_scale=1, raydrop_ratio=0.5, lpips_fn=None):
-    """The meters of the reference's evaluation table (main_nvsf.py:224-240) minus PointsMeter (train_step.PointsMeter) and
+    """The meters of the reference's evaluation table (main_nvsf.py:224-240) minus PointsMeter (evaluate.PointsMeter) and
     LPIPSMeter (no weights here): {"depth", "intensity", "raydrop", "psnr", "rmse", "ssim"}.  "rmse" compares the rendered image
     with the measured one.  The reference feeds its camera RMSE meter the LiDAR-projected camera DEPTH image (trainer.py:1540-1541):
     that is the further meter "rgb_depth" = RMSEMeter(rgb_metric=True), which evaluate_frames adds when the frames carry the map
@@ -400,16 +400,20 @@ def table_meters(scale, intensity_inv_scale=1, raydrop_ratio=0.5, lpips_fn=None)
             "raydrop": RaydropMeter(raydrop_ratio), "psnr": PSNRMeter(), "rmse": RMSEMeter(), "ssim": SSIMMeter()}
 
 
-def update_table(meters, e, scale=1.0):
+def update_table(meters, e, scale=1.0, masks=None):
     """Feeds the meters of `table_meters` from eval_step's output, as evaluate_one_epoch feeds its own (trainer.py:1537-1584).  A
-    "rgb_depth" meter is fed pred_rgb_depth / scale against the depth map in metres (trainer.py:761-762)."""
+    "rgb_depth" meter is fed pred_rgb_depth / scale against the depth map in metres (trainer.py:761-762).  `masks` = (mask_pred, mask_gt,
+    mask_img) feeds one of the two further tables (`split_table_meters`) as trainer.py:1553-1569, 1604-1626 do: the prediction times its own
+    mask, the ground truth times the ground truth's; the camera image and its depth times the one image mask.  None multiplies nothing."""
+    mp, mg, mi, mc = (None,) * 4 if masks is None else (*masks, masks[2][..., None])
+    on = lambda x, m: x if m is None else x * m
     if "rgb_depth" in meters:
-        meters["rgb_depth"].update(e["pred_rgb_depth"] / scale, e["gt_rgb_depth"])
-    meters["depth"].update(e["pred_depth"], e["gt_depth"])
-    meters["intensity"].update(e["pred_intensity"], e["gt_intensity"])
-    meters["raydrop"].update(e["pred_raydrop"], e["gt_raydrop"])
+        meters["rgb_depth"].update(on(e["pred_rgb_depth"] / scale, mi), on(e["gt_rgb_depth"], mi))
+    for k in ("depth", "intensity", "raydrop"):
+        meters[k].update(on(e["pred_" + k], mp), on(e["gt_" + k], mg))
     for k in ("psnr", "rmse", "ssim"):
-        meters[k].update(e["pred_rgb"], e["gt_rgb"])
+        if k in meters:
+            meters[k].update(on(e["pred_rgb"], mc), on(e["gt_rgb"], mc))
 
 
 SPLITS = ("static", "dynamic")
@@ -444,18 +448,6 @@ def frame_object_masks(e, data, frames, lidar_max_depth):
         di = torch.zeros_like(si)
     cast = lambda *ms: tuple(m[None].to(pd.dtype) for m in ms)
     return {"static": cast(sp, sg, si), "dynamic": cast(dp, dg, di)}
-
-
-def update_split_table(meters, e, scale, mask_pred, mask_gt, mask_img):
-    """Feeds one of the two further tables as trainer.py:1553-1569, 1604-1626 do: the prediction times its own mask, the ground truth
-    times the ground truth's; the camera image and its depth times the one image mask."""
-    if "rgb_depth" in meters:
-        meters["rgb_depth"].update(e["pred_rgb_depth"] / scale * mask_img, e["gt_rgb_depth"] * mask_img)
-    meters["depth"].update(e["pred_depth"] * mask_pred, e["gt_depth"] * mask_gt)
-    meters["intensity"].update(e["pred_intensity"] * mask_pred, e["gt_intensity"] * mask_gt)
-    meters["raydrop"].update(e["pred_raydrop"] * mask_pred, e["gt_raydrop"] * mask_gt)
-    for k in ("psnr", "ssim"):
-        meters[k].update(e["pred_rgb"] * mask_img[..., None], e["gt_rgb"] * mask_img[..., None])
 
 
 def report_lines(meters):

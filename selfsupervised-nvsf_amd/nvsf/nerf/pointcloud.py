@@ -161,7 +161,7 @@ def point_removal(pc_raw, dist_min=1, dist_max=50, z_limit=(-2.5, 4), generator=
 def process_pointcloud(frames, lidar_max_depth, z_limit=(-2.5, 4), generator=None):
     """trainer.py:1848-1912 over a `FrameSet(training=False)`: (pc_list, pc_ground_list), dicts {frame index: [P, 3] fp32 device tensor}
     in the scaled world frame, keyed int(time * (num_frames - 1)) as RenderTrainStep.flow_loss looks them up."""
-    from nvsf.nerf.train_step import pano_to_lidar
+    from nvsf.nerf.evaluate import pano_to_lidar
     if generator is None:
         generator = torch.Generator().manual_seed(0)
     scale = float(frames.scale)

@@ -67,7 +67,7 @@ def test_points_meter_cd_and_fscore(dev):
     """PointsMeter = the reference's CD / F-score meter (nvsf/lib/error_matrices.py:12-26, 299-356; pano_to_lidar:
     nvsf/lib/convert.py:221-291) on the HIP chamfer kernel: against a numpy restatement of those formulas (brute-force nearest
     neighbours in float64), incl. zero-range pixels and a second frame in the running mean."""
-    from nvsf.nerf.train_step import PointsMeter, fscore, pano_to_lidar
+    from nvsf.nerf.evaluate import PointsMeter, fscore, pano_to_lidar
     rng = np.random.default_rng(3)
     H, W, scale, K, Kh = 16, 96, 0.0125, (10.0, 40.0), (180.0, 360.0)
 

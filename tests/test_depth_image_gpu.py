@@ -346,7 +346,7 @@ def test_train_step_with_and_without_the_depth_term(dev, tmp_path):
 
 def test_evaluate_frames_reports_the_camera_depth_rmse(dev, tmp_path):
     from nvsf.nerf.dataset import formats as F
-    from nvsf.nerf.train_step import eval_step, evaluate_frames
+    from nvsf.nerf.evaluate import eval_step, evaluate_frames
     from nvsf.nerf import meters as M
     seq, pcs, K = _street_dataset(str(tmp_path))
     scale = 0.0108

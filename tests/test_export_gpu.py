@@ -300,7 +300,7 @@ def _frames(scene, dev, **kw):
 
 
 def test_test_step_equals_eval_step(dev, scene):
-    from nvsf.nerf.train_step import eval_step, test_step
+    from nvsf.nerf.evaluate import eval_step, test_step
     m, fe = scene["model"], _frames(scene, dev)
     data = fe.collate([0])
     thres = float(eval_step(m, data, 32)["pred_raydrop"].median())
@@ -334,7 +334,7 @@ def test_test_step_equals_eval_step(dev, scene):
 
 def test_changed_sensor_on_the_device(dev, scene):
     from nvsf.nerf.dataset import dataset_utils, formats as F
-    from nvsf.nerf.train_step import test_step
+    from nvsf.nerf.evaluate import test_step
     m, plain = scene["model"], _frames(scene, dev)
     change = F.SensorChange(delta_position=(0.5, -0.25, 1.0), delta_orientation=(1.0, -2.0, 25.0), H_lidar_new=8, W_lidar_new=48,
                             intrinsics_lidar_new=(10.0, 35.0), delta_pos_camera=(0.5, 0.1, 0.0), delta_orient_camera=(0.0, 3.0, -10.0), H_new=5, W_new=12)
@@ -359,7 +359,7 @@ def test_export_frames(dev, scene, tmp_path):
     from PIL import Image
     from nvsf.nerf import export as X
     from nvsf.nerf.dataset import formats as F
-    from nvsf.nerf.train_step import test_step
+    from nvsf.nerf.evaluate import test_step
     m = scene["model"]
     fs = _frames(scene, dev, sensor=F.SensorChange(delta_position=(0.0, 0.0, 0.5), H_lidar_new=6, W_lidar_new=40), offset=(1.5, -2.0, 0.25))
     thres = float(test_step(m, fs.collate([0]), 32)[2].median())

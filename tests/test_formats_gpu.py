@@ -55,7 +55,7 @@ def test_eval_step_and_evaluate_frames(tmp_path):
     from test_formats_cpu import make_dataset
     from nvsf.nerf.dataset import formats as F
     from nvsf.nerf.models.network_static import NeRFNetworkStatic
-    from nvsf.nerf.train_step import eval_step, evaluate_frames, psnr, depth_rmse, PointsMeter
+    from nvsf.nerf.evaluate import eval_step, evaluate_frames, psnr, depth_rmse, PointsMeter
     dev = torch.device("cuda:0")
     seq, frames, images, pcs, K = make_dataset(str(tmp_path), n_frames=2, H=24, W=32, Hl=16, Wl=64)
     scale = 0.0108

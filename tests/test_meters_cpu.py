@@ -262,7 +262,7 @@ def test_meters_refuse_cpu_tensors_loudly():
 
 
 def test_evaluate_frames_signature_defaults():
-    from nvsf.nerf.train_step import evaluate_frames
+    from nvsf.nerf.evaluate import evaluate_frames
     params = inspect.signature(evaluate_frames).parameters
     assert params["meters"].default is None and params["intensity_inv_scale"].default == 1
     assert "outside this package's scope" not in evaluate_frames.__doc__

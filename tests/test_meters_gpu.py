@@ -304,7 +304,7 @@ def test_evaluate_frames_table(tmp_path):
     from test_formats_cpu import make_dataset
     from nvsf.nerf.dataset import formats as F
     from nvsf.nerf.models.network_static import NeRFNetworkStatic
-    from nvsf.nerf.train_step import eval_step, evaluate_frames
+    from nvsf.nerf.evaluate import eval_step, evaluate_frames
     from nvsf.nerf import meters as M
     dev = torch.device("cuda:0")
     seq, frames, images, pcs, K = make_dataset(str(tmp_path), n_frames=2, H=24, W=32, Hl=16, Wl=64)

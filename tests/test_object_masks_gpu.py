@@ -261,7 +261,7 @@ def test_evaluate_frames_static_and_dynamic_tables(dev, tmp_path):
     from nvsf.nerf import object_masks as LIB
     from nvsf.nerf.dataset import formats as F
     from nvsf.nerf.models.network_static import NeRFNetworkStatic
-    from nvsf.nerf.train_step import PointsMeter, eval_step, evaluate_frames
+    from nvsf.nerf.evaluate import PointsMeter, eval_step, evaluate_frames
     seq, scale, frames = _rig_dataset(str(tmp_path))
     offset = (4.0, -3.0, 0.5)
     anns = [[{"class": "car", "vertices": _box_in_front(fr["lidar2world"], scale, offset)}] for fr in frames]
@@ -312,7 +312,7 @@ def test_evaluate_frames_static_and_dynamic_tables(dev, tmp_path):
         for s in M.SPLITS:
             pick = (lambda a: a) if s == "dynamic" else (lambda a: (a == 0).astype(np.float32))
             mp, mg, mi = (torch.from_numpy(pick(a)).to(dev)[None] for a in (host["pred_depth"], host["gt_depth"], img))
-            M.update_split_table(hand[s], e, scale, mp, mg, mi)
+            M.update_table(hand[s], e, scale, masks=(mp, mg, mi))
             pts[s].update(e["pred_depth"] * mp, e["gt_depth"] * mg)
     print("dynamic pixels per frame (prediction, ground truth, image):", n_dyn)
     assert all(g > 20 and 0 < im < fe.H * fe.W for _, g, im in n_dyn)

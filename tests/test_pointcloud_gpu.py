@@ -82,7 +82,7 @@ def scene():
 
 
 def test_knn_mean_distance_on_the_scene(dev, scene):
-    from nvsf.nerf.train_step import pano_to_lidar
+    from nvsf.nerf.evaluate import pano_to_lidar
     pano, _, _ = S.street_range_image(np.random.default_rng(0))
     on_dev = pano_to_lidar(torch.from_numpy(pano).to(dev), INTRINSICS, INTRINSICS_HOZ)
     assert on_dev.shape[0] == int((pano != 0).sum())  # the device's cloud is the restatement's, pixel for pixel
@@ -212,7 +212,7 @@ def make_frames(root, dev):
 
 
 def test_process_pointcloud_on_three_frames(dev, tmp_path):
-    from nvsf.nerf.train_step import pano_to_lidar
+    from nvsf.nerf.evaluate import pano_to_lidar
     fs, panos, isolated, poses = make_frames(str(tmp_path), dev)
     pc_list, ground_list = P.process_pointcloud(fs, LIDAR_MAX_DEPTH_M * SCALE, generator=torch.Generator().manual_seed(0))
     assert sorted(pc_list) == [0, 1, 2] and sorted(ground_list) == [0, 1, 2]

@@ -32,7 +32,8 @@ def _batch(S, teacher, dev, n=512, T=48, seed=0):
 def test_training_reduces_loss_and_metrics(dev):
     from nvsf import synthetic as S
     from nvsf.nerf.models.network_static import NeRFNetworkStatic
-    from nvsf.nerf.train_step import RenderTrainStep, psnr, depth_rmse
+    from nvsf.nerf.train_step import RenderTrainStep
+    from nvsf.nerf.evaluate import psnr, depth_rmse
     kw = dict(bound=S.BOUND, min_near=S.MIN_NEAR, min_near_lidar=S.MIN_NEAR, lidar_max_depth=S.LIDAR_MAX_DEPTH, log2_hashmap_size=14)
     torch.manual_seed(1)
     teacher = NeRFNetworkStatic(**kw)

@@ -10,7 +10,7 @@ Legs, on one 66 x 1030 street range image with rendered-looking ray-drop and int
   frame_export   what export_frames does per frame after test_step: the ray-drop gate on intensity and range (torch), the three uint8
                  planes (nvsf_quantize_u8) and the two clouds with the quantised intensity as payload (nvsf_pano_to_cloud), against
                    torch   today's torch form: the same gate, `(x * 255).to(uint8)` for the planes (inputs inside [0, 1]),
-                           train_step.pano_to_lidar's boolean-mask compaction with the payload gathered by the same mask, a true
+                           evaluate.pano_to_lidar's boolean-mask compaction with the payload gathered by the same mask, a true
                            division by the scale and a float64 matmul for the world frame;
   clouds_only    nvsf_pano_to_cloud alone against the torch cloud alone.
 The torch form and the entry are compared on the way: counts, payload column and the largest coordinate difference are in the result.
@@ -30,7 +30,7 @@ import torch  # noqa: E402
 from bench_depth_image import versus  # noqa: E402
 from nvsf import _hip, synthetic as S  # noqa: E402
 from nvsf.nerf import export as X  # noqa: E402
-from nvsf.nerf.train_step import pano_to_lidar  # noqa: E402
+from nvsf.nerf.evaluate import pano_to_lidar  # noqa: E402
 
 FOV, FOV_HOZ, SCALE, OFFSET, THRES = (2.0, 26.9), (180.0, 360.0), 0.01, (1.5, -2.0, 0.25), 0.5
 

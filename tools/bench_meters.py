@@ -11,7 +11,7 @@ Legs per frame:
                                       same statistic (elementwise ops and reductions; kthvalue; conv2d moments in fp64, or fp32 where
                                       the device has no fp64 convolution -- `ssim_torch_dtype` says which);
   table                               all meters of the evaluation table for one frame (launches only, no read), against the host path
-                                      evaluate_frames has used so far: train_step.psnr + train_step.depth_rmse on the same tensors.
+                                      evaluate_frames has used so far: evaluate.psnr + evaluate.depth_rmse on the same tensors.
 `fraction_of_hbm_peak`: the compulsory traffic of the stats and SSIM kernels is one read of both images, 8 bytes per value; the figure
 is (8 n / 8 TB/s) / median.  `decided`: whether the medians differ by more than the two spreads (max - min) combined.
 """
@@ -29,7 +29,7 @@ import torch.nn.functional as F  # noqa: E402
 
 from nvsf import _hip, synthetic as S  # noqa: E402
 from nvsf.nerf import meters as M  # noqa: E402
-from nvsf.nerf.train_step import depth_rmse, psnr  # noqa: E402
+from nvsf.nerf.evaluate import depth_rmse, psnr  # noqa: E402
 
 HBM_PEAK = 8e12
 INF = float("inf")
@@ -157,7 +157,7 @@ def main():
         depth_rmse(e["pred_depth"], e["gt_depth"], scale)
     res["table_per_frame"] = versus(device_table, host_path, args.reps)
     res["table_per_frame"]["kernel"] = "all meters of the table, launches only (3 range-image meters + 3 camera meters)"
-    res["table_per_frame"]["yardstick"] = "train_step.psnr + train_step.depth_rmse: two whole-frame copies to the host each, float64 numpy"
+    res["table_per_frame"]["yardstick"] = "evaluate.psnr + evaluate.depth_rmse: two whole-frame copies to the host each, float64 numpy"
     res["table_report"] = M.report_lines(table)
     res["device"] = torch.cuda.get_device_name(0)
     res["build_digest"] = _hip.build_digest()

@@ -28,7 +28,7 @@ import torch  # noqa: E402
 from nvsf import _hip, synthetic as S  # noqa: E402
 from nvsf.nerf import pointcloud as P  # noqa: E402
 from nvsf.nerf.dataset import formats as F  # noqa: E402
-from nvsf.nerf.train_step import pano_to_lidar  # noqa: E402
+from nvsf.nerf.evaluate import pano_to_lidar  # noqa: E402
 
 PEAK_FP32 = 157.3e12
 FLOP_PER_EVAL = 8

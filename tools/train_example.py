@@ -32,7 +32,7 @@ training frames (Trainer.refine, trainer.py:905-1017; nvsf/nerf/refine.py, --ref
 evaluation is reported twice, without and with it, as the reference logs both; the refined evaluation runs the U-Net's HIP forward
 (csrc/unet.hip) once per frame.
 --test-export DIR (the reference's Trainer.test, trainer.py:1109-1283): after training, every frame of the split is rendered without
-ground truth (train_step.test_step) and written out as the simulated LiDAR sweep -- text clouds in the world and the LiDAR frame, a PCD
+ground truth (evaluate.test_step) and written out as the simulated LiDAR sweep -- text clouds in the world and the LiDAR frame, a PCD
 file -- and as PNGs of the ray-drop mask / intensity / range stack, the camera image and its depth (nvsf/nerf/export.py; clouds and
 uint8 planes built on the device, csrc/export.hip).  The sensor flags (main_nvsf.py:121-131; base_dataset.py:168-227) render it from a
 NOVEL sensor: the LiDAR moved by --delta-position (metres) / --delta-orientation (degrees), with --lidar-channels beams (the range image
@@ -196,7 +196,7 @@ def main():
                 line += f"  error map: {int((em != 1).sum())} of {em.numel()} cells touched, max {float(em.max()):.1f}"
             print(line, flush=True)
     # whole-frame evaluation (Trainer.eval_step / evaluate_one_epoch): every frame rendered with the staged loop, its rays split over the ranks
-    from nvsf.nerf.train_step import evaluate_frames
+    from nvsf.nerf.evaluate import evaluate_frames
     whole = FrameSet(root, args.sequence, "train", scale, device=dev, training=False, camera_depth=args.rgbd_loss,
                      annotations=args.annotations, offset=args.offset)
     refiner = None
