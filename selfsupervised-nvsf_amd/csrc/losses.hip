@@ -17,6 +17,7 @@
 namespace {
 constexpr int kBlock = 1024;
 
+// fp32 partials, wave-level final fold; k_camera_loss_fwd promises another order (fp64 partials, serial fold) and keeps its own
 template <int K>
 __device__ __forceinline__ void block_sums(float (&v)[K], float* __restrict__ out[K]) {
     __shared__ float part[K][kBlock / kWave];
@@ -37,6 +38,17 @@ __device__ __forceinline__ void block_sums(float (&v)[K], float* __restrict__ ou
     }
 }
 
+__device__ __forceinline__ float sgnf(float e) { return e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f); }  // d|x|/dx, 0 at 0 (torch.abs backward)
+struct LidarRay { float m, gd, gi, pd, pr, pi, tr; };  // mask; true range, intensity x mask; rendered range x mask, ray-drop, intensity x mask; smoothed target
+__device__ __forceinline__ LidarRay lidar_ray(const float* __restrict__ image, const float* __restrict__ depth, const float* __restrict__ gt_rd,
+                                              const float* __restrict__ gt_i, const float* __restrict__ gt_d, uint32_t n, float smooth) {
+    const float m = gt_rd[n];
+    return {m, gt_d[n] * m, gt_i[n] * m, depth[n] * m, image[2 * (size_t)n], image[2 * (size_t)n + 1] * m, fminf(fmaxf(m, smooth), 1.0f - smooth)};
+}
+__device__ __forceinline__ void min_max_bits(uint32_t* __restrict__ stats, float v) {  // running (min, max) of the per-ray losses (see below)
+    if (stats && v >= 0.0f) { atomicMin(stats, __float_as_uint(v)); atomicMax(stats + 1, __float_as_uint(v)); }
+}
+
 __global__ __launch_bounds__(kBlock) void k_lidar_losses_fwd(const float* __restrict__ image, const float* __restrict__ depth,
                                                              const float* __restrict__ gt_rd, const float* __restrict__ gt_i,
                                                              const float* __restrict__ gt_d, const float* __restrict__ rays_d, uint32_t N,
@@ -46,21 +58,18 @@ __global__ __launch_bounds__(kBlock) void k_lidar_losses_fwd(const float* __rest
                                                              float* __restrict__ gt_pts) {
     float acc[3] = {0.0f, 0.0f, 0.0f};
     for (uint32_t n = threadIdx.x; n < N; n += kBlock) {
-        const float m = gt_rd[n];
-        const float gd = gt_d[n] * m, gi = gt_i[n] * m;
-        const float pd = depth[n] * m, pr = image[2 * (size_t)n], pi = image[2 * (size_t)n + 1] * m;
-        acc[0] += alpha_d * fabsf(pd - gd);
-        const float tr = fminf(fmaxf(m, smooth), 1.0f - smooth);
-        const float er = pr - tr, ei = pi - gi;
+        const LidarRay t = lidar_ray(image, depth, gt_rd, gt_i, gt_d, n, smooth);
+        acc[0] += alpha_d * fabsf(t.pd - t.gd);
+        const float er = t.pr - t.tr, ei = t.pi - t.gi;
         acc[1] += alpha_r * (er * er);
         acc[2] += alpha_i * (ei * ei);
-        pred_depth[n] = pd;
+        pred_depth[n] = t.pd;
         if (pred_pts) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const float d = rays_d[3 * (size_t)n + k];
-                pred_pts[3 * (size_t)n + k] = d * pd / scale;
-                gt_pts[3 * (size_t)n + k] = d * gd / scale;
+                pred_pts[3 * (size_t)n + k] = d * t.pd / scale;
+                gt_pts[3 * (size_t)n + k] = d * t.gd / scale;
             }
         }
     }
@@ -79,14 +88,8 @@ __global__ __launch_bounds__(256) void k_lidar_losses_bwd(const float* __restric
     const uint32_t n = blockIdx.x * 256u + threadIdx.x;
     if (n >= N) return;
     const float gD = g_depth ? *g_depth : 0.0f, gR = g_rd ? *g_rd : 0.0f, gI = g_int ? *g_int : 0.0f;
-    const float m = gt_rd[n];
-    const float gd = gt_d[n] * m, gi = gt_i[n] * m;
-    const float pd = depth[n] * m, pr = image[2 * (size_t)n], pi = image[2 * (size_t)n + 1] * m;
-    const float tr = fminf(fmaxf(m, smooth), 1.0f - smooth);
-    // d|x|/dx = sign(x), 0 at 0 (torch.abs backward)
-    const float e = pd - gd;
-    const float sgn = e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f);
-    float gpd = gD * alpha_d * sgn;  // gradient of the masked range
+    const LidarRay t = lidar_ray(image, depth, gt_rd, gt_i, gt_d, n, smooth);
+    float gpd = gD * alpha_d * sgnf(t.pd - t.gd);  // gradient of the masked range
     if (g_pred_depth) gpd += g_pred_depth[n];
     if (g_pred_pts) {
         float s = 0.0f;
@@ -94,9 +97,9 @@ __global__ __launch_bounds__(256) void k_lidar_losses_bwd(const float* __restric
         for (int k = 0; k < 3; ++k) s += g_pred_pts[3 * (size_t)n + k] / scale * rays_d[3 * (size_t)n + k];
         gpd += s;
     }
-    grad_depth[n] = gpd * m;
-    grad_image[2 * (size_t)n] = gR * alpha_r * 2.0f * (pr - tr);
-    grad_image[2 * (size_t)n + 1] = gI * alpha_i * 2.0f * (pi - gi) * m;
+    grad_depth[n] = gpd * t.m;
+    grad_image[2 * (size_t)n] = gR * alpha_r * 2.0f * (t.pr - t.tr);
+    grad_image[2 * (size_t)n + 1] = gI * alpha_i * 2.0f * (t.pi - t.gi) * t.m;
 }
 
 __global__ __launch_bounds__(kBlock) void k_mse_sum_fwd(const float* __restrict__ a, const float* __restrict__ b, uint32_t n, float alpha,
@@ -139,8 +142,7 @@ __device__ __forceinline__ float sr_crit(float e, int kind, float param) {
     return a < param ? 0.5f * e * e / param : a - 0.5f * param;                    // SmoothL1(beta)
 }
 __device__ __forceinline__ float sr_crit_grad(float e, int kind, float param) {
-    const float sgn = e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f);
-    const float a = fabsf(e);
+    const float sgn = sgnf(e), a = fabsf(e);
     if (kind == 0) return sgn;
     if (kind == 1) return 2.0f * e;
     if (kind == 2) return a <= param ? e : param * sgn;
@@ -376,14 +378,11 @@ __global__ __launch_bounds__(256) void k_lidar_ray_losses(const float* __restric
                                                           float alpha_r, float alpha_i, float smooth, float* __restrict__ out, uint32_t* __restrict__ stats) {
     const uint32_t n = blockIdx.x * 256u + threadIdx.x;
     if (n >= N) return;
-    const float m = gt_rd[n];
-    const float gd = gt_d[n] * m, gi = gt_i[n] * m;
-    const float pd = depth[n] * m, pr = image[2 * (size_t)n], pi = image[2 * (size_t)n + 1] * m;
-    const float tr = fminf(fmaxf(m, smooth), 1.0f - smooth);
-    const float er = pr - tr, ei = pi - gi;
-    const float v = alpha_d * fabsf(pd - gd) + alpha_r * (er * er) + alpha_i * (ei * ei);
+    const LidarRay t = lidar_ray(image, depth, gt_rd, gt_i, gt_d, n, smooth);
+    const float er = t.pr - t.tr, ei = t.pi - t.gi;
+    const float v = alpha_d * fabsf(t.pd - t.gd) + alpha_r * (er * er) + alpha_i * (ei * ei);
     out[n] = v;
-    if (stats && v >= 0.0f) { atomicMin(stats, __float_as_uint(v)); atomicMax(stats + 1, __float_as_uint(v)); }
+    min_max_bits(stats, v);
 }
 __global__ __launch_bounds__(256) void k_mse_rows(const float* __restrict__ a, const float* __restrict__ b, uint32_t N, uint32_t C, float alpha,
                                                   float* __restrict__ out, uint32_t* __restrict__ stats) {
@@ -395,32 +394,29 @@ __global__ __launch_bounds__(256) void k_mse_rows(const float* __restrict__ a, c
         v += alpha * (e * e);
     }
     out[n] = v;
-    if (stats && v >= 0.0f) { atomicMin(stats, __float_as_uint(v)); atomicMax(stats + 1, __float_as_uint(v)); }
+    min_max_bits(stats, v);
 }
 // error = (loss - min) / (max - min + eps) * 999 + 1; cell = (floor(h eH / H), floor(w eW / W)); map[cell] = 0.1 map[cell] + 0.9 error.
 // Several rays of a batch may fall into one cell: the reference's indexed assignment keeps an unspecified one of them (each computed
 // from the OLD map value); here the ray with the LARGEST index wins (what a sequential execution of the assignment gives): pass 1
 // leaves max(ray index + 1) per touched cell in `owner` (zero on entry), pass 2 lets that ray write and clears the slot again.
+__device__ __forceinline__ size_t error_map_cell(long long ind, uint32_t W, uint32_t eH, uint32_t eW, float sh, float sw) {
+    const uint32_t h = (uint32_t)(ind / (long long)W), w = (uint32_t)(ind % (long long)W);
+    const uint32_t ch = (uint32_t)((float)h * sh), cw = (uint32_t)((float)w * sw);
+    return (size_t)(ch < eH ? ch : eH - 1) * eW + (cw < eW ? cw : eW - 1);  // (a caller-side scale that rounds up: stay inside the map)
+}
 __global__ __launch_bounds__(256) void k_error_map_claim(const long long* __restrict__ inds, uint32_t N, uint32_t W, uint32_t eH, uint32_t eW,
                                                          float sh, float sw, uint32_t* __restrict__ owner) {
     const uint32_t n = blockIdx.x * 256u + threadIdx.x;
     if (n >= N) return;
-    const uint32_t h = (uint32_t)(inds[n] / (long long)W), w = (uint32_t)(inds[n] % (long long)W);
-    uint32_t ch = (uint32_t)((float)h * sh), cw = (uint32_t)((float)w * sw);
-    ch = ch < eH ? ch : eH - 1;  // (a caller-side scale that rounds up: stay inside the map)
-    cw = cw < eW ? cw : eW - 1;
-    atomicMax(owner + (size_t)ch * eW + cw, n + 1u);
+    atomicMax(owner + error_map_cell(inds[n], W, eH, eW, sh, sw), n + 1u);
 }
 __global__ __launch_bounds__(256) void k_error_map_write(const float* __restrict__ loss, const long long* __restrict__ inds, uint32_t N,
                                                          uint32_t W, uint32_t eH, uint32_t eW, float sh, float sw, const uint32_t* __restrict__ stats,
                                                          uint32_t* __restrict__ owner, float* __restrict__ map) {
     const uint32_t n = blockIdx.x * 256u + threadIdx.x;
     if (n >= N) return;
-    const uint32_t h = (uint32_t)(inds[n] / (long long)W), w = (uint32_t)(inds[n] % (long long)W);
-    uint32_t ch = (uint32_t)((float)h * sh), cw = (uint32_t)((float)w * sw);
-    ch = ch < eH ? ch : eH - 1;
-    cw = cw < eW ? cw : eW - 1;
-    const size_t cell = (size_t)ch * eW + cw;
+    const size_t cell = error_map_cell(inds[n], W, eH, eW, sh, sw);
     if (owner[cell] != n + 1u) return;
     const float lo = __uint_as_float(stats[0]), hi = __uint_as_float(stats[1]);
     float e = (loss[n] - lo) / (hi - lo + 1.1920928955078125e-07f);  // torch.finfo().eps
@@ -429,6 +425,12 @@ __global__ __launch_bounds__(256) void k_error_map_write(const float* __restrict
     owner[cell] = 0u;
 }
 }  // namespace
+
+// criterion codes 0 .. 4; Huber (2) and SmoothL1 (3) need their positive parameter
+static inline bool criterion_ok(int kind, float param) { return kind >= 0 && kind <= 4 && (kind < 2 || kind == 4 || param > 0.0f); }
+static inline bool patch_geom_ok(uint32_t N, uint32_t pH, uint32_t pW, uint32_t H, uint32_t W, float scale) {
+    return pH >= 2 && pW >= 2 && N % (pH * pW) == 0 && H >= 2 && W >= 2 && scale != 0.0f;
+}
 
 NVSF_API int nvsf_lidar_losses_fwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
                                    const float* gt_range, const float* rays_d, uint32_t N, float alpha_d, float alpha_r, float alpha_i,
@@ -481,7 +483,7 @@ NVSF_API int nvsf_camera_loss_fwd(const float* image, const float* gt_rgb, const
                                   float alpha_rgb, float alpha_rd, float scale, float max_depth, int criterion, float criterion_param,
                                   float* loss_rgb, float* loss_depth, hipStream_t stream) {
     REQUIRE(loss_rgb && loss_depth && N <= (1u << 30));
-    REQUIRE(criterion >= 0 && criterion <= 4 && (criterion < 2 || criterion == 4 || criterion_param > 0.0f) && max_depth == max_depth);
+    REQUIRE(criterion_ok(criterion, criterion_param) && max_depth == max_depth);
     REQUIRE(N == 0 || (image && gt_rgb && depth && gt_depth_m));
     hipLaunchKernelGGL(k_camera_loss_fwd, dim3(1), dim3(kBlock), 0, stream, image, gt_rgb, depth, gt_depth_m, N, alpha_rgb, alpha_rd, scale,
                        max_depth, criterion, criterion_param, loss_rgb, loss_depth);
@@ -492,8 +494,7 @@ NVSF_API int nvsf_camera_loss_bwd(const float* image, const float* gt_rgb, const
                                   float alpha_rgb, float alpha_rd, float scale, float max_depth, int criterion, float criterion_param,
                                   const float* grad_loss_rgb, const float* grad_loss_depth, float* grad_image, float* grad_depth,
                                   hipStream_t stream) {
-    REQUIRE(N <= (1u << 30));
-    REQUIRE(criterion >= 0 && criterion <= 4 && (criterion < 2 || criterion == 4 || criterion_param > 0.0f) && max_depth == max_depth);
+    REQUIRE(N <= (1u << 30) && criterion_ok(criterion, criterion_param) && max_depth == max_depth);
     if (N == 0) return NVSF_OK;
     REQUIRE(image && gt_rgb && depth && gt_depth_m && grad_image && grad_depth);
     hipLaunchKernelGGL(k_camera_loss_bwd, dim3(cdiv(N, 256)), dim3(256), 0, stream, image, gt_rgb, depth, gt_depth_m, N, alpha_rgb, alpha_rd, scale,
@@ -508,8 +509,7 @@ NVSF_API int nvsf_lidar_grad_loss_fwd(const float* pred_depth, const float* gt_d
     REQUIRE(loss);
     if (N == 0) return hipMemsetAsync(loss, 0, 4, stream) == hipSuccess ? NVSF_OK : (int)hipGetLastError();
     REQUIRE(pred_depth && gt_depth && gt_raydrop && pano_inds && pano_range && pano_stride >= 1);
-    REQUIRE(patch_h >= 2 && patch_w >= 2 && N % (patch_h * patch_w) == 0 && H >= 2 && W >= 2 && scale != 0.0f);
-    REQUIRE(criterion >= 0 && criterion <= 4 && (criterion < 2 || criterion == 4 || criterion_param > 0.0f) && (criterion != 4 || patch_stats));
+    REQUIRE(patch_geom_ok(N, patch_h, patch_w, H, W, scale) && criterion_ok(criterion, criterion_param) && (criterion != 4 || patch_stats));
     const PatchGeom g = {patch_h, patch_w, H, W, scale};
     hipLaunchKernelGGL(k_lidar_grad_loss_fwd, dim3(1), dim3(kBlock), 0, stream, pred_depth, gt_depth, gt_raydrop,
                        reinterpret_cast<const long long*>(pano_inds), pano_range, pano_stride, N, g, criterion, criterion_param, alpha, sobel,
@@ -523,8 +523,7 @@ NVSF_API int nvsf_lidar_grad_loss_bwd(const float* pred_depth, const float* gt_d
                                       const float* patch_stats, const float* grad_loss, float* grad_pred_depth, hipStream_t stream) {
     if (N == 0) return NVSF_OK;
     REQUIRE(pred_depth && gt_depth && gt_raydrop && pano_inds && pano_range && pano_stride >= 1 && grad_loss && grad_pred_depth);
-    REQUIRE(patch_h >= 2 && patch_w >= 2 && N % (patch_h * patch_w) == 0 && H >= 2 && W >= 2 && scale != 0.0f);
-    REQUIRE(criterion >= 0 && criterion <= 4 && (criterion < 2 || criterion == 4 || criterion_param > 0.0f) && (criterion != 4 || patch_stats));
+    REQUIRE(patch_geom_ok(N, patch_h, patch_w, H, W, scale) && criterion_ok(criterion, criterion_param) && (criterion != 4 || patch_stats));
     const PatchGeom g = {patch_h, patch_w, H, W, scale};
     hipLaunchKernelGGL(k_lidar_grad_loss_bwd, dim3(cdiv(N, 256)), dim3(256), 0, stream, pred_depth, gt_depth, gt_raydrop,
                        reinterpret_cast<const long long*>(pano_inds), pano_range, pano_stride, N, g, criterion, criterion_param, alpha, sobel,

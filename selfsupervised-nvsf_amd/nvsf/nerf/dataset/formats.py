@@ -265,7 +265,7 @@ class FrameSet:
 
     def enable_error_maps(self):
         """The sampler's per-frame error maps as base_dataset.py:243-246 creates them: ones, [F, H_lidar / 2, W_lidar / 2] for the range
-        image and [F, H / 4, W / 4] for the camera image (updated by RenderTrainStep.update_error_maps, trainer.py:552-630)."""
+        image and [F, H / 4, W / 4] for the camera image (updated by nerf.losses.update_error_map after every step, trainer.py:552-630)."""
         n = len(self)
         self.error_map = torch.ones(n, int(self.H_lidar / 2), int(self.W_lidar / 2), dtype=torch.float32, device=self.device)
         self.error_map_rgb = torch.ones(n, int(self.H / 4), int(self.W / 4), dtype=torch.float32, device=self.device)

@@ -1,0 +1,246 @@
+"""The loss terms of the training step (nvsf/nerf/train_step.py): the Python half of csrc/losses.hip.
+
+Restated from the reference's `Trainer.train_step` (nvsf/nerf/trainer.py:153-656) with the default CLI settings of
+nvsf/scripts/main_nvsf.py:60-97; nothing here depends on the step object:
+  * LiDAR: ground truth masked by the ray-drop channel (trainer.py:186-189), predictions masked the same way (:203-206),
+    per-ray L1 range (alpha_d 1) + MSE ray-drop against label-smoothed targets (`--smooth_factor`, default 0.0; alpha_r 0.01)
+    + MSE intensity (alpha_i 0.1), all `reduction="none"` and SUMMED over the rays (main_nvsf.py:205-221, trainer.py:540-543);
+    the predicted and the true point cloud `rays_d * depth / scale` of the chamfer term (trainer.py:229-233): `LidarLossFn`,
+    `lidar_losses_host`; URF line-of-sight loss (trainer.py:276-294): `urf_line_of_sight_loss`;
+  * camera: MSE RGB summed over rays and channels (alpha_rgb 1; trainer.py:491-503): `MseSumFn`; optional depth term against the
+    LiDAR-projected camera depth map (`--use_rgbd_loss`, trainer.py:505-518: both capped at 80 m, masked where the map is empty,
+    summed): `CameraLossFn`, `rgb_depth_loss_host`;
+  * the structural regularisation on LiDAR patches in its `grad_loss` form (trainer.py:296-470: first differences (or Sobel
+    gradients) of the rendered / true range inside pH x pW patches, masked by the true ray-drop channel and the flatness of the true
+    frame; criteria `--depth_grad_loss` l1 / mse / huber / smoothl1 / cos, `--sobel_grad`): `LidarGradLossFn`;
+  * the error maps the patch sampler draws from (trainer.py:552-630): `update_error_map`.
+"""
+import math
+
+import torch
+
+
+def _f32(t):
+    return t.detach().float().contiguous()
+
+
+def _f32_or_none(t):
+    return None if t is None else t.float().contiguous()
+
+
+def criterion_code(criterion, scale, table, option):
+    """Criterion name -> (kernel code of `table`, parameter): Huber delta = 0.2 x scale, SmoothL1 beta = 0.1 (main_nvsf.py:207-209).
+    option: (name, line) of the CLI option, for the error text."""
+    if criterion not in table:
+        raise ValueError(f"{option[0]}={criterion!r}: one of {sorted(table)} (main_nvsf.py:{option[1]})")
+    param = 0.2 * float(scale) if criterion == "huber" else (0.1 if criterion == "smoothl1" else 0.0)
+    return table[criterion], param
+
+
+def urf_line_of_sight_loss(weights, z_vals, gt_depth, eps):
+    """Line-of-sight loss of Urban Radiance Fields as written at trainer.py:276-294."""
+    gt = gt_depth.reshape(z_vals.shape[0], 1)
+    n_valid = (gt > 0.0).sum()
+    empty = (z_vals < gt - eps) | (z_vals > gt + eps)
+    loss_empty = ((empty * weights) ** 2).sum() / n_valid
+    near = (z_vals > gt - eps) & (z_vals < gt + eps)
+    distance = near * (z_vals - gt)
+    sigma = eps / 3.0
+    distr = 1.0 / (sigma * math.sqrt(2 * math.pi)) * torch.exp(-(distance ** 2 / (2 * sigma ** 2)))
+    distr = distr / distr.max()
+    distr = distr * near
+    loss_near = ((near * weights - distr) ** 2).sum() / n_valid
+    return 0.1 * loss_empty + 0.1 * loss_near
+
+
+class LidarLossFn(torch.autograd.Function):
+    """The LiDAR terms of Trainer.train_step (trainer.py:187-219) as one HIP launch forward and one backward (csrc/losses.hip): at
+    4096 rays each of the ~60 elementwise / reduction launches the expression costs under autograd is a launch latency.
+    Returns (loss_depth, loss_raydrop, loss_intensity, pred_depth [1,N], pred_points [1,N,3], gt_points [1,N,3]); the point clouds
+    are the inputs of the chamfer term (None when `rays_d` is None)."""
+
+    @staticmethod
+    def forward(ctx, image_lidar, depth_lidar, gt_rd, gt_i, gt_d, rays_d, alpha_d, alpha_r, alpha_i, smooth, scale):
+        from nvsf import _hip
+        N, dev = depth_lidar.numel(), depth_lidar.device
+        img, dep, rd, gi, gd = _f32(image_lidar), _f32(depth_lidar), _f32(gt_rd), _f32(gt_i), _f32(gt_d)
+        dirs = _f32(rays_d) if rays_d is not None else None
+        l = [torch.empty((), dtype=torch.float32, device=dev) for _ in range(3)]
+        pred_depth = torch.empty(1, N, dtype=torch.float32, device=dev)
+        pp = torch.empty(1, N, 3, dtype=torch.float32, device=dev) if dirs is not None else None
+        gp = torch.empty(1, N, 3, dtype=torch.float32, device=dev) if dirs is not None else None
+        _hip.call("nvsf_lidar_losses_fwd", _hip.ptr(img), _hip.ptr(dep), _hip.ptr(rd), _hip.ptr(gi), _hip.ptr(gd), _hip.ptr(dirs), N,
+                  float(alpha_d), float(alpha_r), float(alpha_i), float(smooth), float(scale), _hip.ptr(l[0]), _hip.ptr(l[1]), _hip.ptr(l[2]),
+                  _hip.ptr(pred_depth), _hip.ptr(pp), _hip.ptr(gp))
+        ctx.save_for_backward(img, dep, rd, gi, gd, dirs)
+        ctx.consts = (float(alpha_d), float(alpha_r), float(alpha_i), float(smooth), float(scale), image_lidar.shape, depth_lidar.shape)
+        if gp is not None:
+            ctx.mark_non_differentiable(gp)
+        return l[0], l[1], l[2], pred_depth, pp, gp
+
+    @staticmethod
+    def backward(ctx, g_d, g_r, g_i, g_pd, g_pp, _g_gp):
+        from nvsf import _hip
+        img, dep, rd, gi, gd, dirs = ctx.saved_tensors
+        a_d, a_r, a_i, smooth, scale, shape_img, shape_dep = ctx.consts
+        N = dep.numel()
+        g_d, g_r, g_i, g_pd, g_pp = (_f32_or_none(g) for g in (g_d, g_r, g_i, g_pd, g_pp))
+        grad_img, grad_dep = torch.empty_like(img), torch.empty_like(dep)
+        _hip.call("nvsf_lidar_losses_bwd", _hip.ptr(img), _hip.ptr(dep), _hip.ptr(rd), _hip.ptr(gi), _hip.ptr(gd), _hip.ptr(dirs), N,
+                  a_d, a_r, a_i, smooth, scale, _hip.ptr(g_d), _hip.ptr(g_r), _hip.ptr(g_i), _hip.ptr(g_pd), _hip.ptr(g_pp),
+                  _hip.ptr(grad_img), _hip.ptr(grad_dep))
+        return (grad_img.view(shape_img), grad_dep.view(shape_dep)) + (None,) * 9
+
+
+def lidar_losses_host(image_lidar, depth_lidar, gt_rd, gt_i, gt_d, rays_d, alpha_d, alpha_r, alpha_i, smooth, scale):
+    """LidarLossFn as torch expressions (trainer.py:187-219, 229-233): the host branch of `RenderTrainStep.losses`.  Same arguments and
+    the same six results."""
+    gt_int, gt_depth = gt_i * gt_rd, gt_d * gt_rd  # trainer.py:187-189
+    pred_rd = image_lidar[:, :, 0]
+    pred_int = image_lidar[:, :, 1] * gt_rd
+    pred_depth = depth_lidar * gt_rd
+    l_depth = (alpha_d * (pred_depth - gt_depth).abs()).sum()
+    l_raydrop = (alpha_r * (pred_rd - gt_rd.clamp(smooth, 1 - smooth)) ** 2).sum()
+    l_intensity = (alpha_i * (pred_int - gt_int) ** 2).sum()
+    pred_pts, gt_pts = (None, None) if rays_d is None else (rays_d * pred_depth.unsqueeze(-1) / scale, rays_d * gt_depth.unsqueeze(-1) / scale)
+    return l_depth, l_raydrop, l_intensity, pred_depth, pred_pts, gt_pts
+
+
+class MseSumFn(torch.autograd.Function):
+    """sum(alpha (a - b)^2) -- the camera term (trainer.py:491-503, summed at :540-543) -- as one launch each way."""
+
+    @staticmethod
+    def forward(ctx, a, b, alpha):
+        from nvsf import _hip
+        a32, b32 = _f32(a), _f32(b)
+        out = torch.empty((), dtype=torch.float32, device=a.device)
+        _hip.call("nvsf_mse_sum_fwd", _hip.ptr(a32), _hip.ptr(b32), a32.numel(), float(alpha), _hip.ptr(out))
+        ctx.save_for_backward(a32, b32)
+        ctx.alpha, ctx.shape = float(alpha), a.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from nvsf import _hip
+        a32, b32 = ctx.saved_tensors
+        grad = torch.empty_like(a32)
+        _hip.call("nvsf_mse_sum_bwd", _hip.ptr(a32), _hip.ptr(b32), a32.numel(), ctx.alpha, _hip.ptr(_f32_or_none(g)), _hip.ptr(grad))
+        return grad.view(ctx.shape), None, None
+
+
+class CameraLossFn(torch.autograd.Function):
+    """The two camera terms of Trainer.train_step with `--use_rgbd_loss` (trainer.py:491-518) as one launch each way
+    (nvsf_camera_loss_fwd / _bwd): sum alpha_rgb (image - gt_rgb)^2 and the depth term against the LiDAR-projected depth map --
+    gt = gt_depth_m * scale capped at 80 * scale, the rendered depth capped the same way (a capped ray gets no gradient), mask = gt > 0,
+    alpha_rd * sum criterion(depth * mask, gt * mask).  criterion: `--rgb_depth_loss` (main_nvsf.py:91, 205-212).
+    Returns (loss_rgb, loss_rgb_depth)."""
+    CRITERIA = {"l1": 0, "mse": 1, "huber": 2, "smoothl1": 3, "bce": 4}  # no "cos": CosineSimilarity over dim 1 of a [B, N] pair is no per-ray loss
+
+    @staticmethod
+    def criterion_code(criterion, scale):
+        return criterion_code(criterion, scale, CameraLossFn.CRITERIA, ("rgb_depth_loss", 91))
+
+    @staticmethod
+    def forward(ctx, image, depth, gt_rgb, gt_depth_m, alpha_rgb, alpha_rd, scale, criterion):
+        from nvsf import _hip
+        kind, param = CameraLossFn.criterion_code(criterion, scale)
+        img, dep, rgb, gtd = _f32(image), _f32(depth), _f32(gt_rgb), _f32(gt_depth_m)
+        N = dep.numel()
+        if img.numel() != 3 * N or rgb.numel() != 3 * N or gtd.numel() != N:
+            raise ValueError(f"CameraLossFn: image {tuple(image.shape)}, gt_rgb {tuple(gt_rgb.shape)}, depth {tuple(depth.shape)} and "
+                             f"gt_rgb_depth {tuple(gt_depth_m.shape)} do not describe one ray batch")
+        out = [torch.empty((), dtype=torch.float32, device=dep.device) for _ in range(2)]
+        args = (_hip.ptr(img), _hip.ptr(rgb), _hip.ptr(dep), _hip.ptr(gtd), N, float(alpha_rgb), float(alpha_rd), float(scale),
+                80 * float(scale), kind, float(param))
+        _hip.call("nvsf_camera_loss_fwd", *args, _hip.ptr(out[0]), _hip.ptr(out[1]))
+        ctx.save_for_backward(img, rgb, dep, gtd)
+        ctx.args, ctx.shapes = args, (image.shape, depth.shape)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth):
+        from nvsf import _hip
+        img, _, dep, _ = ctx.saved_tensors
+        g_rgb, g_depth = _f32_or_none(g_rgb), _f32_or_none(g_depth)
+        grad_img, grad_dep = torch.empty_like(img), torch.empty_like(dep)
+        _hip.call("nvsf_camera_loss_bwd", *ctx.args, _hip.ptr(g_rgb), _hip.ptr(g_depth), _hip.ptr(grad_img), _hip.ptr(grad_dep))
+        return (grad_img.view(ctx.shapes[0]), grad_dep.view(ctx.shapes[1])) + (None,) * 6
+
+
+def rgb_depth_loss_host(depth, gt_depth_m, scale, criterion, alpha_rd):
+    """The depth term of CameraLossFn as torch expressions (trainer.py:506-518): the host branch of `RenderTrainStep.losses` and the
+    formulation the device kernels are tested against."""
+    _, param = CameraLossFn.criterion_code(criterion, scale)
+    crit = {"l1": torch.nn.L1Loss, "mse": torch.nn.MSELoss, "bce": torch.nn.BCEWithLogitsLoss,
+            "smoothl1": lambda **kw: torch.nn.SmoothL1Loss(beta=param, **kw),
+            "huber": lambda **kw: torch.nn.HuberLoss(delta=param, **kw)}[criterion](reduction="none")
+    max_depth = 80 * scale
+    gt = (gt_depth_m * scale).clamp(max=max_depth)
+    pred = torch.where(depth > max_depth, torch.full_like(depth, max_depth), depth)  # assignment into the tensor: no gradient there
+    mask = (gt > 0).to(pred.dtype)
+    return (alpha_rd * crit(pred * mask, gt * mask)).sum()
+
+
+class LidarGradLossFn(torch.autograd.Function):
+    """Structural regularisation of trainer.py:296-470 in its `grad_loss` form as one launch each way (nvsf_lidar_grad_loss_fwd / _bwd):
+    pred_depth, gt_depth [1, N] the masked ranges (scene units), gt_raydrop [1, N], pano_inds int64 [1, N] pixel indices of the batch
+    (N / (pH pW) patches in patch order), pano_frame [H, W, 3] (or [1, H, W, 3]) the frame's ground truth (channel 2 = range x scale).
+    criterion: `--depth_grad_loss` (main_nvsf.py:86, 204-221); sobel: `--sobel_grad` (:107)."""
+    CRITERIA = {"l1": 0, "mse": 1, "huber": 2, "smoothl1": 3, "cos": 4}
+
+    @staticmethod
+    def forward(ctx, pred_depth, gt_depth, gt_raydrop, pano_inds, pano_frame, patch, scale, criterion, alpha, sobel=False):
+        from nvsf import _hip
+        kind, param = criterion_code(criterion, scale, LidarGradLossFn.CRITERIA, ("depth_grad_loss", 86))
+        pd, gd, rd = _f32(pred_depth), _f32(gt_depth), _f32(gt_raydrop)
+        inds = pano_inds.detach().long().contiguous()
+        frame = pano_frame.detach().float()
+        frame = frame[0] if frame.dim() == 4 else frame
+        frame = frame.contiguous()
+        H, W, C = frame.shape
+        if C < 3:  # the reference reads data['pano_frame'][0, ..., 2] (trainer.py:296-470): the range channel is channel 2
+            raise ValueError(f"LidarGradLossFn: pano_frame needs >= 3 channels [raydrop, intensity, range], got {C}")
+        pH, pW = int(patch[0]), int(patch[1])
+        N = pd.numel()
+        out = torch.empty((), dtype=torch.float32, device=pd.device)
+        stats = torch.empty(N // (pH * pW), 6, dtype=torch.float32, device=pd.device) if criterion == "cos" else None
+        args = (_hip.ptr(pd), _hip.ptr(gd), _hip.ptr(rd), _hip.ptr(inds), frame.data_ptr() + 4 * 2, C, N, pH, pW, H, W,
+                float(scale), kind, float(param), float(alpha), 1 if sobel else 0, _hip.ptr(stats))
+        _hip.call("nvsf_lidar_grad_loss_fwd", *args, _hip.ptr(out))
+        ctx.save_for_backward(pd, gd, rd, inds, frame, *(() if stats is None else (stats,)))
+        ctx.args, ctx.shape = args, pred_depth.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from nvsf import _hip
+        pd = ctx.saved_tensors[0]
+        grad = torch.empty_like(pd)
+        _hip.call("nvsf_lidar_grad_loss_bwd", *ctx.args, _hip.ptr(_f32_or_none(g)), _hip.ptr(grad))
+        return (grad.view(ctx.shape),) + (None,) * 9
+
+
+def update_error_map(frames, idx, modality, stash, inds, alphas, smooth=0.0):
+    """trainer.py:552-630 on the device for one modality of frame `idx` of the FrameSet `frames`: per-ray loss -> min / max ->
+    normalised to [1, 1000] -> EMA into the frame's coarse map at the rays' pixels `inds` (a handful of small launches, no host read).
+    modality "lidar": stash = (image_lidar, depth_lidar, gt_raydrop, gt_intensity, gt_range), alphas = (alpha_d, alpha_r, alpha_i);
+    "camera": stash = (image, gt_rgb), alphas = (alpha_rgb,).  A FrameSet without that modality's map is left alone."""
+    from nvsf import _hip
+    lidar = modality == "lidar"
+    emap, H, W = (frames.error_map, frames.H_lidar, frames.W_lidar) if lidar else (frames.error_map_rgb, frames.H, frames.W)
+    if emap is None:
+        return
+    inds = inds.detach().long().contiguous().view(-1)
+    N, dev = inds.numel(), inds.device
+    ray_loss = torch.empty(N, dtype=torch.float32, device=dev)
+    stats = frames.error_map_stats(dev)
+    if lidar:
+        img, dep, rd, gi, gd = (_f32(t) for t in stash)
+        _hip.call("nvsf_lidar_ray_losses", _hip.ptr(img), _hip.ptr(dep), _hip.ptr(rd), _hip.ptr(gi), _hip.ptr(gd), N, *alphas, smooth,
+                  _hip.ptr(ray_loss), _hip.ptr(stats))
+    else:
+        img, gt = (_f32(t) for t in stash)
+        _hip.call("nvsf_mse_rows", _hip.ptr(img), _hip.ptr(gt), N, img.shape[-1], *alphas, _hip.ptr(ray_loss), _hip.ptr(stats))
+    eH, eW = emap.shape[-2:]
+    _hip.call("nvsf_error_map_update", _hip.ptr(ray_loss), _hip.ptr(inds), N, int(W), emap[idx].data_ptr(), int(eH), int(eW), float(eH / H),
+              float(eW / W), _hip.ptr(stats), _hip.ptr(frames.error_map_owner(dev, eH * eW)))

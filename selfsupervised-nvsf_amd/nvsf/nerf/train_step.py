@@ -1,215 +1,28 @@
-"""Thin multimodal training step; whole-frame evaluation and its metrics live in nvsf/nerf/evaluate.py.
+"""Thin multimodal training step: render, losses, backward, optimiser.  The loss terms themselves live in
+nvsf/nerf/losses.py (the Python half of csrc/losses.hip), whole-frame evaluation and its metrics in nvsf/nerf/evaluate.py.
 
 Only what sits directly around the hot path, restated from the reference's `Trainer.train_step`
 (nvsf/nerf/trainer.py:153-656) with the default CLI settings of nvsf/scripts/main_nvsf.py:60-97:
-  * LiDAR: ground truth masked by the ray-drop channel (trainer.py:186-189), predictions masked the same way (:203-206),
-    per-ray L1 range (alpha_d 1) + MSE ray-drop against label-smoothed targets (`--smooth_factor`, default 0.0; alpha_r 0.01)
-    + MSE intensity (alpha_i 0.1), all `reduction="none"` and SUMMED over the rays (main_nvsf.py:205-221, trainer.py:540-543);
-    chamfer distance between the predicted and the true point cloud `rays_d * depth / scale`, `(d1 + d2).mean() * 0.5`
-    (trainer.py:229-233; it IS part of the total at :542), on csrc/chamfer.hip; optional scene-flow loss (`--flow_loss`,
-    trainer.py:236-267: chamfer between the flow-warped point cloud of the frame and its neighbours' clouds + mean |flow|) and
-    URF line-of-sight loss (trainer.py:276-294);
-  * camera: MSE RGB summed over rays and channels (alpha_rgb 1; trainer.py:491-503); optional depth term against the LiDAR-projected
-    camera depth map (`--use_rgbd_loss`, trainer.py:505-518: both capped at 80 m, masked where the map is empty, summed; `CameraLossFn`);
-  * NaN -> 0, Inf -> 1e5 on the scalar (trainer.py:545-546);
+  * the sum of the loss parts (trainer.py:540-543): the LiDAR and camera terms of losses.py, the chamfer distance between the predicted
+    and the true point cloud, `(d1 + d2).mean() * 0.5` (trainer.py:229-233; it IS part of the total at :542), on csrc/chamfer.hip, the
+    optional scene-flow loss (`--flow_loss`, trainer.py:236-267); NaN -> 0, Inf -> 1e5 on the scalar (trainer.py:545-546);
   * optimiser: Adam(betas 0.9/0.99, eps 1e-15) on `model.get_params(lr)` and the 0.1^(iter/iters) decay
     (main_nvsf.py:350-362), under the GradScaler of the reference's fp16 run (trainer.py:119, 1332-1334);
   * EMA of the weights, decay 0.95, updated once per epoch (trainer.py:112-114, 1420-1421; nvsf/nerf/ema.py).
 Across GPUs the step is frame-sharded: every rank renders its own frame, then ONE bucketed gradient all-reduce
 (nvsf/frame_shard.py).  Checkpoints use the reference's dict (utils.py:622-747).
-Shipped-config extras (configs/kitti360_1908.txt:13-15 `grad_loss`, `use_error_map`): the structural regularisation on LiDAR patches
-in its `grad_loss` form (trainer.py:296-470: first differences (or Sobel gradients) of the rendered / true range inside pH x pW patches, masked by the true
-ray-drop channel and the flatness of the true frame; `LidarGradLossFn`, csrc/losses.hip), the alternation between random pixels and
-patches (trainer.py:1035-1062: `set_epoch`) and the error maps the patch sampler draws from (trainer.py:552-630: `update_error_maps`).
-The regulariser's criteria (`--depth_grad_loss` l1 / mse / huber / smoothl1 / cos) and `--sobel_grad` are built; its three smoothness switches
-fail in the reference itself (see __init__).  Logging is out of scope; the U-Net ray-drop refinement lives in nvsf/nerf/refine.py.
+Shipped-config extras (configs/kitti360_1908.txt:13-15 `grad_loss`, `use_error_map`): the alternation between random pixels and LiDAR
+patches (trainer.py:1035-1062: `set_epoch`) and the write-back into the error maps the patch sampler draws from (`update_error_maps`).
+The regulariser's three smoothness switches fail in the reference itself (see __init__).  Logging is out of scope; the U-Net ray-drop
+refinement lives in nvsf/nerf/refine.py.
 """
-import math
 import warnings
 
 import torch
 
 from nvsf import frame_shard
-
-
-def urf_line_of_sight_loss(weights, z_vals, gt_depth, eps):
-    """Line-of-sight loss of Urban Radiance Fields as written at trainer.py:276-294."""
-    gt = gt_depth.reshape(z_vals.shape[0], 1)
-    n_valid = (gt > 0.0).sum()
-    empty = (z_vals < gt - eps) | (z_vals > gt + eps)
-    loss_empty = ((empty * weights) ** 2).sum() / n_valid
-    near = (z_vals > gt - eps) & (z_vals < gt + eps)
-    distance = near * (z_vals - gt)
-    sigma = eps / 3.0
-    distr = 1.0 / (sigma * math.sqrt(2 * math.pi)) * torch.exp(-(distance ** 2 / (2 * sigma ** 2)))
-    distr = distr / distr.max()
-    distr = distr * near
-    loss_near = ((near * weights - distr) ** 2).sum() / n_valid
-    return 0.1 * loss_empty + 0.1 * loss_near
-
-
-class LidarLossFn(torch.autograd.Function):
-    """The LiDAR terms of Trainer.train_step (trainer.py:187-219) as one HIP launch forward and one backward (csrc/losses.hip): at
-    4096 rays each of the ~60 elementwise / reduction launches the expression costs under autograd is a launch latency.
-    Returns (loss_depth, loss_raydrop, loss_intensity, pred_depth [1,N], pred_points [1,N,3], gt_points [1,N,3]); the point clouds
-    are the inputs of the chamfer term (None when `rays_d` is None)."""
-
-    @staticmethod
-    def forward(ctx, image_lidar, depth_lidar, gt_rd, gt_i, gt_d, rays_d, alpha_d, alpha_r, alpha_i, smooth, scale):
-        from nvsf import _hip
-        N, dev = depth_lidar.numel(), depth_lidar.device
-        c = lambda t: t.detach().float().contiguous()
-        img, dep, rd, gi, gd = c(image_lidar), c(depth_lidar), c(gt_rd), c(gt_i), c(gt_d)
-        dirs = c(rays_d) if rays_d is not None else None
-        l = [torch.empty((), dtype=torch.float32, device=dev) for _ in range(3)]
-        pred_depth = torch.empty(1, N, dtype=torch.float32, device=dev)
-        pp = torch.empty(1, N, 3, dtype=torch.float32, device=dev) if dirs is not None else None
-        gp = torch.empty(1, N, 3, dtype=torch.float32, device=dev) if dirs is not None else None
-        _hip.call("nvsf_lidar_losses_fwd", _hip.ptr(img), _hip.ptr(dep), _hip.ptr(rd), _hip.ptr(gi), _hip.ptr(gd), _hip.ptr(dirs), N,
-                  float(alpha_d), float(alpha_r), float(alpha_i), float(smooth), float(scale), _hip.ptr(l[0]), _hip.ptr(l[1]), _hip.ptr(l[2]),
-                  _hip.ptr(pred_depth), _hip.ptr(pp), _hip.ptr(gp))
-        ctx.save_for_backward(img, dep, rd, gi, gd, dirs)
-        ctx.consts = (float(alpha_d), float(alpha_r), float(alpha_i), float(smooth), float(scale), image_lidar.shape, depth_lidar.shape)
-        if gp is not None:
-            ctx.mark_non_differentiable(gp)
-        return l[0], l[1], l[2], pred_depth, pp, gp
-
-    @staticmethod
-    def backward(ctx, g_d, g_r, g_i, g_pd, g_pp, _g_gp):
-        from nvsf import _hip
-        img, dep, rd, gi, gd, dirs = ctx.saved_tensors
-        a_d, a_r, a_i, smooth, scale, shape_img, shape_dep = ctx.consts
-        N = dep.numel()
-        c = lambda t: None if t is None else t.float().contiguous()
-        g_d, g_r, g_i, g_pd, g_pp = c(g_d), c(g_r), c(g_i), c(g_pd), c(g_pp)
-        grad_img, grad_dep = torch.empty_like(img), torch.empty_like(dep)
-        _hip.call("nvsf_lidar_losses_bwd", _hip.ptr(img), _hip.ptr(dep), _hip.ptr(rd), _hip.ptr(gi), _hip.ptr(gd), _hip.ptr(dirs), N,
-                  a_d, a_r, a_i, smooth, scale, _hip.ptr(g_d), _hip.ptr(g_r), _hip.ptr(g_i), _hip.ptr(g_pd), _hip.ptr(g_pp),
-                  _hip.ptr(grad_img), _hip.ptr(grad_dep))
-        return (grad_img.view(shape_img), grad_dep.view(shape_dep)) + (None,) * 9
-
-
-class MseSumFn(torch.autograd.Function):
-    """sum(alpha (a - b)^2) -- the camera term (trainer.py:491-503, summed at :540-543) -- as one launch each way."""
-
-    @staticmethod
-    def forward(ctx, a, b, alpha):
-        from nvsf import _hip
-        a32, b32 = a.detach().float().contiguous(), b.detach().float().contiguous()
-        out = torch.empty((), dtype=torch.float32, device=a.device)
-        _hip.call("nvsf_mse_sum_fwd", _hip.ptr(a32), _hip.ptr(b32), a32.numel(), float(alpha), _hip.ptr(out))
-        ctx.save_for_backward(a32, b32)
-        ctx.alpha, ctx.shape = float(alpha), a.shape
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        from nvsf import _hip
-        a32, b32 = ctx.saved_tensors
-        grad = torch.empty_like(a32)
-        _hip.call("nvsf_mse_sum_bwd", _hip.ptr(a32), _hip.ptr(b32), a32.numel(), ctx.alpha, _hip.ptr(g.float().contiguous()), _hip.ptr(grad))
-        return grad.view(ctx.shape), None, None
-
-
-class CameraLossFn(torch.autograd.Function):
-    """The two camera terms of Trainer.train_step with `--use_rgbd_loss` (trainer.py:491-518) as one launch each way
-    (nvsf_camera_loss_fwd / _bwd): sum alpha_rgb (image - gt_rgb)^2 and the depth term against the LiDAR-projected depth map --
-    gt = gt_depth_m * scale capped at 80 * scale, the rendered depth capped the same way (a capped ray gets no gradient), mask = gt > 0,
-    alpha_rd * sum criterion(depth * mask, gt * mask).  criterion: `--rgb_depth_loss` (main_nvsf.py:91, 205-212).
-    Returns (loss_rgb, loss_rgb_depth)."""
-    CRITERIA = {"l1": 0, "mse": 1, "huber": 2, "smoothl1": 3, "bce": 4}
-
-    @staticmethod
-    def criterion_code(criterion, scale):
-        if criterion not in CameraLossFn.CRITERIA:  # "cos": CosineSimilarity over dim 1 of a [B, N] pair is no per-ray loss
-            raise ValueError(f"rgb_depth_loss={criterion!r}: one of {sorted(CameraLossFn.CRITERIA)} (main_nvsf.py:91)")
-        param = 0.2 * float(scale) if criterion == "huber" else (0.1 if criterion == "smoothl1" else 0.0)  # main_nvsf.py:208-209
-        return CameraLossFn.CRITERIA[criterion], param
-
-    @staticmethod
-    def forward(ctx, image, depth, gt_rgb, gt_depth_m, alpha_rgb, alpha_rd, scale, criterion):
-        from nvsf import _hip
-        kind, param = CameraLossFn.criterion_code(criterion, scale)
-        c = lambda t: t.detach().float().contiguous()
-        img, dep, rgb, gtd = c(image), c(depth), c(gt_rgb), c(gt_depth_m)
-        N = dep.numel()
-        if img.numel() != 3 * N or rgb.numel() != 3 * N or gtd.numel() != N:
-            raise ValueError(f"CameraLossFn: image {tuple(image.shape)}, gt_rgb {tuple(gt_rgb.shape)}, depth {tuple(depth.shape)} and "
-                             f"gt_rgb_depth {tuple(gt_depth_m.shape)} do not describe one ray batch")
-        out = [torch.empty((), dtype=torch.float32, device=dep.device) for _ in range(2)]
-        args = (_hip.ptr(img), _hip.ptr(rgb), _hip.ptr(dep), _hip.ptr(gtd), N, float(alpha_rgb), float(alpha_rd), float(scale),
-                80 * float(scale), kind, float(param))
-        _hip.call("nvsf_camera_loss_fwd", *args, _hip.ptr(out[0]), _hip.ptr(out[1]))
-        ctx.save_for_backward(img, rgb, dep, gtd)
-        ctx.args, ctx.shapes = args, (image.shape, depth.shape)
-        return out[0], out[1]
-
-    @staticmethod
-    def backward(ctx, g_rgb, g_depth):
-        from nvsf import _hip
-        img, _, dep, _ = ctx.saved_tensors
-        c = lambda t: None if t is None else t.float().contiguous()
-        g_rgb, g_depth = c(g_rgb), c(g_depth)
-        grad_img, grad_dep = torch.empty_like(img), torch.empty_like(dep)
-        _hip.call("nvsf_camera_loss_bwd", *ctx.args, _hip.ptr(g_rgb), _hip.ptr(g_depth), _hip.ptr(grad_img), _hip.ptr(grad_dep))
-        return (grad_img.view(ctx.shapes[0]), grad_dep.view(ctx.shapes[1])) + (None,) * 6
-
-
-def rgb_depth_loss_host(depth, gt_depth_m, scale, criterion, alpha_rd):
-    """The depth term of CameraLossFn as torch expressions (trainer.py:506-518): the host branch of `losses` and the formulation the
-    device kernels are tested against."""
-    CameraLossFn.criterion_code(criterion, scale)
-    crit = {"l1": torch.nn.L1Loss(reduction="none"), "mse": torch.nn.MSELoss(reduction="none"),
-            "smoothl1": torch.nn.SmoothL1Loss(reduction="none", beta=0.1), "huber": torch.nn.HuberLoss(reduction="none", delta=0.2 * scale),
-            "bce": torch.nn.BCEWithLogitsLoss(reduction="none")}[criterion]
-    max_depth = 80 * scale
-    gt = (gt_depth_m * scale).clamp(max=max_depth)
-    pred = torch.where(depth > max_depth, torch.full_like(depth, max_depth), depth)  # assignment into the tensor: no gradient there
-    mask = (gt > 0).to(pred.dtype)
-    return (alpha_rd * crit(pred * mask, gt * mask)).sum()
-
-
-class LidarGradLossFn(torch.autograd.Function):
-    """Structural regularisation of trainer.py:296-470 in its `grad_loss` form as one launch each way (nvsf_lidar_grad_loss_fwd / _bwd):
-    pred_depth, gt_depth [1, N] the masked ranges (scene units), gt_raydrop [1, N], pano_inds int64 [1, N] pixel indices of the batch
-    (N / (pH pW) patches in patch order), pano_frame [H, W, 3] (or [1, H, W, 3]) the frame's ground truth (channel 2 = range x scale).
-    criterion: `--depth_grad_loss` (main_nvsf.py:86, 204-221); sobel: `--sobel_grad` (:107)."""
-    CRITERIA = {"l1": 0, "mse": 1, "huber": 2, "smoothl1": 3, "cos": 4}
-
-    @staticmethod
-    def forward(ctx, pred_depth, gt_depth, gt_raydrop, pano_inds, pano_frame, patch, scale, criterion, alpha, sobel=False):
-        from nvsf import _hip
-        if criterion not in LidarGradLossFn.CRITERIA:
-            raise ValueError(f"depth_grad_loss={criterion!r}: one of {sorted(LidarGradLossFn.CRITERIA)} (main_nvsf.py:86)")
-        c = lambda t: t.detach().float().contiguous()
-        pd, gd, rd = c(pred_depth), c(gt_depth), c(gt_raydrop)
-        inds = pano_inds.detach().long().contiguous()
-        frame = pano_frame.detach().float()
-        frame = frame[0] if frame.dim() == 4 else frame
-        frame = frame.contiguous()
-        H, W, C = frame.shape
-        if C < 3:  # the reference reads data['pano_frame'][0, ..., 2] (trainer.py:296-470): the range channel is channel 2
-            raise ValueError(f"LidarGradLossFn: pano_frame needs >= 3 channels [raydrop, intensity, range], got {C}")
-        pH, pW = int(patch[0]), int(patch[1])
-        N = pd.numel()
-        kind = LidarGradLossFn.CRITERIA[criterion]
-        param = 0.2 * float(scale) if criterion == "huber" else (0.1 if criterion == "smoothl1" else 0.0)  # main_nvsf.py:207-208
-        out = torch.empty((), dtype=torch.float32, device=pd.device)
-        stats = torch.empty(N // (pH * pW), 6, dtype=torch.float32, device=pd.device) if criterion == "cos" else None
-        args = (_hip.ptr(pd), _hip.ptr(gd), _hip.ptr(rd), _hip.ptr(inds), frame.data_ptr() + 4 * 2, C, N, pH, pW, H, W,
-                float(scale), kind, float(param), float(alpha), 1 if sobel else 0, _hip.ptr(stats))
-        _hip.call("nvsf_lidar_grad_loss_fwd", *args, _hip.ptr(out))
-        ctx.save_for_backward(pd, gd, rd, inds, frame, *(() if stats is None else (stats,)))
-        ctx.args, ctx.shape = args, pred_depth.shape
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        from nvsf import _hip
-        pd = ctx.saved_tensors[0]
-        grad = torch.empty_like(pd)
-        _hip.call("nvsf_lidar_grad_loss_bwd", *ctx.args, _hip.ptr(g.float().contiguous()), _hip.ptr(grad))
-        return (grad.view(ctx.shape),) + (None,) * 9
+from nvsf.nerf.losses import (CameraLossFn, LidarGradLossFn, LidarLossFn, MseSumFn, lidar_losses_host, rgb_depth_loss_host,
+                              update_error_map, urf_line_of_sight_loss)
 
 
 class RenderTrainStep:
@@ -374,35 +187,26 @@ class RenderTrainStep:
                 gt_rd, gt_i, gt_d = batch["gt_raydrop"], batch["gt_intensity"], batch["gt_depth"]
             r = self._render(batch["rays_o_lidar"], batch["rays_d_lidar"], batch["time"], cal_lidar_color=True, perturb=True,
                              num_steps=self.num_steps)
-            if r["depth_lidar"].is_cuda:  # one HIP launch each way for the three sums, the masked range and the chamfer point clouds
-                d = batch["rays_d_lidar"] if self.use_chamfer else None
-                out["depth"], out["raydrop"], out["intensity"], pred_depth, pred_pts, gt_pts = LidarLossFn.apply(
-                    r["image_lidar"], r["depth_lidar"], gt_rd, gt_i, gt_d, d, self.alpha_d, self.alpha_r, self.alpha_i, self.smooth, self.scale)
-                if self.use_chamfer:
-                    d1, d2, _, _ = self._chamfer(pred_pts, gt_pts)
-                    out["chamfer"] = (d1 + d2).mean() * 0.5
-                pH, pW = self._patch_dims()
-                if pH > 1 and self.grad_loss:
-                    if "rays_pano_inds" not in batch or "pano_frame" not in batch:
-                        raise ValueError("grad_loss on LiDAR patches needs batch['rays_pano_inds'] and batch['pano_frame'] (FrameSet.train_batch)")
-                    out["sr"] = LidarGradLossFn.apply(pred_depth, gt_d * gt_rd, gt_rd, batch["rays_pano_inds"], batch["pano_frame"], (pH, pW),
-                                                      self.scale, self.depth_grad_loss, self.alpha_grad, self.sobel_grad)
-                if self.error_maps is not None:
-                    self._for_error_map["lidar"] = (r["image_lidar"].detach(), r["depth_lidar"].detach(), gt_rd, gt_i, gt_d)
-            else:  # host-side logic tests: the same terms as torch expressions
-                if self.grad_loss and self._patch_dims()[0] > 1:
-                    raise NotImplementedError("grad_loss (the structural regulariser on LiDAR patches) exists as HIP kernels only: the host branch would drop the 'sr' term silently")
-                gt_int, gt_depth = gt_i * gt_rd, gt_d * gt_rd  # trainer.py:187-189
-                pred_rd = r["image_lidar"][:, :, 0]
-                pred_int = r["image_lidar"][:, :, 1] * gt_rd
-                pred_depth = r["depth_lidar"] * gt_rd
-                out["depth"] = (self.alpha_d * (pred_depth - gt_depth).abs()).sum()
-                out["raydrop"] = (self.alpha_r * (pred_rd - gt_rd.clamp(self.smooth, 1 - self.smooth)) ** 2).sum()
-                out["intensity"] = (self.alpha_i * (pred_int - gt_int) ** 2).sum()
-                if self.use_chamfer:
-                    d = batch["rays_d_lidar"]
-                    d1, d2, _, _ = self._chamfer(d * pred_depth.unsqueeze(-1) / self.scale, d * gt_depth.unsqueeze(-1) / self.scale)
-                    out["chamfer"] = (d1 + d2).mean() * 0.5
+            on_device = r["depth_lidar"].is_cuda
+            pH, pW = self._patch_dims()
+            if pH > 1 and self.grad_loss and not on_device:
+                raise NotImplementedError("grad_loss (the structural regulariser on LiDAR patches) exists as HIP kernels only: the host branch would drop the 'sr' term silently")
+            # device: one HIP launch each way for the three sums, the masked range and the chamfer point clouds; host-side logic tests:
+            # the same terms as torch expressions
+            lidar_terms = LidarLossFn.apply if on_device else lidar_losses_host
+            d = batch["rays_d_lidar"] if self.use_chamfer else None
+            out["depth"], out["raydrop"], out["intensity"], pred_depth, pred_pts, gt_pts = lidar_terms(
+                r["image_lidar"], r["depth_lidar"], gt_rd, gt_i, gt_d, d, self.alpha_d, self.alpha_r, self.alpha_i, self.smooth, self.scale)
+            if self.use_chamfer:
+                d1, d2, _, _ = self._chamfer(pred_pts, gt_pts)
+                out["chamfer"] = (d1 + d2).mean() * 0.5
+            if pH > 1 and self.grad_loss:
+                if "rays_pano_inds" not in batch or "pano_frame" not in batch:
+                    raise ValueError("grad_loss on LiDAR patches needs batch['rays_pano_inds'] and batch['pano_frame'] (FrameSet.train_batch)")
+                out["sr"] = LidarGradLossFn.apply(pred_depth, gt_d * gt_rd, gt_rd, batch["rays_pano_inds"], batch["pano_frame"], (pH, pW),
+                                                  self.scale, self.depth_grad_loss, self.alpha_grad, self.sobel_grad)
+            if self.error_maps is not None and on_device:
+                self._for_error_map["lidar"] = (r["image_lidar"].detach(), r["depth_lidar"].detach(), gt_rd, gt_i, gt_d)
             if self.use_flow:
                 fl = self.flow_loss(batch["time"])
                 if fl is not None:
@@ -460,32 +264,17 @@ class RenderTrainStep:
         self.error_maps = frames
 
     def update_error_maps(self, batch):
-        """trainer.py:552-630 on the device: per-ray loss -> min / max -> normalised to [1, 1000] -> EMA into the frame's coarse map
-        at the rays' pixels (five small launches per modality, no host read)."""
-        from nvsf import _hip
+        """trainer.py:552-630: the per-ray losses of the batch `losses` stashed go into the error maps of the batch's frame, per modality
+        (losses.update_error_map)."""
         frames, stash = self.error_maps, self._for_error_map
         self._for_error_map = {}
         if frames is None or "index" not in batch:
             return
         idx = int(batch["index"][0])
-        for key, inds_key, emap, H, W in (("lidar", "rays_pano_inds", frames.error_map, frames.H_lidar, frames.W_lidar),
-                                          ("camera", "rays_rgb_inds", frames.error_map_rgb, frames.H, frames.W)):
-            if key not in stash or inds_key not in batch or emap is None:
-                continue
-            inds = batch[inds_key].detach().long().contiguous().view(-1)
-            N, dev = inds.numel(), inds.device
-            ray_loss = torch.empty(N, dtype=torch.float32, device=dev)
-            stats = frames.error_map_stats(dev)
-            if key == "lidar":
-                img, dep, rd, gi, gd = (t.float().contiguous() for t in stash[key])
-                _hip.call("nvsf_lidar_ray_losses", _hip.ptr(img), _hip.ptr(dep), _hip.ptr(rd), _hip.ptr(gi), _hip.ptr(gd), N, self.alpha_d, self.alpha_r,
-                          self.alpha_i, self.smooth, _hip.ptr(ray_loss), _hip.ptr(stats))
-            else:
-                img, gt = (t.float().contiguous() for t in stash[key])
-                _hip.call("nvsf_mse_rows", _hip.ptr(img), _hip.ptr(gt), N, img.shape[-1], self.alpha_rgb, _hip.ptr(ray_loss), _hip.ptr(stats))
-            eH, eW = emap.shape[-2:]
-            _hip.call("nvsf_error_map_update", _hip.ptr(ray_loss), _hip.ptr(inds), N, int(W), emap[idx].data_ptr(), int(eH), int(eW), float(eH / H),
-                      float(eW / W), _hip.ptr(stats), _hip.ptr(frames.error_map_owner(dev, eH * eW)))
+        for key, inds_key, alphas in (("lidar", "rays_pano_inds", (self.alpha_d, self.alpha_r, self.alpha_i)),
+                                      ("camera", "rays_rgb_inds", (self.alpha_rgb,))):
+            if key in stash and inds_key in batch:
+                update_error_map(frames, idx, key, stash[key], batch[inds_key], alphas, self.smooth)
 
     CAMERA_KEYS = ("rays_o", "rays_d", "gt_rgb", "images", "rays_rgb_inds", "H", "W", "gt_rgb_depth")
 
@@ -526,14 +315,65 @@ class RenderTrainStep:
         if self._pending is not None:
             ev, params = self._pending
             torch.cuda.current_stream().wait_event(ev)
-            for p in params:
-                cache = self._cache_of.get(p)
-                if cache is not None and cache.pending is ev:
-                    cache.pending = None
-                owner = self._plane_owner.get(p)
-                if owner is not None and owner.__dict__.get("_pending_update") is ev:
-                    owner.__dict__["_pending_update"] = None
+            self._mark_pending(params, None, match=ev)
             self._pending = None
+
+    def _mark_pending(self, params, ev, match=None):
+        """Sets the pending event of the fp16 cache and of the K-planes owner (read as fp32 by its kernels: the module makes its first
+        reader wait) of each late parameter to `ev`; ev None clears it where it is still `match`."""
+        for p in params:
+            cache = self._cache_of.get(p)
+            if cache is not None and (ev is not None or cache.pending is match):
+                cache.pending = ev
+            owner = self._plane_owner.get(p)
+            if owner is not None and (ev is not None or owner.__dict__.get("_pending_update") is match):
+                owner.__dict__["_pending_update"] = ev
+
+    def _late_step(self, late):
+        """The optimiser pass of a step whose last table scatters (`late`: [(parameter, scatter event)]) are still running on the side
+        stream.  -> (found, carry, ev): the overflow flag of the early gradients (None without loss scaling), the late-only overflow
+        for `_late_carry` (None likewise), the event behind the late tables' pass."""
+        # every gradient but the late tables' is final on this stream: the step's overflow decision is taken from those (for a
+        # table fed by an fp32 input gradient that is sufficient: loss_scaler.py), their update here, the late tables' update
+        # behind their scatter on the side stream.  A table fed through an fp16 hand-over (the static hash of the space-time
+        # field: the density tail's gradient-split kernel casts a finite fp32 dX > 65504 to inf) is NOT covered by that argument (ADVICE r4),
+        # so the late gradients are inspected as well -- on the side stream, behind their scatter: `found_late` = early OR late
+        # is what the late tables' Adam pass skips on (no inf / nan can reach a table, its EMA shadow or its fp16 copy), and an
+        # overflow seen ONLY there reaches the scaler's update one step later (`_late_carry`: the scale is halved after the next
+        # step instead of this one; waiting for it here would put the scatter back on the critical path).
+        from nvsf import field_ops
+        late_set = {p for p, _ in late}
+        early = [p for g in self.opt.param_groups for p in g["params"] if p.grad is not None and p not in late_set]
+        if self.scaler.is_enabled():
+            found = self.scaler.found_inf([p.grad for p in early])
+            scale = self.scaler.scale_tensor()
+            self.opt.grad_scale, self.opt.found_inf = scale, found
+        else:
+            found = None
+        carry = None
+        try:
+            self.opt.step(params=early)
+            main = torch.cuda.current_stream()
+            side = field_ops.side_stream(late[0][0].device)
+            side.wait_stream(main)  # found / scale exist; (the scatters themselves are already in front of us on `side`)
+            with torch.cuda.stream(side):
+                for p in late_set:
+                    p.grad.record_stream(side)  # zero_grad of the next step drops the tensor while this pass may still read it
+                if found is not None:
+                    found.record_stream(side)
+                    scale.record_stream(side)
+                    late_only = self.scaler.found_inf([p.grad for p in late_set])
+                    self.opt.found_inf = torch.maximum(found, late_only)
+                    carry = torch.clamp_(late_only - found, min=0.0)  # 1 only when the early gradients were clean
+                self.opt.step(params=list(late_set))
+                ev = torch.cuda.Event()
+                ev.record(side)
+        finally:
+            if found is not None:
+                del self.opt.grad_scale, self.opt.found_inf
+        self._pending = (ev, list(late_set))
+        self._mark_pending(late_set, ev)
+        return found, carry, ev
 
     def step(self, batch):
         defer = self.defer_last_table and self.scatter_overlap
@@ -542,57 +382,9 @@ class RenderTrainStep:
             from nvsf.nerf.raymarching import raymarching
             if raymarching.march_status_pending():  # occupancy-grid training without a counter read-back: the marcher's failure flag
                 raymarching.check_march_status(wait=True)  # is looked at before the optimiser, not one call later
-        if not late:
-            found = self.scaler.step(self.opt)
-        else:
-            # every gradient but the late tables' is final on this stream: the step's overflow decision is taken from those (for a
-            # table fed by an fp32 input gradient that is sufficient: loss_scaler.py), their update here, the late tables' update
-            # behind their scatter on the side stream.  A table fed through an fp16 hand-over (the static hash of the space-time
-            # field: the density tail's gradient-split kernel casts a finite fp32 dX > 65504 to inf) is NOT covered by that argument,
-            # so the late gradients are inspected as well -- on the side stream, behind their scatter: `found_late` = early OR late
-            # is what the late tables' Adam pass skips on (no inf / nan can reach a table, its EMA shadow or its fp16 copy), and an
-            # overflow seen ONLY there reaches the scaler's update one step later (`_late_carry`: the scale is halved after the next
-            # step instead of this one; waiting for it here would put the scatter back on the critical path).
-            from nvsf import field_ops
-            late_set = {p for p, _ in late}
-            early = [p for g in self.opt.param_groups for p in g["params"] if p.grad is not None and p not in late_set]
-            if self.scaler.is_enabled():
-                found = self.scaler.found_inf([p.grad for p in early])
-                scale = self.scaler.scale_tensor()
-                self.opt.grad_scale, self.opt.found_inf = scale, found
-            else:
-                found = None
-            carry = None
-            try:
-                self.opt.step(params=early)
-                main = torch.cuda.current_stream()
-                side = field_ops.side_stream(late[0][0].device)
-                side.wait_stream(main)  # found / scale exist; (the scatters themselves are already in front of us on `side`)
-                with torch.cuda.stream(side):
-                    for p in late_set:
-                        p.grad.record_stream(side)  # zero_grad of the next step drops the tensor while this pass may still read it
-                    if found is not None:
-                        found.record_stream(side)
-                        scale.record_stream(side)
-                        late_only = self.scaler.found_inf([p.grad for p in late_set])
-                        self.opt.found_inf = torch.maximum(found, late_only)
-                        carry = torch.clamp_(late_only - found, min=0.0)  # 1 only when the early gradients were clean
-                    self.opt.step(params=list(late_set))
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-            finally:
-                if found is not None:
-                    del self.opt.grad_scale, self.opt.found_inf
-            self._pending = (ev, list(late_set))
-            for p in late_set:
-                cache = self._cache_of.get(p)
-                if cache is not None:
-                    cache.pending = ev
-                owner = self._plane_owner.get(p)
-                if owner is not None:  # K-planes: read as fp32 by their kernels, the module makes its first reader wait
-                    owner.__dict__["_pending_update"] = ev
+        found, carry, ev = self._late_step(late) if late else (self.scaler.step(self.opt), None, None)
         if found is not None:
-            prev, self._late_carry = self._late_carry, (None if not late or carry is None else (ev, carry))
+            prev, self._late_carry = self._late_carry, (None if carry is None else (ev, carry))
             if prev is not None:  # a late-only overflow of the PREVIOUS step (its event is long past: this step's passes read that table)
                 main = torch.cuda.current_stream()
                 main.wait_event(prev[0])

@@ -197,7 +197,7 @@ def test_wide_error_stats_take_fp64_differences(dev, hip_lib):
 
 @pytest.mark.parametrize("criterion", O.CRITERIA)
 def test_camera_loss_against_fp64_autograd(dev, criterion):
-    from nvsf.nerf.train_step import CameraLossFn
+    from nvsf.nerf.losses import CameraLossFn
     scale, alpha_rgb, alpha_rd, n = 0.0108, 0.9, 0.7, 4096
     image, gt_rgb, depth, gt_m = (t.to(dev) for t in O.loss_rays(n, scale, seed=11))
     image.requires_grad_()

@@ -34,7 +34,7 @@ def _patch_batch(rng, H, W, pH, pW, n_patch, edge=True):
 @pytest.mark.parametrize("criterion", ["l1", "mse", "huber", "smoothl1", "cos"])
 @pytest.mark.parametrize("patch", [(2, 8), (4, 4), (8, 2)])
 def test_structural_grad_loss_matches_the_restatement(dev, patch, criterion, sobel):
-    from nvsf.nerf.train_step import LidarGradLossFn
+    from nvsf.nerf.losses import LidarGradLossFn
     rng = np.random.default_rng(3)
     H, W, scale = 66, 1030, 0.010851959895748291
     pH, pW = patch
@@ -71,7 +71,7 @@ def test_structural_grad_loss_matches_the_restatement(dev, patch, criterion, sob
 def test_cosine_criterion_on_patches_without_any_valid_gradient(dev):
     """A patch whose pixels are all dropped (or all on a range step) has u = v = 0: CosineSimilarity's eps clamp makes its cosine 0, the
     patch adds alpha pH pW 2 to the loss and nothing to the gradient (trainer.py:442-452 with main_nvsf.py:211)."""
-    from nvsf.nerf.train_step import LidarGradLossFn
+    from nvsf.nerf.losses import LidarGradLossFn
     H, W, scale, patch = 16, 64, 0.01, (2, 8)
     frame = torch.zeros(H, W, 3)
     frame[..., 2] = torch.linspace(5.0, 9.0, W)[None, :] * scale
@@ -98,7 +98,8 @@ def test_structural_grad_loss_rejects_what_is_not_built(dev):
     that its own backward call rejects (trainer.py:337-350, 1332), so there is nothing to match and the step says so."""
     from nvsf import synthetic as S
     from nvsf.nerf.models.network_static import NeRFNetworkStatic
-    from nvsf.nerf.train_step import LidarGradLossFn, RenderTrainStep
+    from nvsf.nerf.losses import LidarGradLossFn
+    from nvsf.nerf.train_step import RenderTrainStep
     z = torch.zeros(1, 16, device=dev)
     with pytest.raises(ValueError):
         LidarGradLossFn.apply(z, z, z, torch.zeros(1, 16, dtype=torch.long, device=dev), torch.zeros(8, 8, 3, device=dev), (2, 8), 1.0, "l3", 0.1)
@@ -188,3 +189,24 @@ def test_patch_epochs_regularise_and_feed_the_error_map(dev, tmp_path):
     assert not torch.equal(fs.error_map[0], em[0])
     assert all(bool(torch.isfinite(p).all()) for p in m.parameters())
     step.sync()
+
+
+@pytest.mark.parametrize("kind, param", [(5, 0.1), (2, 0.0)])  # no such criterion / Huber without its delta
+def test_launchers_reject_a_bad_criterion_before_any_launch(dev, kind, param):
+    """The criterion check the four launchers share sits below the Python validation (losses.criterion_code): called directly with a code
+    out of range or a Huber parameter of 0, each entry returns status -1 and writes nothing."""
+    from nvsf import _hip
+    P = _hip.ptr
+    n, scale = 16, 0.01
+    x, y, z = (torch.rand(n, device=dev) for _ in range(3))
+    rgb, inds, frame = torch.rand(2, n, 3, device=dev), torch.arange(n, device=dev), torch.rand(8, 8, 3, device=dev)
+    outs = [torch.full(s, -7.0, device=dev) for s in ((), (), (n, 3), (n,), (), (n // 16, 6), (n,))]
+    l_rgb, l_d, g_img, g_dep, l_sr, stats, g_pred = outs
+    camera = (P(rgb[0]), P(rgb[1]), P(x), P(y), n, 1.0, 1.0, scale, 80 * scale, kind, param)
+    patch = (P(x), P(y), P(z), P(inds), frame.data_ptr() + 4 * 2, 3, n, 2, 8, 8, 8, scale, kind, param, 0.1, 0, P(stats))
+    for name, args in (("nvsf_camera_loss_fwd", camera + (P(l_rgb), P(l_d))), ("nvsf_camera_loss_bwd", camera + (P(x), P(y), P(g_img), P(g_dep))),
+                       ("nvsf_lidar_grad_loss_fwd", patch + (P(l_sr),)), ("nvsf_lidar_grad_loss_bwd", patch + (P(x), P(g_pred)))):
+        with pytest.raises(_hip.NvsfHipError, match=r"status -1 "):
+            _hip.call(name, *args)
+    torch.cuda.synchronize()
+    assert all(bool((o == -7.0).all()) for o in outs)

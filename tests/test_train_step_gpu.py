@@ -428,7 +428,7 @@ def test_fused_loss_kernels_match_the_torch_expressions(dev):
     """LidarLossFn / MseSumFn (csrc/losses.hip: one launch each way) against the expressions of Trainer.train_step written with torch
     ops (trainer.py:187-219, 229-233, 491-503): values and the gradients that reach the rendered image / range, including the
     gradient that comes back through the chamfer point cloud and a range target equal to the prediction (|x| has gradient 0 at 0)."""
-    from nvsf.nerf.train_step import LidarLossFn, MseSumFn
+    from nvsf.nerf.losses import LidarLossFn, MseSumFn
     g = torch.Generator(device="cpu").manual_seed(5)
     N = 1500
     rnd = lambda *s: torch.rand(*s, generator=g).to(dev)

@@ -36,7 +36,8 @@ import torch  # noqa: E402
 
 from nvsf import _hip, synthetic as S  # noqa: E402
 from nvsf.nerf.dataset import depth_image as D  # noqa: E402
-from nvsf.nerf.train_step import CameraLossFn, MseSumFn, RenderTrainStep, rgb_depth_loss_host  # noqa: E402
+from nvsf.nerf.losses import CameraLossFn, MseSumFn, rgb_depth_loss_host  # noqa: E402
+from nvsf.nerf.train_step import RenderTrainStep  # noqa: E402
 
 HBM_PEAK = 8e12
 
