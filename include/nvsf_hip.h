@@ -732,6 +732,65 @@ int nvsf_camera_loss_bwd(const float* image, const float* gt_rgb, const float* d
                          float alpha_rd, float scale, float max_depth, int criterion, float criterion_param, const float* grad_loss_rgb,
                          const float* grad_loss_depth, float* grad_image, float* grad_depth, nvsf_stream_t stream);
 
+/* ref: the selectable criteria of the per-ray terms, main_nvsf.py:83-88, 205-222 (`--depth_loss`, `--raydrop_loss`, `--intensity_loss`,
+ * `--rgb_loss`), applied as trainer.py:203-218 writes them.  Every *_criterion is a code 0 L1 (derivative 0 at 0), 1 MSE,
+ * 2 Huber(delta = *_param), 3 SmoothL1(beta = *_param), 4 BCE-with-logits (max(x, 0) - x t + log1p(exp(-|x|)), derivative
+ * sigmoid(x) - t); codes 2 and 3 need a positive parameter, anything else is NVSF_ERR_INVALID_ARG.  The entries below are the entries
+ * above of the same name without `_crit`, with the criterion of each term chosen by the caller; everything else (arguments, masking by
+ * the ray-drop channel first, target clamp(gt_raydrop, s, 1 - s), outputs, single-workgroup deterministic sums) is the same.  With
+ * raydrop_criterion 4 the ray-drop prediction goes through a sigmoid BEFORE the criterion, which applies its own: two sigmoids, as
+ * trainer.py:208-209 and BCEWithLogitsLoss do. */
+int nvsf_lidar_losses_crit_fwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
+                               const float* gt_range, const float* rays_d, uint32_t N, float alpha_d, float alpha_r, float alpha_i,
+                               float smooth_factor, float scale, int depth_criterion, float depth_param, int raydrop_criterion,
+                               float raydrop_param, int intensity_criterion, float intensity_param, float* loss_depth, float* loss_raydrop,
+                               float* loss_intensity, float* pred_depth, float* pred_points, float* gt_points, nvsf_stream_t stream);
+int nvsf_lidar_losses_crit_bwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
+                               const float* gt_range, const float* rays_d, uint32_t N, float alpha_d, float alpha_r, float alpha_i,
+                               float smooth_factor, float scale, int depth_criterion, float depth_param, int raydrop_criterion,
+                               float raydrop_param, int intensity_criterion, float intensity_param, const float* grad_loss_depth,
+                               const float* grad_loss_raydrop, const float* grad_loss_intensity, const float* grad_pred_depth,
+                               const float* grad_pred_points, float* grad_image_lidar, float* grad_depth_lidar, nvsf_stream_t stream);
+/* loss = sum alpha crit(a, b) over n floats (nvsf_mse_sum_fwd with a criterion: the colour term under `--rgb_loss`); grad_a = grad_loss
+ * alpha crit'(a, b). */
+int nvsf_crit_sum_fwd(const float* a, const float* b, uint32_t n, float alpha, int criterion, float criterion_param, float* loss,
+                      nvsf_stream_t stream);
+int nvsf_crit_sum_bwd(const float* a, const float* b, uint32_t n, float alpha, int criterion, float criterion_param, const float* grad_loss,
+                      float* grad_a, nvsf_stream_t stream);
+/* nvsf_camera_loss_fwd / _bwd with the colour term under rgb_criterion instead of MSE (`--use_rgbd_loss` with `--rgb_loss`). */
+int nvsf_camera_loss_crit_fwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N, float alpha_rgb,
+                              float alpha_rd, float scale, float max_depth, int criterion, float criterion_param, int rgb_criterion,
+                              float rgb_param, float* loss_rgb, float* loss_depth, nvsf_stream_t stream);
+int nvsf_camera_loss_crit_bwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N, float alpha_rgb,
+                              float alpha_rd, float scale, float max_depth, int criterion, float criterion_param, int rgb_criterion,
+                              float rgb_param, const float* grad_loss_rgb, const float* grad_loss_depth, float* grad_image, float* grad_depth,
+                              nvsf_stream_t stream);
+/* The per-ray losses of the error maps (trainer.py:568, 609) under the same criteria: nvsf_lidar_ray_losses / nvsf_mse_rows with a
+ * criterion per term, the colour summed over the C channels.  A per-ray loss may be negative (BCE against a target outside [0, 1]):
+ * min_max_bits (uint32 [2], may be NULL) is WRITTEN, not accumulated -- the float bit patterns of the true (min, max) of the N values,
+ * the form nvsf_error_map_update reads; the caller initialises nothing.  One workgroup, fixed fold, no atomics. */
+int nvsf_lidar_ray_losses_crit(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
+                               const float* gt_range, uint32_t N, float alpha_d, float alpha_r, float alpha_i, float smooth_factor,
+                               int depth_criterion, float depth_param, int raydrop_criterion, float raydrop_param, int intensity_criterion,
+                               float intensity_param, float* ray_loss, uint32_t* min_max_bits, nvsf_stream_t stream);
+int nvsf_crit_rows(const float* a, const float* b, uint32_t N, uint32_t C, float alpha, int criterion, float criterion_param, float* row_loss,
+                   uint32_t* min_max_bits, nvsf_stream_t stream);
+
+/* ref: the line-of-sight loss of Urban Radiance Fields, `--use_urf_loss`, nvsf/nerf/trainer.py:276-294.  weights, z_vals [N, T] fp32,
+ * gt_depth [N] the masked true range g; N T <= 2^31.  eps + eps_lo is the band half-width as a double split into two floats (the
+ * reference holds it as a Python float): the masks use eps alone, as its fp32 tensors do, sigma = (eps + eps_lo) / 3.
+ *   lo = g - eps, hi = g + eps (one fp32 rounding each); near = lo < z < hi; empty = z < lo or z > hi (on an edge: neither)
+ *   r = exp(-d^2 / (2 sigma^2)), d = near ? z - g : 0;  E = max r over every element (distr.max() over its constant factor: 1 as soon
+ *   as one element is not near);  n = #{g > 0}
+ *   loss = 0.1 sum (empty w)^2 / n + 0.1 sum (near w - near r / E)^2 / n                      (n = 0: what IEEE division gives)
+ * Terms and sums in fp64, rounded to fp32 on store; two launches (per-workgroup partials in `workspace`, >= 65536 bytes, 8-byte
+ * aligned; then one fold in block order), no atomics, bit-identical between runs.  state (double [2]) receives (E, n) for the backward:
+ *   grad_weights = grad_loss 0.2 / n (empty w + near (w - r / E)), recomputed from z_vals and gt_depth; nothing flows to those two. */
+int nvsf_urf_loss_fwd(const float* weights, const float* z_vals, const float* gt_depth, uint32_t N, uint32_t T, float eps, float eps_lo,
+                      void* workspace, size_t ws_bytes, float* loss, double* state, nvsf_stream_t stream);
+int nvsf_urf_loss_bwd(const float* weights, const float* z_vals, const float* gt_depth, uint32_t N, uint32_t T, float eps, float eps_lo,
+                      const double* state, const float* grad_loss, float* grad_weights, nvsf_stream_t stream);
+
 /* ref: torch_ema.ExponentialMovingAverage.update as used by the Trainer (trainer.py:112-114 construction with decay 0.95,
  * :1420-1421 one update per epoch): shadow -= one_minus_decay * (shadow - param), fp32 [n]. */
 int nvsf_ema_update(float* shadow, const float* param, uint64_t n, float one_minus_decay, nvsf_stream_t stream);

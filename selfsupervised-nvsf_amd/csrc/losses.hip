@@ -14,13 +14,16 @@
 // and for the camera batch L_rgb = sum alpha_rgb (image - gt)^2 (trainer.py:491-503).
 #include "common.h"
 
+#include <type_traits>
+
 namespace {
 constexpr int kBlock = 1024;
 
 // fp32 partials, wave-level final fold; k_camera_loss_fwd promises another order (fp64 partials, serial fold) and keeps its own
-template <int K>
-__device__ __forceinline__ void block_sums(float (&v)[K], float* __restrict__ out[K]) {
-    __shared__ float part[K][kBlock / kWave];
+// (T = double: the sums under a chosen criterion, same fold)
+template <int K, typename T>
+__device__ __forceinline__ void block_sums(T (&v)[K], float* __restrict__ out[K]) {
+    __shared__ T part[K][kBlock / kWave];
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -31,9 +34,9 @@ __device__ __forceinline__ void block_sums(float (&v)[K], float* __restrict__ ou
     if (wave == 0) {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            float s = lane < kBlock / kWave ? part[k][lane] : 0.0f;
+            T s = lane < kBlock / kWave ? part[k][lane] : T(0);
             s = wave_sum(s);
-            if (lane == 0) *out[k] = s;
+            if (lane == 0) *out[k] = (float)s;
         }
     }
 }
@@ -49,20 +52,81 @@ __device__ __forceinline__ void min_max_bits(uint32_t* __restrict__ stats, float
     if (stats && v >= 0.0f) { atomicMin(stats, __float_as_uint(v)); atomicMax(stats + 1, __float_as_uint(v)); }
 }
 
+// ---- selectable criteria of the per-ray terms: `--depth_loss`, `--raydrop_loss`, `--intensity_loss`, `--rgb_loss` ----------------
+// (main_nvsf.py:83-88, 205-222).  crit(prediction, target, kind, param) and its derivative are cd_crit / cd_crit_grad (codes 0 L1, 1 MSE,
+// 2 Huber, 3 SmoothL1, 4 BCE-with-logits; sr_crit: the same of a residual, codes 0-3), the one pair every kernel of this file shares.
+// The values exist in fp32 (per-ray losses, the patch regulariser, the camera depth term: the calls they always made) and in fp64: the
+// sums under a chosen criterion evaluate their terms in fp64 and round once, so they carry less error than the fp32 torch expression
+// whatever the criterion.  kCrit = false instantiations are the default criteria (L1 range, MSE elsewhere) as they were.
+__device__ __forceinline__ float t_abs(float x) { return fabsf(x); }
+__device__ __forceinline__ double t_abs(double x) { return fabs(x); }
+__device__ __forceinline__ float t_max0(float x) { return fmaxf(x, 0.0f); }
+__device__ __forceinline__ double t_max0(double x) { return fmax(x, 0.0); }
+__device__ __forceinline__ float t_exp(float x) { return expf(x); }
+__device__ __forceinline__ double t_exp(double x) { return exp(x); }
+__device__ __forceinline__ float t_log1p(float x) { return log1pf(x); }
+__device__ __forceinline__ double t_log1p(double x) { return log1p(x); }
+template <typename T>
+__device__ __forceinline__ T sr_crit(T e, int kind, T param) {
+    const T a = t_abs(e);
+    if (kind == 0) return a;                                                       // L1
+    if (kind == 1) return e * e;                                                   // MSE
+    if (kind == 2) return a <= param ? T(0.5) * e * e : param * (a - T(0.5) * param);  // Huber(delta)
+    return a < param ? T(0.5) * e * e / param : a - T(0.5) * param;                    // SmoothL1(beta)
+}
+__device__ __forceinline__ float sr_crit_grad(float e, int kind, float param) {
+    const float sgn = sgnf(e), a = fabsf(e);
+    if (kind == 0) return sgn;
+    if (kind == 1) return 2.0f * e;
+    if (kind == 2) return a <= param ? e : param * sgn;
+    return a < param ? e / param : sgn;
+}
+template <typename T>
+__device__ __forceinline__ T cd_crit(T x, T y, int kind, T param) {
+    if (kind < 4) return sr_crit(x - y, kind, param);
+    return (t_max0(x) - x * y) + t_log1p(t_exp(-t_abs(x)));  // BCEWithLogitsLoss, logits x, targets y
+}
+__device__ __forceinline__ float cd_crit_grad(float x, float y, int kind, float param) {
+    if (kind < 4) return sr_crit_grad(x - y, kind, param);
+    return 1.0f / (1.0f + expf(-x)) - y;
+}
+struct TermCrit { int kind; float param; };
+struct LidarCrit { TermCrit d, r, i; };  // range, ray-drop, intensity
+// With `--raydrop_loss bce` the reference passes the ray-drop prediction through a sigmoid first (trainer.py:208-209) and then into
+// BCEWithLogitsLoss, which applies a second one: matched as written, that is what the reference trains with.
+template <typename T>
+__device__ __forceinline__ T raydrop_input(T pr, int kind) { return kind == 4 ? T(1) / (T(1) + t_exp(-pr)) : pr; }
+template <typename T>
+struct LidarTerms { T d, r, i; };  // the three weighted per-ray terms (trainer.py:216-218)
+template <typename T>
+__device__ __forceinline__ LidarTerms<T> lidar_terms(const LidarRay& t, const LidarCrit& c, float alpha_d, float alpha_r, float alpha_i) {
+    return {(T)alpha_d * cd_crit((T)t.pd, (T)t.gd, c.d.kind, (T)c.d.param),
+            (T)alpha_r * cd_crit(raydrop_input((T)t.pr, c.r.kind), (T)t.tr, c.r.kind, (T)c.r.param),
+            (T)alpha_i * cd_crit((T)t.pi, (T)t.gi, c.i.kind, (T)c.i.param)};
+}
+
+template <bool kCrit>
 __global__ __launch_bounds__(kBlock) void k_lidar_losses_fwd(const float* __restrict__ image, const float* __restrict__ depth,
                                                              const float* __restrict__ gt_rd, const float* __restrict__ gt_i,
                                                              const float* __restrict__ gt_d, const float* __restrict__ rays_d, uint32_t N,
-                                                             float alpha_d, float alpha_r, float alpha_i, float smooth, float scale,
+                                                             float alpha_d, float alpha_r, float alpha_i, float smooth, float scale, LidarCrit crit,
                                                              float* __restrict__ l_depth, float* __restrict__ l_rd, float* __restrict__ l_int,
                                                              float* __restrict__ pred_depth, float* __restrict__ pred_pts,
                                                              float* __restrict__ gt_pts) {
-    float acc[3] = {0.0f, 0.0f, 0.0f};
+    std::conditional_t<kCrit, double, float> acc[3] = {0, 0, 0};
     for (uint32_t n = threadIdx.x; n < N; n += kBlock) {
         const LidarRay t = lidar_ray(image, depth, gt_rd, gt_i, gt_d, n, smooth);
-        acc[0] += alpha_d * fabsf(t.pd - t.gd);
-        const float er = t.pr - t.tr, ei = t.pi - t.gi;
-        acc[1] += alpha_r * (er * er);
-        acc[2] += alpha_i * (ei * ei);
+        if constexpr (kCrit) {
+            const LidarTerms<double> v = lidar_terms<double>(t, crit, alpha_d, alpha_r, alpha_i);
+            acc[0] += v.d;
+            acc[1] += v.r;
+            acc[2] += v.i;
+        } else {
+            acc[0] += alpha_d * fabsf(t.pd - t.gd);
+            const float er = t.pr - t.tr, ei = t.pi - t.gi;
+            acc[1] += alpha_r * (er * er);
+            acc[2] += alpha_i * (ei * ei);
+        }
         pred_depth[n] = t.pd;
         if (pred_pts) {
 #pragma unroll
@@ -77,10 +141,11 @@ __global__ __launch_bounds__(kBlock) void k_lidar_losses_fwd(const float* __rest
     block_sums<3>(acc, out);
 }
 
+template <bool kCrit>
 __global__ __launch_bounds__(256) void k_lidar_losses_bwd(const float* __restrict__ image, const float* __restrict__ depth,
                                                           const float* __restrict__ gt_rd, const float* __restrict__ gt_i,
                                                           const float* __restrict__ gt_d, const float* __restrict__ rays_d, uint32_t N,
-                                                          float alpha_d, float alpha_r, float alpha_i, float smooth, float scale,
+                                                          float alpha_d, float alpha_r, float alpha_i, float smooth, float scale, LidarCrit crit,
                                                           const float* __restrict__ g_depth, const float* __restrict__ g_rd,
                                                           const float* __restrict__ g_int, const float* __restrict__ g_pred_depth,
                                                           const float* __restrict__ g_pred_pts, float* __restrict__ grad_image,
@@ -89,7 +154,19 @@ __global__ __launch_bounds__(256) void k_lidar_losses_bwd(const float* __restric
     if (n >= N) return;
     const float gD = g_depth ? *g_depth : 0.0f, gR = g_rd ? *g_rd : 0.0f, gI = g_int ? *g_int : 0.0f;
     const LidarRay t = lidar_ray(image, depth, gt_rd, gt_i, gt_d, n, smooth);
-    float gpd = gD * alpha_d * sgnf(t.pd - t.gd);  // gradient of the masked range
+    float gpd, gpr, gpi;  // gradients of the masked range, the ray-drop channel, the masked intensity
+    if constexpr (kCrit) {
+        gpd = gD * alpha_d * cd_crit_grad(t.pd, t.gd, crit.d.kind, crit.d.param);
+        const float x = raydrop_input(t.pr, crit.r.kind);
+        float dr = cd_crit_grad(x, t.tr, crit.r.kind, crit.r.param);
+        if (crit.r.kind == 4) dr *= x * (1.0f - x);  // through the first sigmoid
+        gpr = gR * alpha_r * dr;
+        gpi = gI * alpha_i * cd_crit_grad(t.pi, t.gi, crit.i.kind, crit.i.param);
+    } else {
+        gpd = gD * alpha_d * sgnf(t.pd - t.gd);
+        gpr = gR * alpha_r * 2.0f * (t.pr - t.tr);
+        gpi = gI * alpha_i * 2.0f * (t.pi - t.gi);
+    }
     if (g_pred_depth) gpd += g_pred_depth[n];
     if (g_pred_pts) {
         float s = 0.0f;
@@ -98,25 +175,34 @@ __global__ __launch_bounds__(256) void k_lidar_losses_bwd(const float* __restric
         gpd += s;
     }
     grad_depth[n] = gpd * t.m;
-    grad_image[2 * (size_t)n] = gR * alpha_r * 2.0f * (t.pr - t.tr);
-    grad_image[2 * (size_t)n + 1] = gI * alpha_i * 2.0f * (t.pi - t.gi) * t.m;
+    grad_image[2 * (size_t)n] = gpr;
+    grad_image[2 * (size_t)n + 1] = gpi * t.m;
 }
 
+// the colour term sum alpha crit(a, b) (trainer.py:503); kCrit = false: MSE
+template <bool kCrit>
 __global__ __launch_bounds__(kBlock) void k_mse_sum_fwd(const float* __restrict__ a, const float* __restrict__ b, uint32_t n, float alpha,
-                                                        float* __restrict__ out) {
-    float acc[1] = {0.0f};
+                                                        TermCrit crit, float* __restrict__ out) {
+    std::conditional_t<kCrit, double, float> acc[1] = {0};
     for (uint32_t i = threadIdx.x; i < n; i += kBlock) {
-        const float e = a[i] - b[i];
-        acc[0] += alpha * (e * e);
+        if constexpr (kCrit) {
+            acc[0] += (double)alpha * cd_crit((double)a[i], (double)b[i], crit.kind, (double)crit.param);
+        } else {
+            const float e = a[i] - b[i];
+            acc[0] += alpha * (e * e);
+        }
     }
     float* o[1] = {out};
     block_sums<1>(acc, o);
 }
 
+template <bool kCrit>
 __global__ __launch_bounds__(256) void k_mse_sum_bwd(const float* __restrict__ a, const float* __restrict__ b, uint32_t n, float alpha,
-                                                     const float* __restrict__ g, float* __restrict__ grad_a) {
+                                                     TermCrit crit, const float* __restrict__ g, float* __restrict__ grad_a) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) grad_a[i] = *g * alpha * 2.0f * (a[i] - b[i]);
+    if (i >= n) return;
+    if constexpr (kCrit) grad_a[i] = *g * alpha * cd_crit_grad(a[i], b[i], crit.kind, crit.param);
+    else grad_a[i] = *g * alpha * 2.0f * (a[i] - b[i]);
 }
 
 // ---- structural regularisation on LiDAR patches: the `grad_loss` branch of Trainer.train_step (trainer.py:296-470) ----------------
@@ -134,20 +220,6 @@ struct PatchGeom {
     float scale;
 };
 
-__device__ __forceinline__ float sr_crit(float e, int kind, float param) {
-    const float a = fabsf(e);
-    if (kind == 0) return a;                                                       // L1
-    if (kind == 1) return e * e;                                                   // MSE
-    if (kind == 2) return a <= param ? 0.5f * e * e : param * (a - 0.5f * param);  // Huber(delta)
-    return a < param ? 0.5f * e * e / param : a - 0.5f * param;                    // SmoothL1(beta)
-}
-__device__ __forceinline__ float sr_crit_grad(float e, int kind, float param) {
-    const float sgn = sgnf(e), a = fabsf(e);
-    if (kind == 0) return sgn;
-    if (kind == 1) return 2.0f * e;
-    if (kind == 2) return a <= param ? e : param * sgn;
-    return a < param ? e / param : sgn;
-}
 // first difference of the frame's range channel along x at (h, w), in metres, with the reference's padding of the last column
 __device__ __forceinline__ float pano_dx(const float* __restrict__ pano, uint32_t stride, uint32_t h, uint32_t w, const PatchGeom& g) {
     const uint32_t ww = w < g.W - 1 ? w : g.W - 2;
@@ -303,14 +375,6 @@ __global__ __launch_bounds__(256) void k_lidar_grad_loss_bwd(const float* __rest
 //   tensor), mask = gt > 0, L_depth = sum alpha_rd crit(pred mask, gt mask) over ALL rays (a masked ray gives crit(0, 0): log 2 under
 //   BCE-with-logits).  Per-ray terms are fp32; every thread adds its terms in index order into an fp64 partial, a wave folds its lanes in
 //   a fixed butterfly and thread 0 the 16 wave partials in wave order: no atomic, two runs give the same bits.
-__device__ __forceinline__ float cd_crit(float x, float y, int kind, float param) {
-    if (kind < 4) return sr_crit(x - y, kind, param);
-    return (fmaxf(x, 0.0f) - x * y) + log1pf(expf(-fabsf(x)));  // BCEWithLogitsLoss, logits x, targets y
-}
-__device__ __forceinline__ float cd_crit_grad(float x, float y, int kind, float param) {
-    if (kind < 4) return sr_crit_grad(x - y, kind, param);
-    return 1.0f / (1.0f + expf(-x)) - y;
-}
 struct CamDepth { float x, y, m; bool capped; };  // masked prediction, masked truth, mask, prediction above the cap
 __device__ __forceinline__ CamDepth cam_depth(float depth, float gt_m, float scale, float max_depth) {
     CamDepth t;
@@ -324,15 +388,21 @@ __device__ __forceinline__ CamDepth cam_depth(float depth, float gt_m, float sca
     return t;
 }
 
+// kCrit: the colour term under `--rgb_loss` (rgb) instead of MSE
+template <bool kCrit>
 __global__ __launch_bounds__(kBlock) void k_camera_loss_fwd(const float* __restrict__ image, const float* __restrict__ gt_rgb,
                                                             const float* __restrict__ depth, const float* __restrict__ gt_m, uint32_t N,
                                                             float alpha_rgb, float alpha_rd, float scale, float max_depth, int kind, float param,
-                                                            float* __restrict__ l_rgb, float* __restrict__ l_depth) {
+                                                            TermCrit rgb, float* __restrict__ l_rgb, float* __restrict__ l_depth) {
     __shared__ double part[2][kBlock / kWave];
     double acc[2] = {0.0, 0.0};
     for (uint32_t i = threadIdx.x; i < 3 * N; i += kBlock) {
-        const float e = image[i] - gt_rgb[i];
-        acc[0] += (double)(alpha_rgb * (e * e));
+        if constexpr (kCrit) {
+            acc[0] += (double)alpha_rgb * cd_crit((double)image[i], (double)gt_rgb[i], rgb.kind, (double)rgb.param);
+        } else {
+            const float e = image[i] - gt_rgb[i];
+            acc[0] += (double)(alpha_rgb * (e * e));
+        }
     }
     for (uint32_t n = threadIdx.x; n < N; n += kBlock) {
         const CamDepth t = cam_depth(depth[n], gt_m[n], scale, max_depth);
@@ -352,10 +422,11 @@ __global__ __launch_bounds__(kBlock) void k_camera_loss_fwd(const float* __restr
     }
 }
 
+template <bool kCrit>
 __global__ __launch_bounds__(256) void k_camera_loss_bwd(const float* __restrict__ image, const float* __restrict__ gt_rgb,
                                                          const float* __restrict__ depth, const float* __restrict__ gt_m, uint32_t N,
                                                          float alpha_rgb, float alpha_rd, float scale, float max_depth, int kind, float param,
-                                                         const float* __restrict__ g_rgb, const float* __restrict__ g_depth,
+                                                         TermCrit rgb, const float* __restrict__ g_rgb, const float* __restrict__ g_depth,
                                                          float* __restrict__ grad_image, float* __restrict__ grad_depth) {
     const uint32_t n = blockIdx.x * 256u + threadIdx.x;
     if (n >= N) return;
@@ -363,7 +434,8 @@ __global__ __launch_bounds__(256) void k_camera_loss_bwd(const float* __restrict
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const size_t i = 3 * (size_t)n + k;
-        grad_image[i] = gR * alpha_rgb * 2.0f * (image[i] - gt_rgb[i]);
+        if constexpr (kCrit) grad_image[i] = gR * alpha_rgb * cd_crit_grad(image[i], gt_rgb[i], rgb.kind, rgb.param);
+        else grad_image[i] = gR * alpha_rgb * 2.0f * (image[i] - gt_rgb[i]);
     }
     const CamDepth t = cam_depth(depth[n], gt_m[n], scale, max_depth);
     grad_depth[n] = (t.capped || t.m == 0.0f) ? 0.0f : gD * alpha_rd * cd_crit_grad(t.x, t.y, kind, param);
@@ -424,6 +496,193 @@ __global__ __launch_bounds__(256) void k_error_map_write(const float* __restrict
     map[cell] = 0.1f * map[cell] + 0.9f * e;
     owner[cell] = 0u;
 }
+
+// The per-ray losses under the selectable criteria.  BCE against a target outside [0, 1] (the range term) can be negative, which the
+// unsigned bit-pattern order of min_max_bits does not cover: here ONE workgroup walks the rays and folds (min, max) in a fixed tree of
+// fminf / fmaxf, then WRITES them as the float bit patterns k_error_map_write reads (nothing to initialise, no atomics).
+__device__ __forceinline__ void block_min_max(float lo, float hi, uint32_t* __restrict__ stats) {
+    __shared__ float part[2][kBlock / kWave];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, o, 64));
+        hi = fmaxf(hi, __shfl_xor(hi, o, 64));
+    }
+    if (lane_id() == 0) { part[0][threadIdx.x >> 6] = lo; part[1][threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0 && stats) {
+        for (int w = 1; w < kBlock / kWave; ++w) { lo = fminf(lo, part[0][w]); hi = fmaxf(hi, part[1][w]); }
+        stats[0] = __float_as_uint(lo);
+        stats[1] = __float_as_uint(hi);
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_lidar_ray_losses_crit(const float* __restrict__ image, const float* __restrict__ depth,
+                                                                  const float* __restrict__ gt_rd, const float* __restrict__ gt_i,
+                                                                  const float* __restrict__ gt_d, uint32_t N, float alpha_d, float alpha_r,
+                                                                  float alpha_i, float smooth, LidarCrit crit, float* __restrict__ out,
+                                                                  uint32_t* __restrict__ stats) {
+    float lo = INFINITY, hi = -INFINITY;
+    for (uint32_t n = threadIdx.x; n < N; n += kBlock) {
+        const LidarTerms<float> t = lidar_terms<float>(lidar_ray(image, depth, gt_rd, gt_i, gt_d, n, smooth), crit, alpha_d, alpha_r, alpha_i);
+        const float v = t.d + t.r + t.i;
+        out[n] = v;
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+    block_min_max(lo, hi, stats);
+}
+__global__ __launch_bounds__(kBlock) void k_crit_rows(const float* __restrict__ a, const float* __restrict__ b, uint32_t N, uint32_t C, float alpha,
+                                                      TermCrit crit, float* __restrict__ out, uint32_t* __restrict__ stats) {
+    float lo = INFINITY, hi = -INFINITY;
+    for (uint32_t n = threadIdx.x; n < N; n += kBlock) {
+        float v = 0.0f;
+        for (uint32_t k = 0; k < C; ++k) v += alpha * cd_crit(a[(size_t)n * C + k], b[(size_t)n * C + k], crit.kind, crit.param);
+        out[n] = v;
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+    block_min_max(lo, hi, stats);
+}
+
+// ---- line-of-sight loss of Urban Radiance Fields (`--use_urf_loss`, trainer.py:276-294) over weights / z_vals [N, T] ---------------
+//   lo = g - eps, hi = g + eps (one fp32 rounding each, as the reference's fp32 tensors), near = lo < z < hi, empty = z < lo or z > hi
+//   r = exp(-d^2 / (2 sigma^2)), sigma = eps / 3, d = near ? z - g : 0;  E = max r over EVERY element (distr.max() / c: the constant
+//   c = 1 / (sigma sqrt(2 pi)) cancels in distr / distr.max());  n = #{g > 0}
+//   loss = 0.1 sum (empty w)^2 / n + 0.1 sum (near w - near r / E)^2 / n
+// A pure stream (w and z once forward; w, z and the gradient backward): 16-byte loads along the flat array, grid-stride from the CU
+// count.  An element that is not near has r = 1, so E = 1 as soon as one exists; a launch in which EVERY element is near has
+// E = exp(-min d^2 / (2 sigma^2)) < 1 unless a sample sits on g.  One pass covers both: every thread sums (w - r)^2 (the near term if
+// E = 1) next to w^2, w r and r^2, from which the fold forms sum (w - r / E)^2 = sum w^2 - 2 sum w r / E + sum r^2 / E^2 in the
+// all-near case (fp64: the cancellation costs ~1e-16 of sum w^2 + sum r^2 / E^2).  Per-element terms and partials are fp64, a wave folds
+// by a fixed butterfly, a block its waves in order, the second launch the blocks in order: no atomics, two runs give the same bits.
+constexpr int kUrfBlock = 256, kUrfMaxBlocks = 1024, kUrfSlots = 8;  // partials per block: 5 sums, min |d|, #not near, #{g > 0}
+struct UrfAcc { double se, sn, sww, swr, srr, dmin; uint32_t far; };
+struct UrfBand { bool near, empty; double d; };
+__device__ __forceinline__ UrfBand urf_band(float z, float g, float eps) {
+    const float lo = __fsub_rn(g, eps), hi = __fadd_rn(g, eps);
+    UrfBand b;
+    b.near = z > lo && z < hi;
+    b.empty = z < lo || z > hi;
+    b.d = (double)z - (double)g;
+    return b;
+}
+__device__ __forceinline__ void urf_elem(float w, float z, float g, float eps, double inv2s2, UrfAcc& a) {
+    const UrfBand b = urf_band(z, g, eps);
+    if (b.near) {
+        const double r = exp(-(b.d * b.d * inv2s2)), t = (double)w - r;
+        a.sn += t * t;
+        a.sww += (double)w * (double)w;
+        a.swr += (double)w * r;
+        a.srr += r * r;
+        a.dmin = fmin(a.dmin, fabs(b.d));
+    } else {
+        a.far = 1u;
+        if (b.empty) a.se += (double)w * (double)w;
+    }
+}
+__device__ __forceinline__ double urf_grad_elem(float w, float z, float g, float eps, double inv2s2, double E) {
+    const UrfBand b = urf_band(z, g, eps);
+    if (b.near) return (double)w - exp(-(b.d * b.d * inv2s2)) / E;
+    return b.empty ? (double)w : 0.0;
+}
+// kVec: both arrays 16-byte aligned -> float4 chunks of the flat array (whatever T: a chunk may span rows), the last total % 4 elements
+// one by one; otherwise every element on its own.  kRows4: T % 4 == 0, a chunk lies in one row.
+template <bool kVec, bool kRows4>
+__global__ __launch_bounds__(kUrfBlock) void k_urf_partials(const float* __restrict__ w, const float* __restrict__ z, const float* __restrict__ g,
+                                                            uint32_t N, uint32_t T, float eps, double inv2s2, double* __restrict__ partials) {
+    __shared__ double part[kUrfSlots][kUrfBlock / kWave];
+    const uint32_t total = N * T, tid = blockIdx.x * kUrfBlock + threadIdx.x, stride = gridDim.x * kUrfBlock;  // total <= 2^31 (launcher)
+    UrfAcc a = {0.0, 0.0, 0.0, 0.0, 0.0, INFINITY, 0u};
+    const uint32_t chunks = kVec ? total / 4 : 0;
+    for (uint32_t c = tid; c < chunks; c += stride) {
+        const float4 w4 = reinterpret_cast<const float4*>(w)[c], z4 = reinterpret_cast<const float4*>(z)[c];
+        const float wv[4] = {w4.x, w4.y, w4.z, w4.w}, zv[4] = {z4.x, z4.y, z4.z, z4.w};
+        if constexpr (kRows4) {
+            const float gr = g[(4 * c) / T];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) urf_elem(wv[j], zv[j], gr, eps, inv2s2, a);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) urf_elem(wv[j], zv[j], g[(4 * c + j) / T], eps, inv2s2, a);
+        }
+    }
+    for (uint32_t e = 4 * chunks + tid; e < total; e += stride) urf_elem(w[e], z[e], g[e / T], eps, inv2s2, a);
+    uint32_t valid = 0;
+    for (uint32_t r = tid; r < N; r += stride) valid += g[r] > 0.0f ? 1u : 0u;
+    double v[kUrfSlots] = {a.se, a.sn, a.sww, a.swr, a.srr, a.dmin, (double)a.far, (double)valid};  // counts < 2^53: exact
+#pragma unroll
+    for (int k = 0; k < kUrfSlots; ++k) {
+        if (k == 5) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v[k] = fmin(v[k], __shfl_xor(v[k], o, 64));
+        } else {
+            v[k] = wave_sum(v[k]);
+        }
+        if (lane_id() == 0) part[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kUrfSlots) {
+        const int k = threadIdx.x;
+        double s = part[k][0];
+        for (int q = 1; q < kUrfBlock / kWave; ++q) s = k == 5 ? fmin(s, part[k][q]) : s + part[k][q];
+        partials[(size_t)blockIdx.x * kUrfSlots + k] = s;
+    }
+}
+// folds the blocks' partials in block order; state = (E, n) for the backward
+__global__ __launch_bounds__(kWave) void k_urf_fold(const double* __restrict__ partials, uint32_t blocks, double inv2s2, float* __restrict__ loss,
+                                                    double* __restrict__ state) {
+    double v[kUrfSlots];
+#pragma unroll
+    for (int k = 0; k < kUrfSlots; ++k) v[k] = k == 5 ? (double)INFINITY : 0.0;
+    for (uint32_t b = threadIdx.x; b < blocks; b += kWave) {
+#pragma unroll
+        for (int k = 0; k < kUrfSlots; ++k) {
+            const double p = partials[(size_t)b * kUrfSlots + k];
+            v[k] = k == 5 ? fmin(v[k], p) : v[k] + p;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kUrfSlots; ++k) {
+        if (k == 5) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v[k] = fmin(v[k], __shfl_xor(v[k], o, 64));
+        } else {
+            v[k] = wave_sum(v[k]);
+        }
+    }
+    if (threadIdx.x != 0) return;
+    const double n = v[7];
+    double E = 1.0, near = v[1];
+    if (v[6] == 0.0 && v[5] < (double)INFINITY) {  // every element is near: distr.max() is the sample closest to its g
+        E = exp(-(v[5] * v[5] * inv2s2));
+        near = v[2] - 2.0 * v[3] / E + v[4] / (E * E);
+    }
+    *loss = (float)(0.1 * (v[0] / n) + 0.1 * (near / n));  // n = 0: what IEEE division gives, as the torch expression
+    state[0] = E;
+    state[1] = n;
+}
+template <bool kVec, bool kRows4>
+__global__ __launch_bounds__(kUrfBlock) void k_urf_bwd(const float* __restrict__ w, const float* __restrict__ z, const float* __restrict__ g,
+                                                       uint32_t N, uint32_t T, float eps, double inv2s2, const double* __restrict__ state,
+                                                       const float* __restrict__ g_loss, float* __restrict__ grad_w) {
+    const uint32_t total = N * T, tid = blockIdx.x * kUrfBlock + threadIdx.x, stride = gridDim.x * kUrfBlock;  // total <= 2^31 (launcher)
+    const double E = state[0], k = (double)*g_loss * 0.2 / state[1];
+    const uint32_t chunks = kVec ? total / 4 : 0;
+    for (uint32_t c = tid; c < chunks; c += stride) {
+        const float4 w4 = reinterpret_cast<const float4*>(w)[c], z4 = reinterpret_cast<const float4*>(z)[c];
+        const float wv[4] = {w4.x, w4.y, w4.z, w4.w}, zv[4] = {z4.x, z4.y, z4.z, z4.w};
+        float o[4];
+        if constexpr (kRows4) {
+            const float gr = g[(4 * c) / T];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = (float)(k * urf_grad_elem(wv[j], zv[j], gr, eps, inv2s2, E));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = (float)(k * urf_grad_elem(wv[j], zv[j], g[(4 * c + j) / T], eps, inv2s2, E));
+        }
+        reinterpret_cast<float4*>(grad_w)[c] = make_float4(o[0], o[1], o[2], o[3]);
+    }
+    for (uint32_t e = 4 * chunks + tid; e < total; e += stride) grad_w[e] = (float)(k * urf_grad_elem(w[e], z[e], g[e / T], eps, inv2s2, E));
+}
 }  // namespace
 
 // criterion codes 0 .. 4; Huber (2) and SmoothL1 (3) need their positive parameter
@@ -432,11 +691,16 @@ static inline bool patch_geom_ok(uint32_t N, uint32_t pH, uint32_t pW, uint32_t 
     return pH >= 2 && pW >= 2 && N % (pH * pW) == 0 && H >= 2 && W >= 2 && scale != 0.0f;
 }
 
-NVSF_API int nvsf_lidar_losses_fwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
-                                   const float* gt_range, const float* rays_d, uint32_t N, float alpha_d, float alpha_r, float alpha_i,
-                                   float smooth_factor, float scale, float* loss_depth, float* loss_raydrop, float* loss_intensity,
-                                   float* pred_depth, float* pred_points, float* gt_points, hipStream_t stream) {
-    REQUIRE(loss_depth && loss_raydrop && loss_intensity);
+// the entries with selectable criteria share their launchers with the default ones: crit == nullptr is the default instantiation
+static inline bool lidar_crit_ok(const LidarCrit& c) {
+    return criterion_ok(c.d.kind, c.d.param) && criterion_ok(c.r.kind, c.r.param) && criterion_ok(c.i.kind, c.i.param);
+}
+
+static int lidar_losses_fwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
+                            const float* gt_range, const float* rays_d, uint32_t N, float alpha_d, float alpha_r, float alpha_i,
+                            float smooth_factor, float scale, const LidarCrit* crit, float* loss_depth, float* loss_raydrop,
+                            float* loss_intensity, float* pred_depth, float* pred_points, float* gt_points, hipStream_t stream) {
+    REQUIRE(loss_depth && loss_raydrop && loss_intensity && (!crit || lidar_crit_ok(*crit)));
     if (N == 0) {
         if (hipMemsetAsync(loss_depth, 0, 4, stream) != hipSuccess || hipMemsetAsync(loss_raydrop, 0, 4, stream) != hipSuccess ||
             hipMemsetAsync(loss_intensity, 0, 4, stream) != hipSuccess)
@@ -445,9 +709,34 @@ NVSF_API int nvsf_lidar_losses_fwd(const float* image_lidar, const float* depth_
     }
     REQUIRE(image_lidar && depth_lidar && gt_raydrop && gt_intensity && gt_range && pred_depth);
     REQUIRE((pred_points == nullptr) == (gt_points == nullptr) && (!pred_points || (rays_d && scale != 0.0f)));
-    hipLaunchKernelGGL(k_lidar_losses_fwd, dim3(1), dim3(kBlock), 0, stream, image_lidar, depth_lidar, gt_raydrop, gt_intensity, gt_range, rays_d, N,
-                       alpha_d, alpha_r, alpha_i, smooth_factor, scale, loss_depth, loss_raydrop, loss_intensity, pred_depth, pred_points, gt_points);
+    hipLaunchKernelGGL(crit ? k_lidar_losses_fwd<true> : k_lidar_losses_fwd<false>, dim3(1), dim3(kBlock), 0, stream, image_lidar, depth_lidar,
+                       gt_raydrop, gt_intensity, gt_range, rays_d, N, alpha_d, alpha_r, alpha_i, smooth_factor, scale, crit ? *crit : LidarCrit{},
+                       loss_depth, loss_raydrop, loss_intensity, pred_depth, pred_points, gt_points);
     return nvsf_launch_status();
+}
+
+static int lidar_losses_bwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
+                            const float* gt_range, const float* rays_d, uint32_t N, float alpha_d, float alpha_r, float alpha_i,
+                            float smooth_factor, float scale, const LidarCrit* crit, const float* grad_loss_depth,
+                            const float* grad_loss_raydrop, const float* grad_loss_intensity, const float* grad_pred_depth,
+                            const float* grad_pred_points, float* grad_image_lidar, float* grad_depth_lidar, hipStream_t stream) {
+    REQUIRE(!crit || lidar_crit_ok(*crit));
+    if (N == 0) return NVSF_OK;
+    REQUIRE(image_lidar && depth_lidar && gt_raydrop && gt_intensity && gt_range && grad_image_lidar && grad_depth_lidar);
+    REQUIRE(!grad_pred_points || (rays_d && scale != 0.0f));
+    hipLaunchKernelGGL(crit ? k_lidar_losses_bwd<true> : k_lidar_losses_bwd<false>, dim3(cdiv(N, 256)), dim3(256), 0, stream, image_lidar,
+                       depth_lidar, gt_raydrop, gt_intensity, gt_range, rays_d, N, alpha_d, alpha_r, alpha_i, smooth_factor, scale,
+                       crit ? *crit : LidarCrit{}, grad_loss_depth, grad_loss_raydrop, grad_loss_intensity, grad_pred_depth, grad_pred_points,
+                       grad_image_lidar, grad_depth_lidar);
+    return nvsf_launch_status();
+}
+
+NVSF_API int nvsf_lidar_losses_fwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
+                                   const float* gt_range, const float* rays_d, uint32_t N, float alpha_d, float alpha_r, float alpha_i,
+                                   float smooth_factor, float scale, float* loss_depth, float* loss_raydrop, float* loss_intensity,
+                                   float* pred_depth, float* pred_points, float* gt_points, hipStream_t stream) {
+    return lidar_losses_fwd(image_lidar, depth_lidar, gt_raydrop, gt_intensity, gt_range, rays_d, N, alpha_d, alpha_r, alpha_i, smooth_factor, scale,
+                            nullptr, loss_depth, loss_raydrop, loss_intensity, pred_depth, pred_points, gt_points, stream);
 }
 
 NVSF_API int nvsf_lidar_losses_bwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
@@ -455,51 +744,128 @@ NVSF_API int nvsf_lidar_losses_bwd(const float* image_lidar, const float* depth_
                                    float smooth_factor, float scale, const float* grad_loss_depth, const float* grad_loss_raydrop,
                                    const float* grad_loss_intensity, const float* grad_pred_depth, const float* grad_pred_points,
                                    float* grad_image_lidar, float* grad_depth_lidar, hipStream_t stream) {
-    if (N == 0) return NVSF_OK;
-    REQUIRE(image_lidar && depth_lidar && gt_raydrop && gt_intensity && gt_range && grad_image_lidar && grad_depth_lidar);
-    REQUIRE(!grad_pred_points || (rays_d && scale != 0.0f));
-    hipLaunchKernelGGL(k_lidar_losses_bwd, dim3(cdiv(N, 256)), dim3(256), 0, stream, image_lidar, depth_lidar, gt_raydrop, gt_intensity, gt_range,
-                       rays_d, N, alpha_d, alpha_r, alpha_i, smooth_factor, scale, grad_loss_depth, grad_loss_raydrop, grad_loss_intensity,
-                       grad_pred_depth, grad_pred_points, grad_image_lidar, grad_depth_lidar);
+    return lidar_losses_bwd(image_lidar, depth_lidar, gt_raydrop, gt_intensity, gt_range, rays_d, N, alpha_d, alpha_r, alpha_i, smooth_factor, scale,
+                            nullptr, grad_loss_depth, grad_loss_raydrop, grad_loss_intensity, grad_pred_depth, grad_pred_points, grad_image_lidar,
+                            grad_depth_lidar, stream);
+}
+
+NVSF_API int nvsf_lidar_losses_crit_fwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
+                                        const float* gt_range, const float* rays_d, uint32_t N, float alpha_d, float alpha_r, float alpha_i,
+                                        float smooth_factor, float scale, int depth_criterion, float depth_param, int raydrop_criterion,
+                                        float raydrop_param, int intensity_criterion, float intensity_param, float* loss_depth,
+                                        float* loss_raydrop, float* loss_intensity, float* pred_depth, float* pred_points, float* gt_points,
+                                        hipStream_t stream) {
+    const LidarCrit crit = {{depth_criterion, depth_param}, {raydrop_criterion, raydrop_param}, {intensity_criterion, intensity_param}};
+    return lidar_losses_fwd(image_lidar, depth_lidar, gt_raydrop, gt_intensity, gt_range, rays_d, N, alpha_d, alpha_r, alpha_i, smooth_factor, scale,
+                            &crit, loss_depth, loss_raydrop, loss_intensity, pred_depth, pred_points, gt_points, stream);
+}
+
+NVSF_API int nvsf_lidar_losses_crit_bwd(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
+                                        const float* gt_range, const float* rays_d, uint32_t N, float alpha_d, float alpha_r, float alpha_i,
+                                        float smooth_factor, float scale, int depth_criterion, float depth_param, int raydrop_criterion,
+                                        float raydrop_param, int intensity_criterion, float intensity_param, const float* grad_loss_depth,
+                                        const float* grad_loss_raydrop, const float* grad_loss_intensity, const float* grad_pred_depth,
+                                        const float* grad_pred_points, float* grad_image_lidar, float* grad_depth_lidar, hipStream_t stream) {
+    const LidarCrit crit = {{depth_criterion, depth_param}, {raydrop_criterion, raydrop_param}, {intensity_criterion, intensity_param}};
+    return lidar_losses_bwd(image_lidar, depth_lidar, gt_raydrop, gt_intensity, gt_range, rays_d, N, alpha_d, alpha_r, alpha_i, smooth_factor, scale,
+                            &crit, grad_loss_depth, grad_loss_raydrop, grad_loss_intensity, grad_pred_depth, grad_pred_points, grad_image_lidar,
+                            grad_depth_lidar, stream);
+}
+
+static int crit_sum_fwd(const float* a, const float* b, uint32_t n, float alpha, const TermCrit* crit, float* loss, hipStream_t stream) {
+    REQUIRE(loss && (!crit || criterion_ok(crit->kind, crit->param)));
+    if (n == 0) return hipMemsetAsync(loss, 0, 4, stream) == hipSuccess ? NVSF_OK : (int)hipGetLastError();
+    REQUIRE(a && b);
+    hipLaunchKernelGGL(crit ? k_mse_sum_fwd<true> : k_mse_sum_fwd<false>, dim3(1), dim3(kBlock), 0, stream, a, b, n, alpha,
+                       crit ? *crit : TermCrit{}, loss);
+    return nvsf_launch_status();
+}
+
+static int crit_sum_bwd(const float* a, const float* b, uint32_t n, float alpha, const TermCrit* crit, const float* grad_loss, float* grad_a,
+                        hipStream_t stream) {
+    REQUIRE(!crit || criterion_ok(crit->kind, crit->param));
+    if (n == 0) return NVSF_OK;
+    REQUIRE(a && b && grad_loss && grad_a);
+    hipLaunchKernelGGL(crit ? k_mse_sum_bwd<true> : k_mse_sum_bwd<false>, dim3(cdiv(n, 256)), dim3(256), 0, stream, a, b, n, alpha,
+                       crit ? *crit : TermCrit{}, grad_loss, grad_a);
     return nvsf_launch_status();
 }
 
 NVSF_API int nvsf_mse_sum_fwd(const float* a, const float* b, uint32_t n, float alpha, float* loss, hipStream_t stream) {
-    REQUIRE(loss);
-    if (n == 0) return hipMemsetAsync(loss, 0, 4, stream) == hipSuccess ? NVSF_OK : (int)hipGetLastError();
-    REQUIRE(a && b);
-    hipLaunchKernelGGL(k_mse_sum_fwd, dim3(1), dim3(kBlock), 0, stream, a, b, n, alpha, loss);
-    return nvsf_launch_status();
+    return crit_sum_fwd(a, b, n, alpha, nullptr, loss, stream);
 }
 
 NVSF_API int nvsf_mse_sum_bwd(const float* a, const float* b, uint32_t n, float alpha, const float* grad_loss, float* grad_a, hipStream_t stream) {
-    if (n == 0) return NVSF_OK;
-    REQUIRE(a && b && grad_loss && grad_a);
-    hipLaunchKernelGGL(k_mse_sum_bwd, dim3(cdiv(n, 256)), dim3(256), 0, stream, a, b, n, alpha, grad_loss, grad_a);
+    return crit_sum_bwd(a, b, n, alpha, nullptr, grad_loss, grad_a, stream);
+}
+
+NVSF_API int nvsf_crit_sum_fwd(const float* a, const float* b, uint32_t n, float alpha, int criterion, float criterion_param, float* loss,
+                               hipStream_t stream) {
+    const TermCrit crit = {criterion, criterion_param};
+    return crit_sum_fwd(a, b, n, alpha, &crit, loss, stream);
+}
+
+NVSF_API int nvsf_crit_sum_bwd(const float* a, const float* b, uint32_t n, float alpha, int criterion, float criterion_param,
+                               const float* grad_loss, float* grad_a, hipStream_t stream) {
+    const TermCrit crit = {criterion, criterion_param};
+    return crit_sum_bwd(a, b, n, alpha, &crit, grad_loss, grad_a, stream);
+}
+
+static int camera_loss_fwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N, float alpha_rgb,
+                           float alpha_rd, float scale, float max_depth, int criterion, float criterion_param, const TermCrit* rgb,
+                           float* loss_rgb, float* loss_depth, hipStream_t stream) {
+    REQUIRE(loss_rgb && loss_depth && N <= (1u << 30));
+    REQUIRE(criterion_ok(criterion, criterion_param) && max_depth == max_depth && (!rgb || criterion_ok(rgb->kind, rgb->param)));
+    REQUIRE(N == 0 || (image && gt_rgb && depth && gt_depth_m));
+    hipLaunchKernelGGL(rgb ? k_camera_loss_fwd<true> : k_camera_loss_fwd<false>, dim3(1), dim3(kBlock), 0, stream, image, gt_rgb, depth,
+                       gt_depth_m, N, alpha_rgb, alpha_rd, scale, max_depth, criterion, criterion_param, rgb ? *rgb : TermCrit{}, loss_rgb,
+                       loss_depth);
+    return nvsf_launch_status();
+}
+
+static int camera_loss_bwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N, float alpha_rgb,
+                           float alpha_rd, float scale, float max_depth, int criterion, float criterion_param, const TermCrit* rgb,
+                           const float* grad_loss_rgb, const float* grad_loss_depth, float* grad_image, float* grad_depth, hipStream_t stream) {
+    REQUIRE(N <= (1u << 30) && criterion_ok(criterion, criterion_param) && max_depth == max_depth);
+    REQUIRE(!rgb || criterion_ok(rgb->kind, rgb->param));
+    if (N == 0) return NVSF_OK;
+    REQUIRE(image && gt_rgb && depth && gt_depth_m && grad_image && grad_depth);
+    hipLaunchKernelGGL(rgb ? k_camera_loss_bwd<true> : k_camera_loss_bwd<false>, dim3(cdiv(N, 256)), dim3(256), 0, stream, image, gt_rgb, depth,
+                       gt_depth_m, N, alpha_rgb, alpha_rd, scale, max_depth, criterion, criterion_param, rgb ? *rgb : TermCrit{}, grad_loss_rgb,
+                       grad_loss_depth, grad_image, grad_depth);
     return nvsf_launch_status();
 }
 
 NVSF_API int nvsf_camera_loss_fwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N,
                                   float alpha_rgb, float alpha_rd, float scale, float max_depth, int criterion, float criterion_param,
                                   float* loss_rgb, float* loss_depth, hipStream_t stream) {
-    REQUIRE(loss_rgb && loss_depth && N <= (1u << 30));
-    REQUIRE(criterion_ok(criterion, criterion_param) && max_depth == max_depth);
-    REQUIRE(N == 0 || (image && gt_rgb && depth && gt_depth_m));
-    hipLaunchKernelGGL(k_camera_loss_fwd, dim3(1), dim3(kBlock), 0, stream, image, gt_rgb, depth, gt_depth_m, N, alpha_rgb, alpha_rd, scale,
-                       max_depth, criterion, criterion_param, loss_rgb, loss_depth);
-    return nvsf_launch_status();
+    return camera_loss_fwd(image, gt_rgb, depth, gt_depth_m, N, alpha_rgb, alpha_rd, scale, max_depth, criterion, criterion_param, nullptr,
+                           loss_rgb, loss_depth, stream);
 }
 
 NVSF_API int nvsf_camera_loss_bwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N,
                                   float alpha_rgb, float alpha_rd, float scale, float max_depth, int criterion, float criterion_param,
                                   const float* grad_loss_rgb, const float* grad_loss_depth, float* grad_image, float* grad_depth,
                                   hipStream_t stream) {
-    REQUIRE(N <= (1u << 30) && criterion_ok(criterion, criterion_param) && max_depth == max_depth);
-    if (N == 0) return NVSF_OK;
-    REQUIRE(image && gt_rgb && depth && gt_depth_m && grad_image && grad_depth);
-    hipLaunchKernelGGL(k_camera_loss_bwd, dim3(cdiv(N, 256)), dim3(256), 0, stream, image, gt_rgb, depth, gt_depth_m, N, alpha_rgb, alpha_rd, scale,
-                       max_depth, criterion, criterion_param, grad_loss_rgb, grad_loss_depth, grad_image, grad_depth);
-    return nvsf_launch_status();
+    return camera_loss_bwd(image, gt_rgb, depth, gt_depth_m, N, alpha_rgb, alpha_rd, scale, max_depth, criterion, criterion_param, nullptr,
+                           grad_loss_rgb, grad_loss_depth, grad_image, grad_depth, stream);
+}
+
+NVSF_API int nvsf_camera_loss_crit_fwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N,
+                                       float alpha_rgb, float alpha_rd, float scale, float max_depth, int criterion, float criterion_param,
+                                       int rgb_criterion, float rgb_param, float* loss_rgb, float* loss_depth, hipStream_t stream) {
+    const TermCrit rgb = {rgb_criterion, rgb_param};
+    return camera_loss_fwd(image, gt_rgb, depth, gt_depth_m, N, alpha_rgb, alpha_rd, scale, max_depth, criterion, criterion_param, &rgb, loss_rgb,
+                           loss_depth, stream);
+}
+
+NVSF_API int nvsf_camera_loss_crit_bwd(const float* image, const float* gt_rgb, const float* depth, const float* gt_depth_m, uint32_t N,
+                                       float alpha_rgb, float alpha_rd, float scale, float max_depth, int criterion, float criterion_param,
+                                       int rgb_criterion, float rgb_param, const float* grad_loss_rgb, const float* grad_loss_depth,
+                                       float* grad_image, float* grad_depth, hipStream_t stream) {
+    const TermCrit rgb = {rgb_criterion, rgb_param};
+    return camera_loss_bwd(image, gt_rgb, depth, gt_depth_m, N, alpha_rgb, alpha_rd, scale, max_depth, criterion, criterion_param, &rgb,
+                           grad_loss_rgb, grad_loss_depth, grad_image, grad_depth, stream);
 }
 
 NVSF_API int nvsf_lidar_grad_loss_fwd(const float* pred_depth, const float* gt_depth, const float* gt_raydrop, const int64_t* pano_inds,
@@ -546,6 +912,73 @@ NVSF_API int nvsf_mse_rows(const float* a, const float* b, uint32_t N, uint32_t 
     if (N == 0) return NVSF_OK;
     REQUIRE(a && b && row_loss && C >= 1);
     hipLaunchKernelGGL(k_mse_rows, dim3(cdiv(N, 256)), dim3(256), 0, stream, a, b, N, C, alpha, row_loss, min_max_bits);
+    return nvsf_launch_status();
+}
+
+NVSF_API int nvsf_lidar_ray_losses_crit(const float* image_lidar, const float* depth_lidar, const float* gt_raydrop, const float* gt_intensity,
+                                        const float* gt_range, uint32_t N, float alpha_d, float alpha_r, float alpha_i, float smooth_factor,
+                                        int depth_criterion, float depth_param, int raydrop_criterion, float raydrop_param,
+                                        int intensity_criterion, float intensity_param, float* ray_loss, uint32_t* min_max_bits,
+                                        hipStream_t stream) {
+    const LidarCrit crit = {{depth_criterion, depth_param}, {raydrop_criterion, raydrop_param}, {intensity_criterion, intensity_param}};
+    REQUIRE(lidar_crit_ok(crit));
+    if (N == 0) return NVSF_OK;
+    REQUIRE(image_lidar && depth_lidar && gt_raydrop && gt_intensity && gt_range && ray_loss);
+    hipLaunchKernelGGL(k_lidar_ray_losses_crit, dim3(1), dim3(kBlock), 0, stream, image_lidar, depth_lidar, gt_raydrop, gt_intensity, gt_range, N,
+                       alpha_d, alpha_r, alpha_i, smooth_factor, crit, ray_loss, min_max_bits);
+    return nvsf_launch_status();
+}
+
+NVSF_API int nvsf_crit_rows(const float* a, const float* b, uint32_t N, uint32_t C, float alpha, int criterion, float criterion_param,
+                            float* row_loss, uint32_t* min_max_bits, hipStream_t stream) {
+    REQUIRE(criterion_ok(criterion, criterion_param));
+    if (N == 0) return NVSF_OK;
+    REQUIRE(a && b && row_loss && C >= 1);
+    hipLaunchKernelGGL(k_crit_rows, dim3(1), dim3(kBlock), 0, stream, a, b, N, C, alpha, TermCrit{criterion, criterion_param}, row_loss,
+                       min_max_bits);
+    return nvsf_launch_status();
+}
+
+// ---- line-of-sight loss ---------------------------------------------------------------------------------------------------------
+struct UrfLaunch { uint32_t blocks; bool vec, rows4; double inv2s2; };
+static UrfLaunch urf_launch(const void* a, const void* b, const void* c, uint32_t N, uint32_t T, float eps, float eps_lo) {
+    UrfLaunch l;
+    const uint64_t total = (uint64_t)N * T;
+    l.vec = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0;
+    l.rows4 = l.vec && T % 4 == 0;
+    const uint64_t items = l.vec ? total / 4 + 3 : total;  // grid-stride: a few workgroups per CU, not one thread per element
+    const uint64_t want = (items + kUrfBlock - 1) / kUrfBlock, cap = (uint64_t)4 * (uint64_t)nvsf_cu_count();
+    uint64_t blocks = want < cap ? want : cap;
+    blocks = blocks < 1 ? 1 : (blocks > (uint64_t)kUrfMaxBlocks ? (uint64_t)kUrfMaxBlocks : blocks);
+    l.blocks = (uint32_t)blocks;
+    const double sigma = ((double)eps + (double)eps_lo) / 3.0;
+    l.inv2s2 = 1.0 / (2.0 * sigma * sigma);
+    return l;
+}
+
+NVSF_API int nvsf_urf_loss_fwd(const float* weights, const float* z_vals, const float* gt_depth, uint32_t N, uint32_t T, float eps, float eps_lo,
+                               void* workspace, size_t ws_bytes, float* loss, double* state, hipStream_t stream) {
+    REQUIRE(loss && state && workspace && ((uintptr_t)workspace & 7u) == 0 && ws_bytes >= (size_t)kUrfMaxBlocks * kUrfSlots * sizeof(double));
+    REQUIRE((uint64_t)N * T <= (1ull << 31) && eps > 0.0f && (double)eps + (double)eps_lo > 0.0);
+    REQUIRE((uint64_t)N * T == 0 || (weights && z_vals));
+    REQUIRE(N == 0 || gt_depth);
+    const UrfLaunch l = urf_launch(weights, z_vals, nullptr, N, T, eps, eps_lo);
+    double* partials = static_cast<double*>(workspace);
+    const auto kernel = l.rows4 ? k_urf_partials<true, true> : (l.vec ? k_urf_partials<true, false> : k_urf_partials<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(l.blocks), dim3(kUrfBlock), 0, stream, weights, z_vals, gt_depth, N, T, eps, l.inv2s2, partials);
+    hipLaunchKernelGGL(k_urf_fold, dim3(1), dim3(kWave), 0, stream, partials, l.blocks, l.inv2s2, loss, state);
+    return nvsf_launch_status();
+}
+
+NVSF_API int nvsf_urf_loss_bwd(const float* weights, const float* z_vals, const float* gt_depth, uint32_t N, uint32_t T, float eps, float eps_lo,
+                               const double* state, const float* grad_loss, float* grad_weights, hipStream_t stream) {
+    REQUIRE((uint64_t)N * T <= (1ull << 31) && eps > 0.0f && (double)eps + (double)eps_lo > 0.0);
+    if ((uint64_t)N * T == 0) return NVSF_OK;
+    REQUIRE(weights && z_vals && gt_depth && state && grad_loss && grad_weights);
+    const UrfLaunch l = urf_launch(weights, z_vals, grad_weights, N, T, eps, eps_lo);
+    const auto kernel = l.rows4 ? k_urf_bwd<true, true> : (l.vec ? k_urf_bwd<true, false> : k_urf_bwd<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(l.blocks), dim3(kUrfBlock), 0, stream, weights, z_vals, gt_depth, N, T, eps, l.inv2s2, state, grad_loss,
+                       grad_weights);
     return nvsf_launch_status();
 }
 

@@ -21,7 +21,8 @@ import warnings
 import torch
 
 from nvsf import frame_shard
-from nvsf.nerf.losses import (CameraLossFn, LidarGradLossFn, LidarLossFn, MseSumFn, lidar_losses_host, rgb_depth_loss_host,
+from nvsf.nerf.losses import (DEFAULT_CRITERIA, CameraCritLossFn, CameraLossFn, CritSumFn, LidarCritLossFn, LidarGradLossFn, LidarLossFn,
+                              MseSumFn, UrfLossFn, lidar_losses_host, per_ray_criterion, rgb_depth_loss_host, rgb_loss_host,
                               update_error_map, urf_line_of_sight_loss)
 
 
@@ -31,7 +32,7 @@ class RenderTrainStep:
                  flow_loss=False, pc_list=None, ema_decay=0.95, split_backward=True, ray_chunks=1, grad_loss=False, depth_grad_loss="l1",
                  alpha_grad=0.1, patch_size_lidar=1, change_patch_size_lidar=(2, 8), change_patch_size_epoch=2, use_error_map=False,
                  sobel_grad=False, grad_norm_smooth=False, spatial_smooth=False, tv_loss=False, use_rgbd_loss=False, rgb_depth_loss="l1",
-                 alpha_rd=1.0):
+                 alpha_rd=1.0, depth_loss="l1", raydrop_loss="mse", intensity_loss="mse", rgb_loss="mse"):
         """Defaults = the reference's CLI defaults (main_nvsf.py:60-97).  `scale`: the scene scale the chamfer loss divides by
         (opt.scale); `pc_list`: {frame index: [P, 3] tensor} world-frame point clouds for the scene-flow loss
         (Trainer.process_pointcloud, trainer.py:1848-1912, builds them from the range images); `ema_decay=None` disables EMA.
@@ -41,8 +42,19 @@ class RenderTrainStep:
         gradients (test_train_step_gpu.py); the reference's `nan_to_num` of the total is applied per modality, which differs
         only when a loss is not finite (then that modality contributes no gradient; GradScaler skips such a step anyway).
         `use_rgbd_loss`, `rgb_depth_loss`, `alpha_rd` (main_nvsf.py:84, 91, 97): the camera depth term against the LiDAR-projected
-        depth map batch["gt_rgb_depth"] (FrameSet(camera_depth=True)); switched on, both camera terms are one launch (CameraLossFn)."""
+        depth map batch["gt_rgb_depth"] (FrameSet(camera_depth=True)); switched on, both camera terms are one launch (CameraLossFn).
+        `depth_loss`, `raydrop_loss`, `intensity_loss`, `rgb_loss` (main_nvsf.py:83-88): the criterion of each per-ray term, one of
+        l1 / mse / huber / smoothl1 / bce; the defaults go through the entries they always did, anything else through the `_crit`
+        entries of csrc/losses.hip (and the error maps follow)."""
         self.model = model
+        self.criteria = {"depth_loss": str(depth_loss), "raydrop_loss": str(raydrop_loss), "intensity_loss": str(intensity_loss),
+                         "rgb_loss": str(rgb_loss)}
+        for option, name in self.criteria.items():
+            per_ray_criterion(option, name, scale)  # an unknown criterion (or "cos") fails here, with the option named
+        lidar = tuple(self.criteria[k] for k in ("depth_loss", "raydrop_loss", "intensity_loss"))
+        # None = the default criteria: the entries and host expressions without a criterion argument
+        self.lidar_criteria = None if all(self.criteria[k] == DEFAULT_CRITERIA[k] for k in ("depth_loss", "raydrop_loss", "intensity_loss")) else lidar
+        self.rgb_criterion = None if self.criteria["rgb_loss"] == DEFAULT_CRITERIA["rgb_loss"] else self.criteria["rgb_loss"]
         self.use_rgbd_loss, self.rgb_depth_loss, self.alpha_rd = bool(use_rgbd_loss), str(rgb_depth_loss), float(alpha_rd)
         if self.use_rgbd_loss:
             CameraLossFn.criterion_code(self.rgb_depth_loss, scale)  # an unknown criterion (or "cos") fails here, not at the first step
@@ -193,10 +205,14 @@ class RenderTrainStep:
                 raise NotImplementedError("grad_loss (the structural regulariser on LiDAR patches) exists as HIP kernels only: the host branch would drop the 'sr' term silently")
             # device: one HIP launch each way for the three sums, the masked range and the chamfer point clouds; host-side logic tests:
             # the same terms as torch expressions
-            lidar_terms = LidarLossFn.apply if on_device else lidar_losses_host
+            # (non-default criteria: the `_crit` pair / the torch.nn criteria, one argument more)
+            if self.lidar_criteria is None:
+                lidar_terms, crit = (LidarLossFn.apply if on_device else lidar_losses_host), ()
+            else:
+                lidar_terms, crit = (LidarCritLossFn.apply if on_device else lidar_losses_host), (self.lidar_criteria,)
             d = batch["rays_d_lidar"] if self.use_chamfer else None
             out["depth"], out["raydrop"], out["intensity"], pred_depth, pred_pts, gt_pts = lidar_terms(
-                r["image_lidar"], r["depth_lidar"], gt_rd, gt_i, gt_d, d, self.alpha_d, self.alpha_r, self.alpha_i, self.smooth, self.scale)
+                r["image_lidar"], r["depth_lidar"], gt_rd, gt_i, gt_d, d, self.alpha_d, self.alpha_r, self.alpha_i, self.smooth, self.scale, *crit)
             if self.use_chamfer:
                 d1, d2, _, _ = self._chamfer(pred_pts, gt_pts)
                 out["chamfer"] = (d1 + d2).mean() * 0.5
@@ -213,21 +229,28 @@ class RenderTrainStep:
                     out["flow"] = fl
             if self.use_urf:
                 eps = 0.02 * 0.1 ** min(self.global_step / self.iters, 1)
-                out["los"] = urf_line_of_sight_loss(r["weights"], r["z_vals"], gt_d * gt_rd, eps)
+                # device: two streaming passes forward, one backward (UrfLossFn); host-side logic tests: the torch expression
+                out["los"] = (UrfLossFn.apply if on_device else urf_line_of_sight_loss)(r["weights"], r["z_vals"], gt_d * gt_rd, eps)
         if "rays_o" in batch:
             gt_rgb = batch["gt_rgb"] if "gt_rgb" in batch else batch["images"][..., :3]
             r = self._render(batch["rays_o"], batch["rays_d"], batch["time"], perturb=True, num_steps=self.num_steps, bg_color=1)
             if not self.use_rgbd_loss:
-                out["rgb"] = MseSumFn.apply(r["image"], gt_rgb, self.alpha_rgb) if r["image"].is_cuda else (self.alpha_rgb * (r["image"] - gt_rgb) ** 2).sum()
+                if not r["image"].is_cuda:
+                    out["rgb"] = rgb_loss_host(r["image"], gt_rgb, self.alpha_rgb, self.criteria["rgb_loss"], self.scale)
+                elif self.rgb_criterion is None:
+                    out["rgb"] = MseSumFn.apply(r["image"], gt_rgb, self.alpha_rgb)
+                else:
+                    out["rgb"] = CritSumFn.apply(r["image"], gt_rgb, self.alpha_rgb, self.rgb_criterion, self.scale)
             else:
                 if "gt_rgb_depth" not in batch:
                     raise ValueError("use_rgbd_loss needs batch['gt_rgb_depth'] (FrameSet(camera_depth=True).train_batch)")
                 gt_m = batch["gt_rgb_depth"].reshape(r["depth"].shape)
                 if r["image"].is_cuda:  # both camera terms in one HIP launch each way
-                    out["rgb"], out["rgb_depth"] = CameraLossFn.apply(r["image"], r["depth"], gt_rgb, gt_m, self.alpha_rgb, self.alpha_rd, self.scale,
-                                                                      self.rgb_depth_loss)
+                    camera_terms, crit = (CameraLossFn.apply, ()) if self.rgb_criterion is None else (CameraCritLossFn.apply, (self.rgb_criterion,))
+                    out["rgb"], out["rgb_depth"] = camera_terms(r["image"], r["depth"], gt_rgb, gt_m, self.alpha_rgb, self.alpha_rd, self.scale,
+                                                                self.rgb_depth_loss, *crit)
                 else:  # host-side logic tests: the same terms as torch expressions
-                    out["rgb"] = (self.alpha_rgb * (r["image"] - gt_rgb) ** 2).sum()
+                    out["rgb"] = rgb_loss_host(r["image"], gt_rgb, self.alpha_rgb, self.criteria["rgb_loss"], self.scale)
                     out["rgb_depth"] = rgb_depth_loss_host(r["depth"], gt_m, self.scale, self.rgb_depth_loss, self.alpha_rd)
             if self.error_maps is not None and r["image"].is_cuda:
                 self._for_error_map["camera"] = (r["image"].detach(), gt_rgb)
@@ -271,10 +294,11 @@ class RenderTrainStep:
         if frames is None or "index" not in batch:
             return
         idx = int(batch["index"][0])
-        for key, inds_key, alphas in (("lidar", "rays_pano_inds", (self.alpha_d, self.alpha_r, self.alpha_i)),
-                                      ("camera", "rays_rgb_inds", (self.alpha_rgb,))):
+        rgb = None if self.rgb_criterion is None else (self.rgb_criterion,)
+        for key, inds_key, alphas, criteria in (("lidar", "rays_pano_inds", (self.alpha_d, self.alpha_r, self.alpha_i), self.lidar_criteria),
+                                                ("camera", "rays_rgb_inds", (self.alpha_rgb,), rgb)):
             if key in stash and inds_key in batch:
-                update_error_map(frames, idx, key, stash[key], batch[inds_key], alphas, self.smooth)
+                update_error_map(frames, idx, key, stash[key], batch[inds_key], alphas, self.smooth, criteria, self.scale)
 
     CAMERA_KEYS = ("rays_o", "rays_d", "gt_rgb", "images", "rays_rgb_inds", "H", "W", "gt_rgb_depth")
 

@@ -101,6 +101,11 @@ def main():
                     "(device-side meters, nvsf/nerf/meters.py)")
     ap.add_argument("--rgbd-loss", action="store_true", help="camera depth supervision from the LiDAR-projected depth map (FrameSet(camera_depth=True), "
                     "RenderTrainStep(use_rgbd_loss=True)); adds the camera depth RMSE to --eval-table")
+    for option, default in (("depth", "l1"), ("raydrop", "mse"), ("intensity", "mse"), ("rgb", "mse")):
+        ap.add_argument(f"--{option}-loss", default=default, choices=["l1", "mse", "huber", "smoothl1", "bce"],
+                        help=f"criterion of the {option} term (RenderTrainStep({option}_loss=...))")
+    ap.add_argument("--urf-loss", action="store_true", help="line-of-sight loss of Urban Radiance Fields on the LiDAR samples "
+                    "(RenderTrainStep(use_urf_loss=True): one HIP pass each way)")
     ap.add_argument("--annotations", default=None, metavar="PATH", help="JSON sidecar of the moving objects' 3-D boxes per frame id (world frame, "
                     "metres); --eval-table then also prints the static / dynamic tables (nvsf/nerf/object_masks.py)")
     ap.add_argument("--refine", action="store_true", help="fit the ray-drop refinement U-Net after training and evaluate with it as well "
@@ -173,7 +178,9 @@ def main():
                   + "  ".join(f"{k}: {pc_list[k].shape[0]} points / {pc_ground[k].shape[0]} ground" for k in sorted(pc_list)), flush=True)
     trainer = RenderTrainStep(model, iters=args.epochs * per_epoch, num_steps=args.num_steps, scale=scale, grad_loss=not args.plain,
                               use_error_map=not args.plain, change_patch_size_lidar=(1,) if args.plain else (2, 8),
-                              flow_loss=args.flow_loss, pc_list=pc_list, use_rgbd_loss=args.rgbd_loss)
+                              flow_loss=args.flow_loss, pc_list=pc_list, use_rgbd_loss=args.rgbd_loss, use_urf_loss=args.urf_loss,
+                              depth_loss=args.depth_loss, raydrop_loss=args.raydrop_loss, intensity_loss=args.intensity_loss,
+                              rgb_loss=args.rgb_loss)
     if not args.plain:
         trainer.attach_error_maps(data)
     it = 0
