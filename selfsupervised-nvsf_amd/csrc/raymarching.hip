@@ -103,7 +103,59 @@ __global__ __launch_bounds__(kBlock) void k_packbits(const float* __restrict__ g
 }
 
 // ------------------------------------------------------------------------------------------------
-// Occupancy-grid sample generation (the marcher itself: march_device.h).
+// Occupancy-grid sample generation (the marcher itself: march_device.h).  First what the kernels below share.
+// A ray's row of `rays`: {ray id, first packed sample, samples}; range_fits: it has samples and they lie inside the M allocated ones.
+__device__ __forceinline__ bool range_fits(uint32_t offset, uint32_t count, uint32_t M) { return count != 0 && offset + count <= M; }
+struct RayRange { uint32_t index, offset, count; };
+__device__ __forceinline__ RayRange load_ray_range(const int* __restrict__ rays, uint32_t n) {
+    return {(uint32_t)rays[3 * (size_t)n], (uint32_t)rays[3 * (size_t)n + 1], (uint32_t)rays[3 * (size_t)n + 2]};
+}
+
+// the first chain member of a ray that enters at t: jittered by `noise` steps
+__device__ __forceinline__ float march_t_start(const Marcher& m, float t, float noise) { return t + m.step_len(t) * noise; }
+
+// Ray setup: the marcher of ray `ray` (a row of rays_o / rays_d / fars), with the spread table `lut` when LUT (wave forms), its far
+// end and its jittered start.  The entry parameter and the noise come as addresses of the two values: the training kernels read
+// nears[n] / noises[n], the inference kernels rays_t[index] / noises[slot].  (Addresses: the loads stay behind init(),
+// where every kernel had them -- profiles/NOTES.md.)
+struct RayStart { float far, t; };
+template <bool LUT>
+__device__ __forceinline__ RayStart march_ray_setup(Marcher& m, size_t ray, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                    const uint8_t* __restrict__ grid, float bound, float dt_gamma, uint32_t max_steps, uint32_t C,
+                                                    uint32_t H, const uint32_t* lut, const float* __restrict__ fars, const float* t_enter, const float* noise) {
+    m.init(rays_o + 3 * ray, rays_d + 3 * ray, grid, bound, dt_gamma, max_steps, C, H);
+    if (LUT) m.use_lut(lut);
+    return {fars[ray], march_t_start(m, *t_enter, *noise)};
+}
+
+// The thread-per-ray walk (Marcher::probe, the reference's loop): at most max_n samples between t and far; returns their number.
+// STORE: they go to the rows first, first + 1, ... of the sample arrays.  (k_march_rays8 keeps this loop written out around its
+// eight register records: handed to a shared walk as a functor they end up in scratch, 208 bytes per lane.)
+template <bool STORE>
+__device__ __forceinline__ uint32_t march_walk(const Marcher& m, float t, float far, uint32_t max_n, size_t first = 0, float* xyzs = nullptr,
+                                               float* dirs = nullptr, float* deltas = nullptr) {
+    float last_t = t;
+    float* px = xyzs + 3 * first;
+    float* pd = dirs + 3 * first;
+    float* pl = deltas + 2 * first;
+    uint32_t step = 0;
+    float x, y, z, dt;
+    while (t < far && step < max_n) {
+        if (m.probe(t, x, y, z, dt)) {
+            t += dt;
+            if (STORE) {
+                px[0] = x; px[1] = y; px[2] = z;
+                pd[0] = m.dx; pd[1] = m.dy; pd[2] = m.dz;
+                pl[0] = dt; pl[1] = t - last_t;
+                px += 3; pd += 3; pl += 2;
+            }
+            last_t = t;
+            ++step;
+        }
+    }
+    return step;
+}
+
 // pass 1: per-ray sample count -> rays[n].z
 __global__ __launch_bounds__(kBlock) void k_march_count(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                         const uint8_t* __restrict__ grid, float bound, float dt_gamma,
@@ -113,16 +165,8 @@ __global__ __launch_bounds__(kBlock) void k_march_count(const float* __restrict_
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     if (n >= N) return;
     Marcher m;
-    m.init(rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n, grid, bound, dt_gamma, max_steps, C, H);
-    const float far = fars[n];
-    float t = nears[n];
-    t += m.step_len(t) * noises[n];
-    uint32_t count = 0;
-    float x, y, z, dt;
-    while (t < far && count < max_steps) {
-        if (m.probe(t, x, y, z, dt)) { ++count; t += dt; }
-    }
-    rays[3 * (size_t)n + 2] = (int)count;
+    const RayStart rs = march_ray_setup<false>(m, n, rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, nullptr, fars, nears + n, noises + n);
+    rays[3 * (size_t)n + 2] = (int)march_walk<false>(m, rs.t, rs.far, max_steps);
 }
 
 // The same two passes with a WAVE per ray (ChainWalker, march_device.h): 64 chain members are classified per
@@ -140,102 +184,25 @@ __global__ __launch_bounds__(kBlock) void k_march_count_wave(const float* __rest
     if (n >= N) return;
     const int lane = lane_id();
     Marcher m;
-    m.init(rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n, grid, bound, dt_gamma, max_steps, C, H);
-    m.use_lut(s_lut);
-    const float far = fars[n];
-    float t = nears[n];
-    t += m.step_len(t) * noises[n];
+    const RayStart rs = march_ray_setup<true>(m, n, rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, s_lut, fars, nears + n, noises + n);
     ChainWalker w;
-    w.init(t);
+    w.init(rs.t);
     uint32_t count = 0;
     while (count < max_steps) {
-        const unsigned long long S = w.next_samples(m, far, lane, max_steps - count, serial != 0);
+        const unsigned long long S = w.next_samples(m, rs.far, lane, max_steps - count, serial != 0);
         if (!S) break;
         count += (uint32_t)__builtin_popcountll(S);
     }
     if (lane == 0) rays[3 * (size_t)n + 2] = (int)count;
 }
 
-__global__ __launch_bounds__(kBlock) void k_march_write_wave(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-                                                             const uint8_t* __restrict__ grid, float bound, float dt_gamma,
-                                                             uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M,
-                                                             const float* __restrict__ nears, const float* __restrict__ fars,
-                                                             const float* __restrict__ noises, const int* __restrict__ rays,
-                                                             float* __restrict__ xyzs, float* __restrict__ dirs,
-                                                             float* __restrict__ deltas, int serial) {
-    __shared__ uint32_t s_lut[kSpreadLutMax];
-    fill_spread_lut(s_lut, H);
-    __syncthreads();
-    const uint32_t n = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6));
-    if (n >= N) return;
-    const int lane = lane_id();
-    const uint32_t offset = (uint32_t)rays[3 * (size_t)n + 1], count = (uint32_t)rays[3 * (size_t)n + 2];
-    if (count == 0 || offset + count > M) return;
-    Marcher m;
-    m.init(rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n, grid, bound, dt_gamma, max_steps, C, H);
-    m.use_lut(s_lut);
-    const float far = fars[n];
-    float t = nears[n];
-    t += m.step_len(t) * noises[n];
-    float last_t = t;
-    ChainWalker w;
-    w.init(t);
-    // the samples of a batch sit in the lanes of the mask S, in chain order: every such lane stores its own sample
-    uint32_t step = 0;
-    while (step < count) {
-        const unsigned long long S = w.next_samples(m, far, lane, count - step, serial != 0);
-        if (!S) break;
-        const float t_after = w.bt + w.bdt;
-        const unsigned long long lower = S & ((1ull << lane) - 1ull);  // samples of this batch before this lane
-        const int prev_lane = lower ? 63 - __builtin_clzll(lower) : lane;
-        const float prev_after = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(prev_lane << 2, __builtin_bit_cast(int, t_after)));
-        if ((S >> lane) & 1ull) {
-            const size_t s = (size_t)offset + step + (uint32_t)__builtin_popcountll(lower);
-            xyzs[3 * s] = w.bx; xyzs[3 * s + 1] = w.by; xyzs[3 * s + 2] = w.bz;
-            dirs[3 * s] = m.dx; dirs[3 * s + 1] = m.dy; dirs[3 * s + 2] = m.dz;
-            deltas[2 * s] = w.bdt; deltas[2 * s + 1] = t_after - (lower ? prev_after : last_t);
-        }
-        last_t = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t_after), 63 - __builtin_clzll(S)));
-        step += (uint32_t)__builtin_popcountll(S);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// march_rays_train in ONE launch that classifies every chain member ONCE (nvsf_march_rays_train_ws).
-//
-// The reference-shaped three-launch form classifies every chain member twice (count pass, write pass: ~115 VALU instructions per
-// 64 members each) because the sample ranges are only known after the scan.  Here a wave counts its ray once and keeps, per batch
-// that holds samples, a 16-byte record {first chain parameter, members, 64-bit sample mask} and (for the first kMarchBtCap
-// batches) the 64 member parameters in LDS; once the ray's range is known it replays the records -- positions by the marcher's
-// own clamp(o + t d) -- and stores the samples.  No second classification, and the stores of one ticket drain while the next
-// one is counted (counting is VALU-bound, the stores are not).
-// Order of the packed samples: ray-index order, exactly as the three-launch form and the CPU oracle (the reference's order
-// depends on the arrival order of its atomics, raymarching.cu:445-446).
-//
-// Where the ranges come from.  Workgroups 1.. are WORKERS: they draw tickets (4 consecutive rays, one per wave) from an atomic
-// counter until none are left; per ticket: count, publish the ticket's sum, and -- one ticket LATER, after counting the next one --
-// fetch the ticket's exclusive prefix and store.  Workgroup 0 is the SCANNER: one wave that walks the published sums in ticket
-// order (up to 512 per poll) and publishes every ticket's exclusive prefix.  A worker therefore touches two 8-byte flags per
-// ticket and never adds up anybody else's sums.  (Two earlier forms of this launch let every workgroup look back over its
-// predecessors' sums itself: all workgroups of the chip start together, finish counting together, and each then needs ~2000
-// flags through agent-scope loads that miss the L2s -- 0.15 of 0.30 ms was waiting, and counting the next ticket meanwhile did
-// not help because the look-back itself was the cost.  Count / scan / replay as three launches with the records in global
-// memory: 0.36 ms, the stores no longer overlap the counting.)
-// Inter-workgroup protocol (cdna_hip_programming.md Guideline 16, recipe R2): a ticket is drawn by a RUNNING workgroup, which
-// publishes the ticket's sum without waiting for anything, so the scanner (workgroup 0: dispatched first) only ever waits for
-// running workgroups, and workers only wait for the scanner.  Each flag is ONE naturally aligned 8-byte {status, value} granule
-// written by a single agent-scope atomic store and read by agent-scope atomic loads -- no other data crosses workgroups.  Every
-// spin is bounded (kMarchSpinLimit polls); on a timeout the launch still terminates and reports through counter[1] < 0.
-constexpr int kMarchRecCap = 24;  // records per ray kept in LDS; a ray with more sample-bearing batches re-marches when writing
-// (template parameter BT) batches per ray whose member parameters stay in LDS; the others come from Marcher::fill_batch again
-constexpr int kMarchRays = kBlock / kWave;  // rays per ticket: one per wave
-constexpr uint32_t kMarchSpinLimit = 1u << 22;
-struct MarchRec { float t0; uint32_t nb; unsigned long long S; };
-
+// The samples of a batch sit in the lanes of the mask S, in chain order: every such lane stores its own sample.
 // OFF32: 12 * M < 2^32, so sample byte offsets fit 32 bits and the stores take the scalar base + 32-bit lane offset form (no
 // 64-bit multiply-adds per lane).  The per-lane sample index is offset + step + (samples of the batch below the lane); the second
 // delta needs t + dt of the previous sample: the neighbouring lane when the batch's samples are a contiguous run (one DPP move),
 // the lane below found through the mask otherwise.
+// (The occupancy render in fused_field.hip keeps its own copy of this arithmetic: folding it in here means a shared header and
+// a new build of the headline's render kernels, which belongs to a change that is allowed to move the headline.)
 struct MarchDirs { float x, y, z; };
 template <bool OFF32>
 __device__ __forceinline__ void march_store_batch(const MarchDirs& dv, float bt, float bx, float by, float bz, float bdt, unsigned long long S,
@@ -276,49 +243,107 @@ __device__ __forceinline__ void march_store_batch(const MarchDirs& dv, float bt,
     step += (uint32_t)__builtin_popcountll(S);
 }
 
-// Everything a wave keeps of a ray between its count and its stores (two per wave: one being counted, one waiting for its range)
-template <int BT>
-struct MarchRayLds {
-    MarchRec rec[kMarchRecCap];
-    float bt[BT][kWave];
-};
-
-__device__ __forceinline__ float march_t_start(const Marcher& m, const float* __restrict__ nears, const float* __restrict__ noises, uint32_t n) {
-    const float t = nears[n];
-    return t + m.step_len(t) * noises[n];
+// wave = one ray whose `count` samples start at `offset`: march it and store every batch (the three-launch write pass, and the
+// one-launch kernel for a ray with more sample-bearing batches than it keeps records of)
+template <bool OFF32>
+__device__ __forceinline__ void march_write_ray(const Marcher& m, const MarchDirs& dv, const RayStart& rs, int lane, uint32_t offset, uint32_t count,
+                                                float* __restrict__ xyzs, float* __restrict__ dirs, float* __restrict__ deltas, int serial) {
+    float last_t = rs.t;
+    uint32_t step = 0;
+    ChainWalker w;
+    w.init(rs.t);
+    while (step < count) {
+        const unsigned long long S = w.next_samples(m, rs.far, lane, count - step, serial != 0);
+        if (!S) break;
+        march_store_batch<OFF32>(dv, w.bt, w.bx, w.by, w.bz, w.bdt, S, lane, offset, step, last_t, xyzs, dirs, deltas);
+    }
 }
 
+__global__ __launch_bounds__(kBlock) void k_march_write_wave(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                             const uint8_t* __restrict__ grid, float bound, float dt_gamma,
+                                                             uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M,
+                                                             const float* __restrict__ nears, const float* __restrict__ fars,
+                                                             const float* __restrict__ noises, const int* __restrict__ rays,
+                                                             float* __restrict__ xyzs, float* __restrict__ dirs,
+                                                             float* __restrict__ deltas, int serial) {
+    __shared__ uint32_t s_lut[kSpreadLutMax];
+    fill_spread_lut(s_lut, H);
+    __syncthreads();
+    const uint32_t n = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6));
+    if (n >= N) return;
+    const RayRange rr = load_ray_range(rays, n);
+    if (!range_fits(rr.offset, rr.count, M)) return;
+    Marcher m;
+    const RayStart rs = march_ray_setup<true>(m, n, rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, s_lut, fars, nears + n, noises + n);
+    march_write_ray<false>(m, {m.dx, m.dy, m.dz}, rs, lane_id(), rr.offset, rr.count, xyzs, dirs, deltas, serial);
+}
+
+// ------------------------------------------------------------------------------------------------
+// march_rays_train in ONE launch that classifies every chain member ONCE (nvsf_march_rays_train_ws).
+//
+// The reference-shaped three-launch form classifies every chain member twice (count pass, write pass: ~115 VALU instructions per
+// 64 members each) because the sample ranges are only known after the scan.  Here a wave counts its ray once and keeps, per batch
+// that holds samples, a 16-byte record {first chain parameter, members, 64-bit sample mask} and (for the first kMarchBt
+// batches) the 64 member parameters in LDS; once the ray's range is known it replays the records -- positions by the marcher's
+// own clamp(o + t d) -- and stores the samples.  No second classification, and the stores of one ticket drain while the next
+// one is counted (counting is VALU-bound, the stores are not).
+// Order of the packed samples: ray-index order, exactly as the three-launch form and the CPU oracle (the reference's order
+// depends on the arrival order of its atomics, raymarching.cu:445-446).
+//
+// Where the ranges come from.  Workgroups 1.. are WORKERS: they draw tickets (4 consecutive rays, one per wave) from an atomic
+// counter until none are left; per ticket: count, publish the ticket's sum, and -- one ticket LATER, after counting the next one --
+// fetch the ticket's exclusive prefix and store.  Workgroup 0 is the SCANNER: one wave that walks the published sums in ticket
+// order (up to 512 per poll) and publishes every ticket's exclusive prefix.  A worker therefore touches two 8-byte flags per
+// ticket and never adds up anybody else's sums.  (Two earlier forms of this launch let every workgroup look back over its
+// predecessors' sums itself: all workgroups of the chip start together, finish counting together, and each then needs ~2000
+// flags through agent-scope loads that miss the L2s -- 0.15 of 0.30 ms was waiting, and counting the next ticket meanwhile did
+// not help because the look-back itself was the cost.  Count / scan / replay as three launches with the records in global
+// memory: 0.36 ms, the stores no longer overlap the counting.)
+// Inter-workgroup protocol (cdna_hip_programming.md Guideline 16, recipe R2): a ticket is drawn by a RUNNING workgroup, which
+// publishes the ticket's sum without waiting for anything, so the scanner (workgroup 0: dispatched first) only ever waits for
+// running workgroups, and workers only wait for the scanner.  Each flag is ONE naturally aligned 8-byte {status, value} granule
+// written by a single agent-scope atomic store and read by agent-scope atomic loads -- no other data crosses workgroups.  Every
+// spin is bounded (kMarchSpinLimit polls); on a timeout the launch still terminates and reports through counter[1] < 0.
+constexpr int kMarchRecCap = 24;  // records per ray kept in LDS; a ray with more sample-bearing batches re-marches when writing
+constexpr int kMarchBt = 11;      // batches per ray whose member parameters stay in LDS; the others come from Marcher::fill_batch again
+constexpr int kMarchRays = kBlock / kWave;  // rays per ticket: one per wave
+constexpr uint32_t kMarchSpinLimit = 1u << 22;
+struct MarchRec { float t0; uint32_t nb; unsigned long long S; };
+
+// Everything a wave keeps of a ray between its count and its stores (two per wave: one being counted, one waiting for its range)
+struct MarchRayLds {
+    MarchRec rec[kMarchRecCap];
+    float bt[kMarchBt][kWave];
+};
+
 // wave = ray n: count it once; remember the sample-bearing batches
-template <int BT>
-__device__ __forceinline__ void march_count_ray(MarchRayLds<BT>& L, int lane, uint32_t n, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+__device__ __forceinline__ void march_count_ray(MarchRayLds& L, int lane, uint32_t n, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                 const uint8_t* __restrict__ grid, float bound, float dt_gamma, uint32_t max_steps, uint32_t C,
                                                 uint32_t H, const uint32_t* lut, const float* __restrict__ nears, const float* __restrict__ fars,
                                                 const float* __restrict__ noises, int serial, uint32_t& count, uint32_t& nrec) {
     Marcher m;
-    m.init(rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n, grid, bound, dt_gamma, max_steps, C, H);
-    m.use_lut(lut);
-    const float far = fars[n];
+    const RayStart rs = march_ray_setup<true>(m, n, rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, lut, fars, nears + n, noises + n);
     ChainWalker w;
-    w.init(march_t_start(m, nears, noises, n));
+    w.init(rs.t);
     count = 0;
     nrec = 0;
     while (count < max_steps) {
-        const unsigned long long S = w.next_samples(m, far, lane, max_steps - count, serial != 0);
+        const unsigned long long S = w.next_samples(m, rs.far, lane, max_steps - count, serial != 0);
         if (!S) break;
         if (nrec < (uint32_t)kMarchRecCap && lane == 0) {
             MarchRec r;
             r.t0 = w.t_batch; r.nb = (uint32_t)w.nb; r.S = S;
             L.rec[nrec] = r;
         }
-        if (nrec < (uint32_t)BT) L.bt[nrec][lane] = w.bt;
+        if (nrec < (uint32_t)kMarchBt) L.bt[nrec][lane] = w.bt;
         ++nrec;
         count += (uint32_t)__builtin_popcountll(S);
     }
 }
 
 // wave = ray n, whose `count` samples start at `offset`: write rays[n] and replay the records into the sample arrays
-template <bool OFF32, int BT>
-__device__ __forceinline__ void march_store_ray(const MarchRayLds<BT>& L, uint32_t offset, uint32_t count, uint32_t nrec, int lane, uint32_t n, uint32_t M,
+template <bool OFF32>
+__device__ __forceinline__ void march_store_ray(const MarchRayLds& L, uint32_t offset, uint32_t count, uint32_t nrec, int lane, uint32_t n, uint32_t M,
                                                 const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                 const uint8_t* __restrict__ grid, float bound, float dt_gamma, uint32_t max_steps, uint32_t C,
                                                 uint32_t H, const uint32_t* lut, const float* __restrict__ nears, const float* __restrict__ fars,
@@ -329,22 +354,22 @@ __device__ __forceinline__ void march_store_ray(const MarchRayLds<BT>& L, uint32
         rays[3 * (size_t)n + 1] = (int)offset;
         rays[3 * (size_t)n + 2] = (int)count;
     }
-    if (count == 0 || offset + count > M) return;
+    if (!range_fits(offset, count, M)) return;
     Marcher m;
     m.init_replay(rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n, bound, dt_gamma, max_steps, C, H);
-    const float t_start = march_t_start(m, nears, noises, n);
-    float last_t = t_start;
-    uint32_t step = 0;
+    const float t_start = march_t_start(m, nears[n], noises[n]);
     MarchDirs dv = {m.dx, m.dy, m.dz};
     asm volatile("" : "+v"(dv.x), "+v"(dv.y), "+v"(dv.z));  // three registers for the whole loop instead of three moves per batch
     if (nrec <= (uint32_t)kMarchRecCap) {
+        float last_t = t_start;
+        uint32_t step = 0;
         for (uint32_t r = 0; r < nrec; ++r) {
             const MarchRec rec = L.rec[r];
             // the record is the same in every lane: as scalars, so that the mask arithmetic of the stores runs on the scalar unit
             const unsigned long long S = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(rec.S >> 32)) << 32) |
                                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)rec.S);
             float bt;
-            if (r < (uint32_t)BT) {
+            if (r < (uint32_t)kMarchBt) {
                 bt = L.bt[r][lane];
             } else {
                 float tn;
@@ -363,16 +388,8 @@ __device__ __forceinline__ void march_store_ray(const MarchRayLds<BT>& L, uint32
             march_store_batch<OFF32>(dv, bt, bx, by, bz, bdt, S, lane, offset, step, last_t, xyzs, dirs, deltas);
         }
     } else {  // more sample-bearing batches than LDS records: march again, as the three-launch write pass does
-        m.init(rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n, grid, bound, dt_gamma, max_steps, C, H);
-        m.use_lut(lut);
-        const float far = fars[n];
-        ChainWalker w;
-        w.init(t_start);
-        while (step < count) {
-            const unsigned long long S = w.next_samples(m, far, lane, count - step, serial != 0);
-            if (!S) break;
-            march_store_batch<OFF32>(dv, w.bt, w.bx, w.by, w.bz, w.bdt, S, lane, offset, step, last_t, xyzs, dirs, deltas);
-        }
+        const RayStart rs = march_ray_setup<true>(m, n, rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, lut, fars, nears + n, noises + n);
+        march_write_ray<OFF32>(m, dv, rs, lane, offset, count, xyzs, dirs, deltas, serial);
     }
 }
 
@@ -473,8 +490,13 @@ __device__ __forceinline__ uint32_t march_draw_any(unsigned int* heads, uint32_t
 
 // PLAIN: dt_gamma == 0 and the batch-parallel walk -- the reference's defaults -- are compile-time facts of the instance: the
 // step-length recurrences, the per-member dt-level and the serial-walk switch fold away (fewer instructions and fewer live scalars).
-template <bool OFF32, bool PLAIN, int BT>
-__device__ __forceinline__ void march_train_onepass_body(
+// Six waves per SIMD: 80 registers hold the marcher's state without spills (at eight waves = 64 registers, 12-14 of them went to
+// scratch, whose loads and stores queue behind the sample stores on the wave's memory counter), and six workgroups per compute
+// unit leave LDS for the member parameters of 11 batches per ray (a camera ray through a full grid has ~12).  Measured (32 768
+// rays x 1024 steps, dense grid): 0.233 -> 0.211 ms.
+constexpr uint32_t kMarchWgPerCu = 6;
+template <bool OFF32, bool PLAIN>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kMarchWgPerCu, kMarchWgPerCu))) void k_march_train_onepass(
     const float* __restrict__ rays_o, const float* __restrict__ rays_d, const uint8_t* __restrict__ grid, float bound, float dt_gamma_arg,
     uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* __restrict__ nears, const float* __restrict__ fars,
     const float* __restrict__ noises, int* __restrict__ rays, int* __restrict__ counter, unsigned long long* __restrict__ ws,
@@ -491,7 +513,7 @@ __device__ __forceinline__ void march_train_onepass_body(
         return;
     }
     extern __shared__ uint32_t s_lut[];  // H entries
-    __shared__ MarchRayLds<BT> s_ray[kMarchRays][2];
+    __shared__ MarchRayLds s_ray[kMarchRays][2];
     __shared__ uint32_t s_late;
     __shared__ uint32_t s_cnt[2][kMarchRays], s_next[2], s_arrived[2];  // by parity of the iteration: written before its barrier, read right after it
     fill_spread_lut(s_lut, H);
@@ -510,7 +532,7 @@ __device__ __forceinline__ void march_train_onepass_body(
         uint32_t count = 0, nrec = 0, before = 0;
         if (have) {
             if (n < N)
-                march_count_ray<BT>(s_ray[wid][cur], lane, n, rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, s_lut, nears, fars, noises, serial, count, nrec);
+                march_count_ray(s_ray[wid][cur], lane, n, rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, s_lut, nears, fars, noises, serial, count, nrec);
             if (lane == 0) s_cnt[cur][wid] = count;
             // the next ticket is drawn late: the scanner works in ticket order, and a ticket drawn long before it is counted holds
             // everybody's ranges back (drawn before the count: 0.274 ms instead of 0.25) -- by the wave that finishes its ray FIRST, so
@@ -546,7 +568,7 @@ __device__ __forceinline__ void march_train_onepass_body(
             if (status != 1u) {
                 if (lane == 0) atomicOr(reinterpret_cast<unsigned int*>(counter + 1), 0x80000000u);
             } else if (pend_n < N) {
-                march_store_ray<OFF32, BT>(s_ray[wid][cur ^ 1], excl + pend_before, pend_count, pend_nrec, lane, pend_n, M, rays_o, rays_d, grid, bound, dt_gamma,
+                march_store_ray<OFF32>(s_ray[wid][cur ^ 1], excl + pend_before, pend_count, pend_nrec, lane, pend_n, M, rays_o, rays_d, grid, bound, dt_gamma,
                                        max_steps, C, H, s_lut, nears, fars, noises, rays, xyzs, dirs, deltas, serial);
             }
         }
@@ -567,24 +589,6 @@ __device__ __forceinline__ void march_train_onepass_body(
         cur ^= 1;
     }
 }
-
-#define NVSF_MARCH_ONEPASS_KERNEL(NAME, WAVES, BT)                                                                                                  \
-    template <bool OFF32, bool PLAIN>                                                                                                       \
-    __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void NAME(                                     \
-        const float* __restrict__ rays_o, const float* __restrict__ rays_d, const uint8_t* __restrict__ grid, float bound, float dt_gamma,  \
-        uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* __restrict__ nears,                                \
-        const float* __restrict__ fars, const float* __restrict__ noises, int* __restrict__ rays, int* __restrict__ counter,                \
-        unsigned long long* __restrict__ ws, float* __restrict__ xyzs, float* __restrict__ dirs, float* __restrict__ deltas, int serial,    \
-        uint32_t spin_limit, uint32_t skew) {                                                                                               \
-        march_train_onepass_body<OFF32, PLAIN, BT>(rays_o,       rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, noises, rays,     \
-                                               counter, ws, xyzs, dirs, deltas, serial, spin_limit, skew);                                  \
-    }
-// Six waves per SIMD: 80 registers hold the marcher's state without spills (at eight waves = 64 registers, 12-14 of them went to
-// scratch, whose loads and stores queue behind the sample stores on the wave's memory counter), and six workgroups per compute
-// unit leave LDS for the member parameters of 11 batches per ray (a camera ray through a full grid has ~12).  Measured (32 768
-// rays x 1024 steps, dense grid): 0.233 -> 0.211 ms.
-constexpr uint32_t kMarchWgPerCu = 6;
-NVSF_MARCH_ONEPASS_KERNEL(k_march_train_onepass, 6, 11)
 
 // pass 2: one workgroup; exclusive scan of the counts in ray order, reserving [counter[0], +total).
 // A thread takes kScanPer consecutive rays per round (4096 rays per round: one round at the BASELINE batch size).
@@ -637,31 +641,11 @@ __global__ __launch_bounds__(kBlock) void k_march_write(const float* __restrict_
                                                         float* __restrict__ deltas) {
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     if (n >= N) return;
-    const uint32_t offset = (uint32_t)rays[3 * (size_t)n + 1], count = (uint32_t)rays[3 * (size_t)n + 2];
-    if (count == 0 || offset + count > M) return;
+    const RayRange rr = load_ray_range(rays, n);
+    if (!range_fits(rr.offset, rr.count, M)) return;
     Marcher m;
-    m.init(rays_o + 3 * (size_t)n, rays_d + 3 * (size_t)n, grid, bound, dt_gamma, max_steps, C, H);
-    const float far = fars[n];
-    float t = nears[n];
-    t += m.step_len(t) * noises[n];
-    float last_t = t;
-    float* px = xyzs + 3 * (size_t)offset;
-    float* pd = dirs + 3 * (size_t)offset;
-    float* pl = deltas + 2 * (size_t)offset;
-    uint32_t step = 0;
-    float x, y, z, dt;
-    while (t < far && step < count) {
-        if (m.probe(t, x, y, z, dt)) {
-            px[0] = x; px[1] = y; px[2] = z;
-            pd[0] = m.dx; pd[1] = m.dy; pd[2] = m.dz;
-            t += dt;
-            pl[0] = dt;
-            pl[1] = t - last_t;
-            last_t = t;
-            px += 3; pd += 3; pl += 2;
-            ++step;
-        }
-    }
+    const RayStart rs = march_ray_setup<false>(m, n, rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, nullptr, fars, nears + n, noises + n);
+    march_walk<true>(m, rs.t, rs.far, rr.count, rr.offset, xyzs, dirs, deltas);
 }
 
 // inference marcher: fixed n_step slots per alive ray
@@ -676,28 +660,8 @@ __global__ __launch_bounds__(kBlock) void k_march_rays(uint32_t n_alive, uint32_
     if (n >= n_alive) return;
     const int index = rays_alive[n];
     Marcher m;
-    m.init(rays_o + 3 * (size_t)index, rays_d + 3 * (size_t)index, grid, bound, dt_gamma, max_steps, C, H);
-    float* px = xyzs + 3 * (size_t)n * n_step;
-    float* pd = dirs + 3 * (size_t)n * n_step;
-    float* pl = deltas + 2 * (size_t)n * n_step;
-    const float far = fars[index];
-    float t = rays_t[index];
-    t += m.step_len(t) * noises[n];
-    float last_t = t;
-    uint32_t step = 0;
-    float x, y, z, dt;
-    while (t < far && step < n_step) {
-        if (m.probe(t, x, y, z, dt)) {
-            px[0] = x; px[1] = y; px[2] = z;
-            pd[0] = m.dx; pd[1] = m.dy; pd[2] = m.dz;
-            t += dt;
-            pl[0] = dt;
-            pl[1] = t - last_t;
-            last_t = t;
-            px += 3; pd += 3; pl += 2;
-            ++step;
-        }
-    }
+    const RayStart rs = march_ray_setup<false>(m, (size_t)index, rays_o, rays_d, grid, bound, dt_gamma, max_steps, C, H, nullptr, fars, rays_t + index, noises + n);
+    march_walk<true>(m, rs.t, rs.far, n_step, (size_t)n * n_step, xyzs, dirs, deltas);
 }
 
 // n_step == 8: the samples of a ray are collected in registers and leave as whole records (xyz / dirs 96 B, deltas 64 B
@@ -714,12 +678,11 @@ __global__ __launch_bounds__(kBlock) void k_march_rays8(uint32_t n_alive, const 
     if (n - (uint32_t)lane_id() >= n_alive) return;  // whole wave past the end
     const bool valid = n < n_alive;                    // lanes past the end of the last wave march nothing but help to store
     const int index = rays_alive[valid ? n : n_alive - 1u];
+    // (setup and walk stay written out here, not through march_ray_setup / march_walk: see the note at march_walk)
     Marcher m;
     m.init(rays_o + 3 * (size_t)index, rays_d + 3 * (size_t)index, grid, bound, dt_gamma, max_steps, C, H);
     const float far = valid ? fars[index] : -1.0f;
-    float t = rays_t[index];
-    t += m.step_len(t) * noises[valid ? n : n_alive - 1u];
-    float last_t = t;
+    float t = march_t_start(m, rays_t[index], noises[valid ? n : n_alive - 1u]), last_t = t;
     float rec[8][5];  // x, y, z, dt, t_new - last_t; unfilled slots stay zero (they signal termination to composite_rays)
 #pragma unroll
     for (int k = 0; k < 8; ++k)
@@ -782,6 +745,26 @@ __global__ __launch_bounds__(kBlock) void k_march_rays8(uint32_t n_alive, const 
 // transmittance is a cross-lane exclusive product scan carried between rounds.
 constexpr int kRaysPerBlock = kBlock / kWave;
 
+// One round of the forward and of the backward (this lane's sample of 64 consecutive ones; `valid`: the ray has it): its alpha, the
+// transmittance in front of and behind it (T: behind the last sample of the round before), live: the sample counts -- the first one that leaves
+// T_after < T_thresh is the last that does (`last`) --, stop (wave-uniform): the ray ends with this round.
+struct CompositeRound { float alpha, T_before, T_after; bool live, last, stop; };
+__device__ __forceinline__ CompositeRound composite_round(bool valid, float sigma, float d0, float T_thresh, int lane, float T) {
+    CompositeRound c;
+    c.alpha = valid ? 1.0f - expf(-sigma * d0) : 0.0f;
+    const float incl = wave_scan_mul(1.0f - c.alpha);
+    float excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 1.0f;
+    c.T_before = T * excl;
+    c.T_after = T * incl;
+    const unsigned long long stop = __ballot(valid && (c.T_after < T_thresh));
+    const int first_stop = stop ? (int)__builtin_ctzll(stop) : 64;
+    c.live = valid && lane <= first_stop;
+    c.last = lane == first_stop;
+    c.stop = stop != 0ull;
+    return c;
+}
+
 __global__ __launch_bounds__(kBlock) void k_composite_train_fwd(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                 const float* __restrict__ deltas, const int* __restrict__ rays,
                                                                 uint32_t M, uint32_t N, float T_thresh,
@@ -790,45 +773,37 @@ __global__ __launch_bounds__(kBlock) void k_composite_train_fwd(const float* __r
     const uint32_t n = blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
     if (n >= N) return;
     const int lane = lane_id();
-    const uint32_t index = (uint32_t)rays[3 * (size_t)n], offset = (uint32_t)rays[3 * (size_t)n + 1],
-                   count = (uint32_t)rays[3 * (size_t)n + 2];
+    const RayRange rr = load_ray_range(rays, n);
     float r = 0, g = 0, b = 0, ws = 0, d = 0;
-    if (count != 0 && offset + count <= M) {
+    if (range_fits(rr.offset, rr.count, M)) {
         float T_carry = 1.0f, t_carry = 0.0f;
-        for (uint32_t base = 0; base < count; base += 64) {
+        for (uint32_t base = 0; base < rr.count; base += 64) {
             const uint32_t i = base + lane;
-            const bool valid = i < count;
+            const bool valid = i < rr.count;
             float sg = 0, d0 = 0, d1 = 0, cr = 0, cg = 0, cb = 0;
             if (valid) {
-                const size_t p = (size_t)offset + i;
+                const size_t p = (size_t)rr.offset + i;
                 sg = sigmas[p];
                 const float2 dl = reinterpret_cast<const float2*>(deltas)[p];
                 d0 = dl.x; d1 = dl.y;
                 cr = rgbs[3 * p]; cg = rgbs[3 * p + 1]; cb = rgbs[3 * p + 2];
             }
-            const float alpha = valid ? 1.0f - expf(-sg * d0) : 0.0f;
-            const float om = 1.0f - alpha;
-            const float incl = wave_scan_mul(om);
-            float excl = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 1.0f;
-            const float T_before = T_carry * excl, T_after = T_carry * incl;
-            const unsigned long long stop = __ballot(valid && (T_after < T_thresh));
-            const int first_stop = stop ? (int)__builtin_ctzll(stop) : 64;
-            const float w = (valid && lane <= first_stop) ? alpha * T_before : 0.0f;
+            const CompositeRound c = composite_round(valid, sg, d0, T_thresh, lane, T_carry);
+            const float w = c.live ? c.alpha * c.T_before : 0.0f;
             const float t_here = t_carry + wave_scan_add(d1);
             r += w * cr; g += w * cg; b += w * cb;
             d += w * t_here;
             ws += w;
-            if (stop) break;
-            T_carry = __shfl(T_after, 63, 64);
+            if (c.stop) break;
+            T_carry = __shfl(c.T_after, 63, 64);
             t_carry = __shfl(t_here, 63, 64);
         }
         r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); ws = wave_sum(ws); d = wave_sum(d);
     }
     if (lane == 0) {
-        weights_sum[index] = ws;
-        depth[index] = d;
-        image[3 * (size_t)index] = r; image[3 * (size_t)index + 1] = g; image[3 * (size_t)index + 2] = b;
+        weights_sum[rr.index] = ws;
+        depth[rr.index] = d;
+        image[3 * (size_t)rr.index] = r; image[3 * (size_t)rr.index + 1] = g; image[3 * (size_t)rr.index + 2] = b;
     }
 }
 
@@ -841,53 +816,77 @@ __global__ __launch_bounds__(kBlock) void k_composite_train_bwd(const float* __r
     const uint32_t n = blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
     if (n >= N) return;
     const int lane = lane_id();
-    const uint32_t index = (uint32_t)rays[3 * (size_t)n], offset = (uint32_t)rays[3 * (size_t)n + 1],
-                   count = (uint32_t)rays[3 * (size_t)n + 2];
-    if (count == 0 || offset + count > M) return;
+    const RayRange rr = load_ray_range(rays, n);
+    if (!range_fits(rr.offset, rr.count, M)) return;
+    const size_t index = rr.index;
     const float gws = grad_ws[index];
-    const float gr = grad_image[3 * (size_t)index], gg = grad_image[3 * (size_t)index + 1], gb = grad_image[3 * (size_t)index + 2];
-    const float rF = image[3 * (size_t)index], gF = image[3 * (size_t)index + 1], bF = image[3 * (size_t)index + 2];
+    const float gr = grad_image[3 * index], gg = grad_image[3 * index + 1], gb = grad_image[3 * index + 2];
+    const float rF = image[3 * index], gF = image[3 * index + 1], bF = image[3 * index + 2];
     const float wsF = weights_sum[index];
     float T_carry = 1.0f, r_carry = 0, g_carry = 0, b_carry = 0;
-    for (uint32_t base = 0; base < count; base += 64) {
+    for (uint32_t base = 0; base < rr.count; base += 64) {
         const uint32_t i = base + lane;
-        const bool valid = i < count;
-        const size_t p = (size_t)offset + (valid ? i : 0);
+        const bool valid = i < rr.count;
+        const size_t p = (size_t)rr.offset + (valid ? i : 0);
         float sg = 0, d0 = 0, cr = 0, cg = 0, cb = 0;
         if (valid) {
             sg = sigmas[p];
             d0 = deltas[2 * p];
             cr = rgbs[3 * p]; cg = rgbs[3 * p + 1]; cb = rgbs[3 * p + 2];
         }
-        const float alpha = valid ? 1.0f - expf(-sg * d0) : 0.0f;
-        const float incl = wave_scan_mul(1.0f - alpha);
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.0f;
-        const float T_before = T_carry * excl, T_after = T_carry * incl;
-        const unsigned long long stop = __ballot(valid && (T_after < T_thresh));
-        const int first_stop = stop ? (int)__builtin_ctzll(stop) : 64;
-        const bool live = valid && lane <= first_stop;
-        const float w = live ? alpha * T_before : 0.0f;
+        const CompositeRound c = composite_round(valid, sg, d0, T_thresh, lane, T_carry);
+        const float w = c.live ? c.alpha * c.T_before : 0.0f;
         const float r = r_carry + wave_scan_add(w * cr);
         const float g = g_carry + wave_scan_add(w * cg);
         const float b = b_carry + wave_scan_add(w * cb);
-        if (live) {
+        if (c.live) {
             grad_rgbs[3 * p] = gr * w; grad_rgbs[3 * p + 1] = gg * w; grad_rgbs[3 * p + 2] = gb * w;
             // Behind the ray's last live sample, or behind one that leaves a transmittance of exactly zero, every weight is exactly
             // zero: the colour that remains is 0 and 1 - weights_sum is T_after.  Taken from the forward's totals instead they are
             // the rounding residue of two summation orders (the forward's lane sums against this scan; the reference's sequential
             // loops give r_final == r there), a few ulps of the total -- which trunc_exp's backward multiplies by up to e^15 on
             // exactly these samples, the saturating ones
-            const bool nothing_behind = lane == first_stop || i + 1 == count || T_after == 0.0f;
+            const bool nothing_behind = c.last || i + 1 == rr.count || c.T_after == 0.0f;
             const float rem_r = nothing_behind ? 0.0f : rF - r, rem_g = nothing_behind ? 0.0f : gF - g, rem_b = nothing_behind ? 0.0f : bF - b;
-            const float T_final = nothing_behind ? T_after : 1.0f - wsF;
-            grad_sigmas[p] = d0 * (gr * (T_after * cr - rem_r) + gg * (T_after * cg - rem_g) + gb * (T_after * cb - rem_b) + gws * T_final);
+            const float T_final = nothing_behind ? c.T_after : 1.0f - wsF;
+            grad_sigmas[p] = d0 * (gr * (c.T_after * cr - rem_r) + gg * (c.T_after * cg - rem_g) + gb * (c.T_after * cb - rem_b) + gws * T_final);
         }
-        if (stop) break;
-        T_carry = __shfl(T_after, 63, 64);
+        if (c.stop) break;
+        T_carry = __shfl(c.T_after, 63, 64);
         r_carry = __shfl(r, 63, 64); g_carry = __shfl(g, 63, 64); b_carry = __shfl(b, 63, 64);
     }
 }
+
+// What the inference compositors carry per ray from call to call (row `index` of rays_t / weights_sum / depth / image), and the
+// reference's recurrence over the slots of one call.
+struct RayAccum {
+    float t, ws, d, r, g, b;
+    __device__ __forceinline__ void load(int index, const float* rays_t, const float* weights_sum, const float* depth, const float* image) {
+        t = rays_t[index]; ws = weights_sum[index]; d = depth[index];
+        r = image[3 * (size_t)index]; g = image[3 * (size_t)index + 1]; b = image[3 * (size_t)index + 2];
+    }
+    // one slot {sigma, deltas d0 d1, colour}; true: the ray stops here (an unfilled slot, or the transmittance in front of it was below T_thresh)
+    __device__ __forceinline__ bool add_slot(float sigma, float d0, float d1, float c0, float c1, float c2, float T_thresh) {
+        if (d0 == 0.0f) return true;
+        const float alpha = 1.0f - expf(-sigma * d0);
+        const float T = 1.0f - ws;
+        const float w = alpha * T;
+        ws += w;
+        t += d1;
+        d += w * t;
+        r += w * c0; g += w * c1; b += w * c2;
+        return T < T_thresh;
+    }
+    // stopped: slot n of rays_alive is retired; otherwise the ray's parameter moves on
+    __device__ __forceinline__ void store(bool stopped, uint32_t n, int index, int* rays_alive, float* rays_t, float* weights_sum, float* depth,
+                                          float* image) const {
+        if (stopped) rays_alive[n] = -1;
+        else rays_t[index] = t;
+        weights_sum[index] = ws;
+        depth[index] = d;
+        image[3 * (size_t)index] = r; image[3 * (size_t)index + 1] = g; image[3 * (size_t)index + 2] = b;
+    }
+};
 
 // inference compositor: n_step is small (1..8 in practice) and n_alive large -> one lane per ray.
 __global__ __launch_bounds__(kBlock) void k_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh,
@@ -901,32 +900,20 @@ __global__ __launch_bounds__(kBlock) void k_composite_rays(uint32_t n_alive, uin
     const float* s = sigmas + (size_t)n * n_step;
     const float* c = rgbs + 3 * (size_t)n * n_step;
     const float* dl = deltas + 2 * (size_t)n * n_step;
-    float t = rays_t[index], ws = weights_sum[index], d = depth[index];
-    float r = image[3 * (size_t)index], g = image[3 * (size_t)index + 1], b = image[3 * (size_t)index + 2];
+    RayAccum a;
+    a.load(index, rays_t, weights_sum, depth, image);
     uint32_t step = 0;
     while (step < n_step) {
-        if (dl[0] == 0.0f) break;
-        const float alpha = 1.0f - expf(-s[0] * dl[0]);
-        const float T = 1.0f - ws;
-        const float w = alpha * T;
-        ws += w;
-        t += dl[1];
-        d += w * t;
-        r += w * c[0]; g += w * c[1]; b += w * c[2];
-        if (T < T_thresh) break;
+        if (a.add_slot(s[0], dl[0], dl[1], c[0], c[1], c[2], T_thresh)) break;
         ++s; c += 3; dl += 2; ++step;
     }
-    if (step < n_step) rays_alive[n] = -1;
-    else rays_t[index] = t;
-    weights_sum[index] = ws;
-    depth[index] = d;
-    image[3 * (size_t)index] = r; image[3 * (size_t)index + 1] = g; image[3 * (size_t)index + 2] = b;
+    a.store(step < n_step, n, index, rays_alive, rays_t, weights_sum, depth, image);
 }
 
 // The same accumulation with EIGHT lanes per ray (n_step <= 8): lane j of a group loads slot j of its ray, so the loads of
 // a wave are contiguous (sigma 4 B, rgb 12 B, deltas 8 B per lane) instead of 64 lanes striding over 8-slot records; the
 // serial recurrence then runs on values broadcast inside the group (every lane of a group carries the same state, lane 0
-// stores it).  Same operations in the same order as k_composite_rays: identical results.
+// stores it).  The recurrence is RayAccum::add_slot, the one k_composite_rays runs: identical results.
 __global__ __launch_bounds__(kBlock) void k_composite_rays_g8(uint32_t n_alive, uint32_t n_step, float T_thresh,
                                                               int* __restrict__ rays_alive, float* __restrict__ rays_t,
                                                               const float* __restrict__ sigmas, const float* __restrict__ rgbs,
@@ -942,32 +929,18 @@ __global__ __launch_bounds__(kBlock) void k_composite_rays_g8(uint32_t n_alive, 
     const float d0 = has ? deltas[2 * slot] : 0.0f, d1 = has ? deltas[2 * slot + 1] : 0.0f;
     const float c0 = has ? rgbs[3 * slot] : 0.0f, c1 = has ? rgbs[3 * slot + 1] : 0.0f, c2 = has ? rgbs[3 * slot + 2] : 0.0f;
     const int index = rays_alive[nn];
-    float t = rays_t[index], ws = weights_sum[index], d = depth[index];
-    float r = image[3 * (size_t)index], g = image[3 * (size_t)index + 1], b = image[3 * (size_t)index + 2];
+    RayAccum a;
+    a.load(index, rays_t, weights_sum, depth, image);
     uint32_t step = 0;
     bool stopped = false;
     for (uint32_t k = 0; k < 8u; ++k) {  // uniform trip count: the shuffles need every lane
         const float sk = __shfl(sg, (int)k, 8), dk0 = __shfl(d0, (int)k, 8), dk1 = __shfl(d1, (int)k, 8);
         const float ck0 = __shfl(c0, (int)k, 8), ck1 = __shfl(c1, (int)k, 8), ck2 = __shfl(c2, (int)k, 8);
         if (stopped || k >= n_step) continue;
-        if (dk0 == 0.0f) { stopped = true; continue; }
-        const float alpha = 1.0f - expf(-sk * dk0);
-        const float T = 1.0f - ws;
-        const float w = alpha * T;
-        ws += w;
-        t += dk1;
-        d += w * t;
-        r += w * ck0; g += w * ck1; b += w * ck2;
-        if (T < T_thresh) { stopped = true; continue; }
-        ++step;
+        stopped = a.add_slot(sk, dk0, dk1, ck0, ck1, ck2, T_thresh);
+        if (!stopped) ++step;
     }
-    if (ray_ok && j == 0u) {
-        if (step < n_step) rays_alive[n] = -1;
-        else rays_t[index] = t;
-        weights_sum[index] = ws;
-        depth[index] = d;
-        image[3 * (size_t)index] = r; image[3 * (size_t)index + 1] = g; image[3 * (size_t)index + 2] = b;
-    }
+    if (ray_ok && j == 0u) a.store(step < n_step, n, index, rays_alive, rays_t, weights_sum, depth, image);
 }
 
 }  // namespace
@@ -1014,31 +987,52 @@ NVSF_API int nvsf_packbits(const float* grid, uint32_t N, float density_thresh, 
     return nvsf_launch_status();
 }
 
+// the occupancy grid the marcher can walk: 1..8 cascades of 2..1024 (the spread table's size) cells a side
+static bool march_grid_ok(uint32_t C, uint32_t H, uint32_t max_steps) { return C >= 1 && C <= 8 && H >= 2 && H <= 1024 && max_steps >= 1; }
+
+// The argument list the three nvsf_march_rays_train* entries share (include/nvsf_hip.h), filled once per entry
+struct MarchTrainArgs {
+    const float *rays_o, *rays_d;
+    const uint8_t* grid;
+    float bound, dt_gamma;
+    uint32_t max_steps, N, C, H, M;
+    const float *nears, *fars;
+    float *xyzs, *dirs, *deltas;
+    int32_t *rays, *counter;
+    const float* noises;
+};
+static bool march_train_args_ok(const MarchTrainArgs& a) {
+    return a.rays_o && a.rays_d && a.grid && a.nears && a.fars && a.xyzs && a.dirs && a.deltas && a.rays && a.counter && a.noises &&
+           march_grid_ok(a.C, a.H, a.max_steps);
+}
+
 // count / scan / write as three launches: no inter-workgroup wait, no scratch (the form the one-launch kernel falls back to)
+static int march_train_passes(const MarchTrainArgs& a, hipStream_t stream) {
+    if (a.N == 0) return NVSF_OK;
+    REQUIRE(march_train_args_ok(a));
+    const int variant = nvsf_variant(kVarMarch);  // tests: 1 = one thread per ray (first formulation), 2 = wave kernels, batch walked member by member
+    if (variant == 1) {
+        hipLaunchKernelGGL(k_march_count, dim3(cdiv(a.N, kBlock)), dim3(kBlock), 0, stream, a.rays_o, a.rays_d, a.grid, a.bound, a.dt_gamma,
+                           a.max_steps, a.N, a.C, a.H, a.nears, a.fars, a.noises, a.rays);
+        hipLaunchKernelGGL(k_march_scan, dim3(1), dim3(1024), 0, stream, a.N, a.rays, a.counter);
+        hipLaunchKernelGGL(k_march_write, dim3(cdiv(a.N, kBlock)), dim3(kBlock), 0, stream, a.rays_o, a.rays_d, a.grid, a.bound, a.dt_gamma,
+                           a.max_steps, a.N, a.C, a.H, a.M, a.nears, a.fars, a.noises, a.rays, a.xyzs, a.dirs, a.deltas);
+        return nvsf_launch_status();
+    }
+    const int serial = variant == 2;
+    const dim3 wgrid(cdiv(a.N, kBlock / kWave));
+    hipLaunchKernelGGL(k_march_count_wave, wgrid, dim3(kBlock), 0, stream, a.rays_o, a.rays_d, a.grid, a.bound, a.dt_gamma, a.max_steps, a.N,
+                       a.C, a.H, a.nears, a.fars, a.noises, a.rays, serial);
+    hipLaunchKernelGGL(k_march_scan, dim3(1), dim3(1024), 0, stream, a.N, a.rays, a.counter);
+    hipLaunchKernelGGL(k_march_write_wave, wgrid, dim3(kBlock), 0, stream, a.rays_o, a.rays_d, a.grid, a.bound, a.dt_gamma, a.max_steps, a.N,
+                       a.C, a.H, a.M, a.nears, a.fars, a.noises, a.rays, a.xyzs, a.dirs, a.deltas, serial);
+    return nvsf_launch_status();
+}
 NVSF_API int nvsf_march_rays_train_passes(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
                                           uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
                                           const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays,
                                           int32_t* counter, const float* noises, hipStream_t stream) {
-    if (N == 0) return NVSF_OK;
-    REQUIRE(rays_o && rays_d && grid && nears && fars && xyzs && dirs && deltas && rays && counter && noises);
-    REQUIRE(C >= 1 && C <= 8 && H >= 2 && H <= 1024 && max_steps >= 1);
-    const int variant = nvsf_variant(kVarMarch);  // tests: 1 = one thread per ray (first formulation), 2 = wave kernels, batch walked member by member
-    if (variant == 1) {
-        hipLaunchKernelGGL(k_march_count, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, stream, rays_o, rays_d, grid, bound, dt_gamma,
-                           max_steps, N, C, H, nears, fars, noises, rays);
-        hipLaunchKernelGGL(k_march_scan, dim3(1), dim3(1024), 0, stream, N, rays, counter);
-        hipLaunchKernelGGL(k_march_write, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, stream, rays_o, rays_d, grid, bound, dt_gamma,
-                           max_steps, N, C, H, M, nears, fars, noises, rays, xyzs, dirs, deltas);
-        return nvsf_launch_status();
-    }
-    const int serial = variant == 2;
-    const dim3 wgrid(cdiv(N, kBlock / kWave));
-    hipLaunchKernelGGL(k_march_count_wave, wgrid, dim3(kBlock), 0, stream, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H,
-                       nears, fars, noises, rays, serial);
-    hipLaunchKernelGGL(k_march_scan, dim3(1), dim3(1024), 0, stream, N, rays, counter);
-    hipLaunchKernelGGL(k_march_write_wave, wgrid, dim3(kBlock), 0, stream, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M,
-                       nears, fars, noises, rays, xyzs, dirs, deltas, serial);
-    return nvsf_launch_status();
+    return march_train_passes({rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays, counter, noises}, stream);
 }
 
 // compute units of the current device (one process drives one GPU): the persistent launch below fills each with kMarchWgPerCu workgroups
@@ -1054,25 +1048,29 @@ static int march_cu_count() {
 // ticket queue heads (one 128-byte line each) + {sum, exclusive prefix} flag per ticket of kMarchRays rays
 NVSF_API size_t nvsf_march_rays_train_ws_bytes(uint32_t N) { return 8u * (size_t)(kMarchHeadWords + 2u * cdiv(N, (uint32_t)kMarchRays)); }
 
+static int march_train_ws(const MarchTrainArgs& a, void* workspace, size_t workspace_bytes, uint32_t spin_limit, hipStream_t stream) {
+    if (a.N == 0) return NVSF_OK;
+    REQUIRE(march_train_args_ok(a) && workspace);
+    REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0 && workspace_bytes >= nvsf_march_rays_train_ws_bytes(a.N));
+    const int serial = nvsf_variant(kVarMarch) == 2;  // tests: the batch walked member by member
+    if (hipMemsetAsync(workspace, 0, nvsf_march_rays_train_ws_bytes(a.N), stream) != hipSuccess) return (int)hipGetLastError();
+    const bool off32 = (unsigned long long)a.M * 12ull < (1ull << 32), plain = a.dt_gamma == 0.0f && !serial;
+    auto kernel = off32 ? (plain ? k_march_train_onepass<true, true> : k_march_train_onepass<true, false>)
+                        : (plain ? k_march_train_onepass<false, true> : k_march_train_onepass<false, false>);
+    // the scanner + one worker per ticket until the chip is full (kMarchWgPerCu workgroups per compute unit)
+    const uint32_t wanted = 1u + cdiv(a.N, (uint32_t)kMarchRays), resident = kMarchWgPerCu * (uint32_t)march_cu_count();
+    hipLaunchKernelGGL(kernel, dim3(wanted < resident ? wanted : resident), dim3(kBlock), a.H * sizeof(uint32_t), stream, a.rays_o, a.rays_d, a.grid,
+                       a.bound, a.dt_gamma, a.max_steps, a.N, a.C, a.H, a.M, a.nears, a.fars, a.noises, a.rays, a.counter,
+                       reinterpret_cast<unsigned long long*>(workspace), a.xyzs, a.dirs, a.deltas, serial, spin_limit ? spin_limit : kMarchSpinLimit,
+                       (uint32_t)nvsf_variant(kVarMarchSkew));
+    return nvsf_launch_status();
+}
 NVSF_API int nvsf_march_rays_train_ws(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
                                       uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
                                       const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
                                       const float* noises, void* workspace, size_t workspace_bytes, uint32_t spin_limit, hipStream_t stream) {
-    if (N == 0) return NVSF_OK;
-    REQUIRE(rays_o && rays_d && grid && nears && fars && xyzs && dirs && deltas && rays && counter && noises && workspace);
-    REQUIRE(C >= 1 && C <= 8 && H >= 2 && H <= 1024 && max_steps >= 1);
-    REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0 && workspace_bytes >= nvsf_march_rays_train_ws_bytes(N));
-    const int serial = nvsf_variant(kVarMarch) == 2;  // tests: the batch walked member by member
-    if (hipMemsetAsync(workspace, 0, nvsf_march_rays_train_ws_bytes(N), stream) != hipSuccess) return (int)hipGetLastError();
-    const bool off32 = (unsigned long long)M * 12ull < (1ull << 32), plain = dt_gamma == 0.0f && !serial;
-    auto kernel = off32 ? (plain ? k_march_train_onepass<true, true> : k_march_train_onepass<true, false>)
-                        : (plain ? k_march_train_onepass<false, true> : k_march_train_onepass<false, false>);
-    // the scanner + one worker per ticket until the chip is full (kMarchWgPerCu workgroups per compute unit)
-    const uint32_t wanted = 1u + cdiv(N, (uint32_t)kMarchRays), resident = kMarchWgPerCu * (uint32_t)march_cu_count();
-    hipLaunchKernelGGL(kernel, dim3(wanted < resident ? wanted : resident), dim3(kBlock), H * sizeof(uint32_t), stream, rays_o, rays_d, grid, bound, dt_gamma,
-                       max_steps, N, C, H, M, nears, fars, noises, rays, counter, reinterpret_cast<unsigned long long*>(workspace), xyzs, dirs,
-                       deltas, serial, spin_limit ? spin_limit : kMarchSpinLimit, (uint32_t)nvsf_variant(kVarMarchSkew));
-    return nvsf_launch_status();
+    return march_train_ws({rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays, counter, noises}, workspace,
+                          workspace_bytes, spin_limit, stream);
 }
 
 // Scratch of the reference-shaped entry below.  SURVEY 8b's ownership rule is "native code never allocates": the entry points that
@@ -1130,16 +1128,15 @@ NVSF_API int nvsf_march_rays_train(const float* rays_o, const float* rays_d, con
                                    const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays,
                                    int32_t* counter, const float* noises, hipStream_t stream) {
     if (N == 0) return NVSF_OK;
+    const MarchTrainArgs a = {rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays, counter, noises};
     void* scratch = nullptr;
     const size_t bytes = nvsf_march_rays_train_ws_bytes(N);
     scratch_pool_hold_once();
     if (nvsf_variant(kVarMarch) != 0 || hipMallocAsync(&scratch, bytes, stream) != hipSuccess || !scratch) {
         (void)hipGetLastError();
-        return nvsf_march_rays_train_passes(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays,
-                                            counter, noises, stream);
+        return march_train_passes(a, stream);
     }
-    const int st = nvsf_march_rays_train_ws(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays,
-                                            counter, noises, scratch, bytes, 0u, stream);
+    const int st = march_train_ws(a, scratch, bytes, 0u, stream);
     const hipError_t fr = hipFreeAsync(scratch, stream);
     return st != NVSF_OK ? st : (fr == hipSuccess ? NVSF_OK : (int)fr);
 }
@@ -1172,7 +1169,7 @@ NVSF_API int nvsf_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* r
                              float* dirs, float* deltas, const float* noises, hipStream_t stream) {
     if (n_alive == 0 || n_step == 0) return NVSF_OK;
     REQUIRE(rays_alive && rays_t && rays_o && rays_d && grid && nears && fars && xyzs && dirs && deltas && noises);
-    REQUIRE(C >= 1 && C <= 8 && H >= 2 && H <= 1024 && max_steps >= 1);
+    REQUIRE(march_grid_ok(C, H, max_steps));
     if (n_step == 8u && (reinterpret_cast<uintptr_t>(xyzs) & 15u) == 0 && (reinterpret_cast<uintptr_t>(dirs) & 15u) == 0 &&
         (reinterpret_cast<uintptr_t>(deltas) & 15u) == 0) {
         hipLaunchKernelGGL(k_march_rays8, dim3(cdiv(n_alive, kBlock)), dim3(kBlock), 0, stream, n_alive, rays_alive, rays_t, rays_o, rays_d,

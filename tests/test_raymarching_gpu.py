@@ -503,7 +503,7 @@ def test_composite_rays_train_against_fp64(rm, dev, T_thresh):
     assert k_c <= 4.0 * r["mult_c"], f"grad_rgbs: {k_c:.3g} units, the oracle {r['mult_c']:.3g}"
 
 
-@pytest.mark.parametrize("n_step", [4, 8, 3, 1])  # 8: the record-store march kernel; <= 8: eight lanes per ray in composite_rays
+@pytest.mark.parametrize("n_step", [4, 8, 3, 1, 12])  # 8: the record-store march kernel; <= 8: eight lanes per ray in composite_rays; 12: one lane per ray (k_composite_rays)
 def test_inference_march_and_composite_loop(rm, dev, scene, n_step):
     """The n_alive loop of the reference's docstrings (raymarching.py:389-409, 480-493), against the oracle."""
     n, max_steps = 1500, 256
