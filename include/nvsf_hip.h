@@ -1031,6 +1031,50 @@ int nvsf_quantize_u8(const float* x, uint32_t n, int srgb, uint8_t* out, nvsf_st
 /* ref: utils.linear_to_srgb, nvsf/nerf/utils.py:31-36.  The colour transform of nvsf_quantize_u8 alone: out [n] fp32.  One launch. */
 int nvsf_linear_to_srgb(const float* x, uint32_t n, float* out, nvsf_stream_t stream);
 
+/* ---- 15. hierarchical importance resampling of the uniform ray render ---------------------------------------------------------- */
+
+/* Contract as sections 10 to 14: status return, explicit stream, no allocation, caller-owned buffers, NVSF_ERR_INVALID_ARG (null
+ * pointer, zero size) or NVSF_ERR_UNSUPPORTED (a size beyond what the per-wave LDS plan holds) before any launch, outputs untouched.
+ * A batch of 0 rays is a no-op.  DESIGN.md section 9j has the specification of the pass these four entries make up. */
+
+/* ref: sample_pdf, nvsf/nerf/models/renderer_dynamic.py:8-52, with the draws supplied by the caller.  bins [B, nb], weights
+ * [B, nb - 1], samples [B, U]; u [U] shared by all rays (u_per_ray = 0) or [B, U] (u_per_ray != 0); samples come in the order of u.
+ * weights + 1e-5 is formed in fp32; the sum, the pdf, the running cdf (leading 0) and the interpolation
+ *   inds = searchsorted(cdf, u, right = True), below = max(inds - 1, 0), above = min(inds, nb - 1),
+ *   denom = cdf[above] - cdf[below], 1 where it is below (double)1e-5f,
+ *   sample = bins[below] + (u - cdf[below]) / denom * (bins[above] - bins[below])
+ * are float64, rounded to fp32 once.  One wave per ray, the ray's bins and cdf in LDS, a cross-lane scan for the cdf, one binary
+ * search per draw.  2 <= nb <= 1024, 1 <= U <= 65536.  One launch. */
+int nvsf_sample_pdf(const float* bins, const float* weights, const float* u, uint32_t u_per_ray, uint32_t B, uint32_t nb, uint32_t U,
+                    float* samples, nvsf_stream_t stream);
+
+/* ref: the hierarchical pass NeRFRenderer.run was derived from: the missing call site of sample_pdf,
+ * nvsf/nerf/models/renderer_dynamic.py:8-52, whose `[N, T+t]` rows the comments of run still name
+ * (renderer_dynamic.py:181-194).  rays_o, rays_d [N, 3], aabb [6], z_vals, weights [N, T] (the coarse row and its compositing
+ * weights), u as above.  In one launch: bins mid[i] = z[i] + 0.5 (z[i+1] - z[i]) (fp32, T - 1 of them); pdf weights weights[:, 1 : T-1] with
+ * non-finite and negative entries counted as 0; nvsf_sample_pdf's device function on them; the U new depths sorted ascending into
+ * z_new [N, U]; xyz_new [N, U, 3] = clip(o + d z, aabb) with nvsf_uniform_samples' operations (product, then sum, no fma);
+ * z_merged [N, T + U] = the stable merge of the coarse row and z_new (on equal values the coarse sample first); src [N, T + U] int32
+ * = the index into cat([coarse, new]) each merged slot came from, a permutation of 0 .. T + U - 1 per ray.
+ * The merge goes by rank (two binary searches per element).  3 <= T <= 1024, 1 <= U <= 256, N (T + U) < 2^31. */
+int nvsf_resample_merge(const float* rays_o, const float* rays_d, const float* aabb, const float* z_vals, const float* weights,
+                        const float* u, uint32_t u_per_ray, uint32_t N, uint32_t T, uint32_t U, float* z_new, float* xyz_new,
+                        float* z_merged, int32_t* src, nvsf_stream_t stream);
+
+/* ref: the `torch.cat` + `torch.gather` by the sort index that follows sample_pdf in the renderer run was derived from: the
+ * per-sample rows of the density outputs, nvsf/nerf/models/renderer_dynamic.py:177-199, in `[N, T+t]` order.  a [N, T, row_bytes],
+ * b [N, U, row_bytes], src [N, T + U] as nvsf_resample_merge writes it:
+ * out[n, s] = cat(a[n], b[n])[src[n, s]], rows of any element type copied as bytes (16-byte vectors where row_bytes and the three
+ * pointers are multiples of 16, else 4-, 2- or 1-byte units).  An index outside [0, T + U) moves nothing.  N (T + U) < 2^31.
+ * One launch. */
+int nvsf_merge_rows(const void* a, const void* b, const int32_t* src, uint32_t N, uint32_t T, uint32_t U, uint32_t row_bytes, void* out,
+                    nvsf_stream_t stream);
+
+/* ref: autograd of the gather above (the rows of nvsf/nerf/models/renderer_dynamic.py:177-199).  The reverse copy:
+ * a[n, src[n, s]] or b[n, src[n, s] - T] = merged[n, s].  src is a permutation per ray, so every row of a and b is written exactly once: no atomics, and as the gradient of nvsf_merge_rows it is exact. */
+int nvsf_split_rows(const void* merged, const int32_t* src, uint32_t N, uint32_t T, uint32_t U, uint32_t row_bytes, void* a, void* b,
+                    nvsf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,11 @@ SIGNATURES = {
     "nvsf_pano_to_cloud": [_P, _P, _U, _U, _P, _P, _P, ctypes.c_size_t, _P, _P, _U, _P],
     "nvsf_quantize_u8": [_P, _U, _I, _P],
     "nvsf_linear_to_srgb": [_P, _U, _P],
+    # section 15: hierarchical importance resampling
+    "nvsf_sample_pdf": [_P, _P, _P, _U, _U, _U, _U, _P],
+    "nvsf_resample_merge": [_P, _P, _P, _P, _P, _P, _U, _U, _U, _U, _P, _P, _P, _P],
+    "nvsf_merge_rows": [_P, _P, _P, _U, _U, _U, _U, _P],
+    "nvsf_split_rows": [_P, _P, _U, _U, _U, _U, _P, _P],
 }
 
 _lib = None

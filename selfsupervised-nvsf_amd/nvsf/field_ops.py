@@ -1260,6 +1260,126 @@ class CompositeImageFn(Function):
 
 
 # ------------------------------------------------------------------------------------------------
+# hierarchical importance resampling (include/nvsf_hip.h section 15)
+# ------------------------------------------------------------------------------------------------
+RESAMPLE_MAX_BINS = 1024     # nb of nvsf_sample_pdf
+RESAMPLE_MAX_DRAWS = 1 << 16  # U of nvsf_sample_pdf
+RESAMPLE_MAX_COARSE = 1024   # T of nvsf_resample_merge
+RESAMPLE_MAX_FINE = 256      # U of nvsf_resample_merge
+_U_CACHE = {}
+
+
+def check_resample_sizes(T, U):
+    """ValueError for a (num_steps, upsample_steps) pair the hierarchical pass does not take (csrc/resample.hip keeps a ray's
+    float64 cdf, its coarse row and its new depths in LDS)."""
+    T, U = int(T), int(U)
+    if T < 3:
+        raise ValueError(f"hierarchical resampling needs num_steps >= 3 (the pdf has num_steps - 2 weights), got {T}")
+    if U < 1:
+        raise ValueError(f"hierarchical resampling needs upsample_steps >= 1, got {U}")
+    if T > RESAMPLE_MAX_COARSE or U > RESAMPLE_MAX_FINE:
+        raise ValueError(f"hierarchical resampling takes num_steps <= {RESAMPLE_MAX_COARSE} and upsample_steps <= {RESAMPLE_MAX_FINE}, "
+                         f"got {T} and {U}")
+
+
+def stratified_u(U, device):
+    """torch.linspace(0.5 / U, 1 - 0.5 / U, U) as the host forms it in fp32, on `device`, cached (the deterministic draws of sample_pdf,
+    renderer_dynamic.py:29-31)."""
+    key = (int(U), str(device))
+    if key not in _U_CACHE:
+        _U_CACHE[key] = torch.linspace(0.0 + 0.5 / int(U), 1.0 - 0.5 / int(U), steps=int(U)).to(device)
+    return _U_CACHE[key]
+
+
+def _draws(u, B, U):
+    u = u.float().contiguous()
+    if tuple(u.shape) == (U,):
+        return u, 0
+    if tuple(u.shape) == (B, U):
+        return u, 1
+    raise ValueError(f"u is [U] (shared by all rays) or [B, U], got {tuple(u.shape)} for B = {B}, U = {U}")
+
+
+def sample_pdf(bins, weights, u):
+    """bins [B, nb], weights [B, nb - 1], u [U] or [B, U] -> samples [B, U] in the order of u (renderer_dynamic.py:8-52, float64 inside)."""
+    bins, weights = bins.float().contiguous(), weights.float().contiguous()
+    B, nb = bins.shape
+    if tuple(weights.shape) != (B, nb - 1):
+        raise ValueError(f"weights is [B, nb - 1] = {(B, nb - 1)}, got {tuple(weights.shape)}")
+    U = int(u.shape[-1])
+    if nb < 2 or U < 1:
+        raise ValueError(f"sample_pdf needs at least two bins and one draw, got {nb} and {U}")
+    if nb > RESAMPLE_MAX_BINS or U > RESAMPLE_MAX_DRAWS:
+        raise ValueError(f"sample_pdf takes at most {RESAMPLE_MAX_BINS} bins and {RESAMPLE_MAX_DRAWS} draws per ray, got {nb} and {U}")
+    u, per_ray = _draws(u, B, U)
+    ptrs = (_hip.ptr(bins), _hip.ptr(weights), _hip.ptr(u))  # a CPU tensor fails here
+    samples = torch.empty(B, U, dtype=torch.float32, device=bins.device)
+    _hip.call("nvsf_sample_pdf", *ptrs, per_ray, B, nb, U, _hip.ptr(samples))
+    return samples
+
+
+def resample_merge(rays_o, rays_d, aabb, z_vals, weights, u):
+    """Steps 2-4 of the hierarchical pass in one launch: (z_new [N,U] sorted, xyz_new [N,U,3], z_merged [N,T+U], src [N,T+U] int32)."""
+    z_vals, weights = z_vals.float().contiguous(), weights.float().contiguous()
+    N, T = z_vals.shape
+    U = int(u.shape[-1])
+    check_resample_sizes(T, U)
+    if tuple(weights.shape) != (N, T):
+        raise ValueError(f"weights is [N, T] = {(N, T)}, got {tuple(weights.shape)}")
+    u, per_ray = _draws(u, N, U)
+    rays_o, rays_d = rays_o.float().contiguous(), rays_d.float().contiguous()
+    ptrs = [_hip.ptr(t) for t in (rays_o, rays_d, aabb, z_vals, weights, u)]  # a CPU tensor fails here
+    dev = z_vals.device
+    z_new = torch.empty(N, U, dtype=torch.float32, device=dev)
+    xyz_new = torch.empty(N, U, 3, dtype=torch.float32, device=dev)
+    z_merged = torch.empty(N, T + U, dtype=torch.float32, device=dev)
+    src = torch.empty(N, T + U, dtype=torch.int32, device=dev)
+    _hip.call("nvsf_resample_merge", *ptrs, per_ray, N, T, U, _hip.ptr(z_new), _hip.ptr(xyz_new), _hip.ptr(z_merged), _hip.ptr(src))
+    return z_new, xyz_new, z_merged, src
+
+
+def _row_bytes(a, b, src):
+    ok = src.dim() == 2 and src.dtype == torch.int32 and a.dim() >= 2 and b.dim() >= 2 and a.dtype == b.dtype
+    if ok:
+        N, TU = src.shape
+        T, U = a.shape[1], b.shape[1]
+        ok = a.shape[0] == N and b.shape[0] == N and T + U == TU and a.shape[2:] == b.shape[2:]
+    if not ok:
+        raise ValueError(f"merge rows: a [N, T, ...] and b [N, U, ...] of one dtype with src int32 [N, T + U]; got {tuple(a.shape)} "
+                         f"{a.dtype}, {tuple(b.shape)} {b.dtype}, {tuple(src.shape)} {src.dtype}")
+    row = a.element_size()
+    for s in a.shape[2:]:
+        row *= int(s)
+    return N, T, U, row
+
+
+class MergeRowsFn(Function):
+    """(a [N,T,...], b [N,U,...], src int32 [N,T+U]) -> cat([a, b], 1) gathered by src: [N,T+U,...].  Rows of any dtype; the backward
+    is the reverse copy (src is a permutation per ray), exact."""
+
+    @staticmethod
+    def forward(ctx, a, b, src):
+        a, b, src = a.contiguous(), b.contiguous(), src.contiguous()
+        N, T, U, row = _row_bytes(a, b, src)
+        ptrs = (_hip.ptr(a), _hip.ptr(b), _hip.ptr(src))
+        out = torch.empty((N, T + U) + tuple(a.shape[2:]), dtype=a.dtype, device=a.device)
+        _hip.call("nvsf_merge_rows", *ptrs, N, T, U, row, _hip.ptr(out))
+        ctx.save_for_backward(src)
+        ctx.dims = (T, U, row, tuple(a.shape), tuple(b.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        (src,) = ctx.saved_tensors
+        T, U, row, a_shape, b_shape = ctx.dims
+        g_out = g_out.contiguous()
+        g_a = torch.empty(a_shape, dtype=g_out.dtype, device=g_out.device)
+        g_b = torch.empty(b_shape, dtype=g_out.dtype, device=g_out.device)
+        _hip.call("nvsf_split_rows", _hip.ptr(g_out), _hip.ptr(src), src.shape[0], T, U, row, _hip.ptr(g_a), _hip.ptr(g_b))
+        return g_a, g_b, None
+
+
+# ------------------------------------------------------------------------------------------------
 # fused uniform-render kernels (static hash field)
 # ------------------------------------------------------------------------------------------------
 L2_BYTES_PER_XCD = 4 << 20

@@ -15,6 +15,10 @@ by HIP kernels instead of a chain of torch elementwise / cumprod ops:
 A network may additionally provide `fused_uniform_render(...)` (see network_static.py): when gradients are
 not being recorded the whole chain then runs as three fused kernels and the [N,T,3] positions, the masks
 and the per-sample colours are never materialised.
+
+`run(..., hierarchical=True)` adds the hierarchical pass `sample_pdf` (:8-52) belongs to -- its call site is missing from the
+reference -- on the operator chain: nvsf_resample_merge draws `upsample_steps` more depths per ray from the coarse weights and
+merges them into the row, nvsf_merge_rows carries the field outputs into that order.
 """
 import math
 
@@ -23,6 +27,19 @@ import torch.nn as nn
 
 from nvsf import field_ops as ops
 from nvsf.nerf.raymarching import raymarching
+
+
+def sample_pdf(bins, weights, n_samples, det=False, u=None):
+    """Hierarchical sampling by the inverse CDF (the reference's function, renderer_dynamic.py:8-52) as one HIP launch
+    (nvsf_sample_pdf: sum, pdf, cdf and interpolation in float64).
+    bins [B, T], weights [B, T - 1] -> [B, n_samples].  `det`: the draws are linspace(0.5 / n, 1 - 0.5 / n, n) for every ray, else
+    torch.rand per ray.  `u` (an extension): the draws, [n_samples] or [B, n_samples], instead of either."""
+    if u is None:
+        B = bins.shape[0]
+        u = ops.stratified_u(n_samples, bins.device) if det else torch.rand(B, int(n_samples), dtype=torch.float32, device=bins.device)
+    elif int(u.shape[-1]) != int(n_samples):
+        raise ValueError(f"u has {int(u.shape[-1])} draws per ray, n_samples is {int(n_samples)}")
+    return ops.sample_pdf(bins, weights, u)
 
 
 class NeRFRenderer(nn.Module):
@@ -122,10 +139,12 @@ class NeRFRenderer(nn.Module):
         return d["sigma"].float() * self.density_scale, rgbs
 
     def run_cuda(self, rays_o, rays_d, time, cal_lidar_color=False, dt_gamma=0, bg_color=None, perturb=False,
-                 force_all_rays=False, max_steps=1024, T_thresh=1e-4, **kwargs):
+                 force_all_rays=False, max_steps=1024, T_thresh=1e-4, hierarchical=False, **kwargs):
         """Occupancy-grid render: training mode packs all samples of the batch (march_rays_train ->
         field -> composite_rays_train, differentiable); evaluation mode advances the surviving rays a few steps
         at a time (march_rays -> field -> composite_rays) until all have terminated."""
+        if hierarchical:
+            raise ValueError("hierarchical resampling belongs to the uniform render (run); the occupancy-grid march has no coarse pass to resample")
         out_dim = self.out_lidar_color_dim if cal_lidar_color else self.out_color_dim
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
@@ -221,10 +240,41 @@ class NeRFRenderer(nn.Module):
             return self._lidar_range
         return raymarching.near_far_from_aabb(rays_o, rays_d, aabb, self.min_near)
 
+    def _render_hierarchical(self, rays_o, rays_d, nears, fars, T, U, aabb, noise, u, time, cal_lidar_color, bg_host, **kwargs):
+        """The hierarchical pass on the operator chain: coarse samples and density as in `run`, coarse weights
+        without autograd, U new depths per ray drawn from them and merged into the coarse row (ops.resample_merge, one launch), the
+        field's density on the new positions, every density output and the positions merged row-wise (ops.MergeRowsFn), then the
+        unchanged compositors on the T + U rows.  Returns (z_vals, weights, weights_sum, depth, image)."""
+        N = rays_o.shape[0]
+        z_vals, xyzs = ops.uniform_samples(rays_o, rays_d, nears, fars, T, aabb, noise)
+        with self._rows_hint().rows(T):
+            coarse = self.density(xyzs.view(-1, 3), time, cal_lidar_color, **kwargs)
+        with torch.no_grad():
+            w_coarse = ops.CompositeWeightsFn.apply(coarse["sigma"].detach().view(N, T), z_vals, nears, fars, self._k_scale())[0]
+        _, xyz_new, z_vals, src = ops.resample_merge(rays_o, rays_d, aabb, z_vals, w_coarse, u)
+        with self._rows_hint().rows(U):
+            fine = self.density(xyz_new.view(-1, 3), time, cal_lidar_color, **kwargs)
+        merged = {k: ops.MergeRowsFn.apply(v.reshape(N, T, -1), fine[k].reshape(N, U, -1), src) for k, v in coarse.items()}
+        xyz_arg = ops.MergeRowsFn.apply(xyzs, xyz_new, src).view(-1, 3)
+        dirs_arg = rays_d.view(-1, 1, 3).expand(N, T + U, 3).reshape(-1, 3)
+        sigma = merged.pop("sigma").view(N, T + U)
+        weights, weights_sum, depth = ops.CompositeWeightsFn.apply(sigma, z_vals, nears, fars, self._k_scale())
+        mask = weights > ops.W_THRESH
+        extra = {k: v.view(N * (T + U), -1) for k, v in merged.items()}
+        rgbs = self.color(xyz_arg, dirs_arg, cal_lidar_color=cal_lidar_color, mask=mask.reshape(-1), ray_dirs=rays_d, **extra)
+        bg_dev = ops.device_constant(bg_host, rays_o.device) if bg_host is not None else None
+        image = ops.CompositeImageFn.apply(weights, rgbs.view(N, T + U, self.out_dim), weights_sum, bg_dev)
+        return z_vals, weights, weights_sum, depth, image
+
     def run(self, rays_o, rays_d, time, cal_lidar_color=False, num_steps=768, upsample_steps=128, bg_color=None,
-            perturb=False, **kwargs):
+            perturb=False, hierarchical=False, **kwargs):
         """rays_o, rays_d: [B, N, 3] (B == 1).  Returns the reference's dictionary: depth / image /
-        weights_sum (with a `_lidar` suffix for LiDAR rays) plus `weights` and `z_vals` [N, T]."""
+        weights_sum (with a `_lidar` suffix for LiDAR rays) plus `weights` and `z_vals` [N, T].
+        `hierarchical=True` (with upsample_steps = U > 0): U more samples per ray are drawn from the coarse weights (sample_pdf) and
+        merged into the row; `weights` and `z_vals` are then [N, T + U].  The fused one-launch renders are bypassed.  By default
+        `upsample_steps` is ignored, as in the reference (its call site of sample_pdf was cut out)."""
+        if hierarchical:
+            ops.check_resample_sizes(num_steps, upsample_steps)
         self.out_dim = self.out_lidar_color_dim if cal_lidar_color else self.out_color_dim
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
@@ -233,6 +283,9 @@ class NeRFRenderer(nn.Module):
         aabb = self.aabb_train if self.training else self.aabb_infer
         nears, fars = self._near_far(rays_o, rays_d, cal_lidar_color, aabb)
         noise = torch.rand(N, T, dtype=torch.float32, device=rays_o.device) if perturb else None
+        if hierarchical:
+            U = int(upsample_steps)
+            u = torch.rand(N, U, dtype=torch.float32, device=rays_o.device) if perturb else ops.stratified_u(U, rays_o.device)
 
         per_ray_bg = None
         bg_host = None
@@ -252,7 +305,10 @@ class NeRFRenderer(nn.Module):
 
         fused = getattr(self, "fused_uniform_render", None)
         rendered = None
-        if fused is not None and not torch.is_grad_enabled():
+        if hierarchical:
+            rendered = self._render_hierarchical(rays_o, rays_d, nears, fars, T, U, aabb, noise, u, time, cal_lidar_color, bg_host,
+                                                 **kwargs)
+        elif fused is not None and not torch.is_grad_enabled():
             z_vals, weights, weights_sum, depth, image = fused(rays_o, rays_d, nears, fars, T, aabb, noise, cal_lidar_color,
                                                                bg_host, time=time, **kwargs)
         else:

@@ -32,7 +32,7 @@ class RenderTrainStep:
                  flow_loss=False, pc_list=None, ema_decay=0.95, split_backward=True, ray_chunks=1, grad_loss=False, depth_grad_loss="l1",
                  alpha_grad=0.1, patch_size_lidar=1, change_patch_size_lidar=(2, 8), change_patch_size_epoch=2, use_error_map=False,
                  sobel_grad=False, grad_norm_smooth=False, spatial_smooth=False, tv_loss=False, use_rgbd_loss=False, rgb_depth_loss="l1",
-                 alpha_rd=1.0, depth_loss="l1", raydrop_loss="mse", intensity_loss="mse", rgb_loss="mse"):
+                 alpha_rd=1.0, depth_loss="l1", raydrop_loss="mse", intensity_loss="mse", rgb_loss="mse", upsample_steps=0):
         """Defaults = the reference's CLI defaults (main_nvsf.py:60-97).  `scale`: the scene scale the chamfer loss divides by
         (opt.scale); `pc_list`: {frame index: [P, 3] tensor} world-frame point clouds for the scene-flow loss
         (Trainer.process_pointcloud, trainer.py:1848-1912, builds them from the range images); `ema_decay=None` disables EMA.
@@ -45,8 +45,21 @@ class RenderTrainStep:
         depth map batch["gt_rgb_depth"] (FrameSet(camera_depth=True)); switched on, both camera terms are one launch (CameraLossFn).
         `depth_loss`, `raydrop_loss`, `intensity_loss`, `rgb_loss` (main_nvsf.py:83-88): the criterion of each per-ray term, one of
         l1 / mse / huber / smoothl1 / bce; the defaults go through the entries they always did, anything else through the `_crit`
-        entries of csrc/losses.hip (and the error maps follow)."""
+        entries of csrc/losses.hip (and the error maps follow).
+        `upsample_steps` (main_nvsf.py:73) above 0: both modalities are rendered with `hierarchical=True, upsample_steps=...`
+        (NeRFRenderer.run: that many more samples per ray, drawn from the coarse weights); the line-of-sight loss then reads the
+        merged rows.  0, the default, leaves the step as it is."""
         self.model = model
+        self.upsample_steps = int(upsample_steps)
+        if self.upsample_steps < 0:
+            raise ValueError(f"upsample_steps is a sample count, got {upsample_steps}")
+        if self.upsample_steps > 0:
+            from nvsf import field_ops as _ops
+            _ops.check_resample_sizes(num_steps, self.upsample_steps)  # fails here, not at the first step
+            if getattr(model, "cuda_ray", False):
+                raise ValueError("upsample_steps > 0 renders with hierarchical=True, which the occupancy-grid path (run_cuda) "
+                                 "does not do: train this model with upsample_steps=0, or without its occupancy grid")
+        self._resample_kw = {"hierarchical": True, "upsample_steps": self.upsample_steps} if self.upsample_steps > 0 else {}
         self.criteria = {"depth_loss": str(depth_loss), "raydrop_loss": str(raydrop_loss), "intensity_loss": str(intensity_loss),
                          "rgb_loss": str(rgb_loss)}
         for option, name in self.criteria.items():
@@ -198,7 +211,7 @@ class RenderTrainStep:
             else:
                 gt_rd, gt_i, gt_d = batch["gt_raydrop"], batch["gt_intensity"], batch["gt_depth"]
             r = self._render(batch["rays_o_lidar"], batch["rays_d_lidar"], batch["time"], cal_lidar_color=True, perturb=True,
-                             num_steps=self.num_steps)
+                             num_steps=self.num_steps, **self._resample_kw)
             on_device = r["depth_lidar"].is_cuda
             pH, pW = self._patch_dims()
             if pH > 1 and self.grad_loss and not on_device:
@@ -233,7 +246,8 @@ class RenderTrainStep:
                 out["los"] = (UrfLossFn.apply if on_device else urf_line_of_sight_loss)(r["weights"], r["z_vals"], gt_d * gt_rd, eps)
         if "rays_o" in batch:
             gt_rgb = batch["gt_rgb"] if "gt_rgb" in batch else batch["images"][..., :3]
-            r = self._render(batch["rays_o"], batch["rays_d"], batch["time"], perturb=True, num_steps=self.num_steps, bg_color=1)
+            r = self._render(batch["rays_o"], batch["rays_d"], batch["time"], perturb=True, num_steps=self.num_steps, bg_color=1,
+                             **self._resample_kw)
             if not self.use_rgbd_loss:
                 if not r["image"].is_cuda:
                     out["rgb"] = rgb_loss_host(r["image"], gt_rgb, self.alpha_rgb, self.criteria["rgb_loss"], self.scale)

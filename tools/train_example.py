@@ -90,6 +90,8 @@ def main():
     ap.add_argument("--plain", action="store_true", help="no structural regularisation / error maps / patch epochs")
     ap.add_argument("--num-rays", type=int, default=4096)
     ap.add_argument("--num-steps", type=int, default=768)
+    ap.add_argument("--upsample-steps", type=int, default=0, metavar="U", help="hierarchical importance resampling: U more samples per ray drawn "
+                    "from the coarse weights (RenderTrainStep(upsample_steps=U), run(hierarchical=True)); training, --eval-table and --test-export")
     ap.add_argument("--dynamic", action="store_true", help="the reference's space-time model instead of the static hash field")
     ap.add_argument("--flow-loss", action="store_true", help="scene-flow supervision of the space-time model (needs --dynamic): the frames' "
                     "LiDAR clouds are cleaned on the device first (nvsf/nerf/pointcloud.py)")
@@ -180,7 +182,8 @@ def main():
                               use_error_map=not args.plain, change_patch_size_lidar=(1,) if args.plain else (2, 8),
                               flow_loss=args.flow_loss, pc_list=pc_list, use_rgbd_loss=args.rgbd_loss, use_urf_loss=args.urf_loss,
                               depth_loss=args.depth_loss, raydrop_loss=args.raydrop_loss, intensity_loss=args.intensity_loss,
-                              rgb_loss=args.rgb_loss)
+                              rgb_loss=args.rgb_loss, upsample_steps=args.upsample_steps)
+    resample_kw = {"hierarchical": True, "upsample_steps": args.upsample_steps} if args.upsample_steps > 0 else {}
     if not args.plain:
         trainer.attach_error_maps(data)
     it = 0
@@ -221,7 +224,7 @@ def main():
                   f"BCE {np.mean(losses[:5]):.4f} -> {np.mean(losses[-5:]):.4f}", flush=True)
     for label, r in ((("", None),) + ((("refined ", refiner),) if refiner is not None else ())):
         res = evaluate_frames(model, whole, args.num_steps, indices=range(min(len(whole), 4)), ema=trainer.ema,
-                              meters="table" if args.eval_table else None, refiner=r)
+                              meters="table" if args.eval_table else None, refiner=r, **resample_kw)
         if rank == 0:
             print(f"{label}evaluation over {res['frames']} frames: loss {res['loss']:.4f}, PSNR {res['psnr']:.2f} dB, range RMSE "
                   f"{res['depth_rmse_m']:.2f} m, chamfer distance {res['chamfer_distance']:.3f}, F-score {res['f_score']:.3f}")
@@ -234,7 +237,7 @@ def main():
         novel = FrameSet(root, args.sequence, "train", scale, device=dev, training=False, offset=args.offset, sensor=sensor)
         t0 = time.perf_counter()
         counts = export_frames(model, novel, args.test_export, f"{args.sequence}_ep{args.epochs:04d}", args.num_steps, refiner=refiner, ema=trainer.ema,
-                               write=(rank == 0))
+                               write=(rank == 0), **resample_kw)
         torch.cuda.synchronize()
         if rank == 0:
             what = "changed sensors" if novel.sensor is not None else "the recording's sensors"
