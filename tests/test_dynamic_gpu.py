@@ -53,7 +53,8 @@ def test_planes4d_forward_backward(dev):
 @pytest.mark.parametrize("dynamic_only", [False, True])
 def test_planes_backward_run_merging_equals_per_sample_atomics(dev, dynamic_only, variants):
     """The run-merging plane-gradient kernel (default) against the one-atomic-per-(sample, texel, channel) kernel -- itself
-    pinned by the reference's autograd above -- on ray-ordered rows (long runs inside one texel quad at the coarse scales,
+    pinned by the reference's autograd above at the fixture's shape, and both forms to the float64 restatement at wave and workgroup
+    edge shapes (tests/test_dynamic_f64_gpu.py::test_planes_fn) -- on ray-ordered rows (long runs inside one texel quad at the coarse scales,
     a constant time coordinate as in a training step), both `want` forms, M not a multiple of the chunk length."""
     from nvsf.nerf.models.planes_field import Planes4D
     rng = np.random.default_rng(3)
@@ -176,7 +177,8 @@ def test_constructor_options_outside_the_reference_configuration(dev):
 @pytest.mark.parametrize("t_val", [0.37, 0.0, 1.0])  # between two slices / exactly on the first / on the last slice
 def test_hashgrid4d_fused_training_path_equals_the_per_slice_path(dev, t_val, variants):
     """HashDynFn (fused forward + fused table-gradient kernel) against the per-slice operator path (six tcnn.Encoding calls,
-    blend, Lagrange reduction through autograd): same features, same gradients on the same slice parameters, none elsewhere."""
+    blend, Lagrange reduction through autograd): same features, same gradients on the same slice parameters, none elsewhere.  Both
+    forms are pinned to the float64 restatement, each on its own, in tests/test_dynamic_f64_gpu.py::test_hash_dynamic_training."""
     from nvsf.nerf.models.hash_field import HashGrid4D
     rng = np.random.default_rng(5)
     n_rays, T = 23, 150
@@ -291,7 +293,8 @@ def test_density_tail_training_path_equals_the_operator_path(dev, t_val, logit_g
 
 def test_flow_grid_training_path_equals_the_operator_path(dev):
     """FlowGridFn (fused grid + Lagrange forward kernel, table gradient straight from dL/d(reduced)) against encoder ->
-    .float() -> lagrange_reduce through autograd: flows and the gradient of the grid table and of the Linear layers."""
+    .float() -> lagrange_reduce through autograd: flows and the gradient of the grid table and of the Linear layers.  Both forms of
+    the grid are pinned to the float64 restatement, each on its own, in tests/test_dynamic_f64_gpu.py::test_flow_grid."""
     from nvsf.nerf.models.flow_field import FlowField
     xt = torch.cat([torch.rand(7000, 3, generator=torch.Generator().manual_seed(3)), torch.full((7000, 1), 0.43)], -1).to(dev)
     res = {}
@@ -732,7 +735,8 @@ def test_planes_forward_along_rays_is_bit_identical_and_multi_eval(dev, M, kind,
 def test_dynamic_hash_gradient_through_lds_equals_the_run_merging_kernel(dev, variants):
     """nvsf_hashgrid4d_dynamic_bwd_scalar: the LDS form (a workgroup accumulates one level of one pair -- 2^13 / 2^15 scalar sums --
     in LDS and adds it to the global sums once) against the run-merging global-atomic kernel (testing.variant(hash4d_bwd="runs"), itself pinned
-    through HashDynFn against the per-slice autograd path above): same sums up to fp32 addition order, on ray-ordered rows, with
+    through HashDynFn against the per-slice autograd path above, and both forms against the float64 restatement in
+    tests/test_dynamic_f64_gpu.py::test_hash_dynamic_training): same sums up to fp32 addition order, on ray-ordered rows, with
     zero gradients mixed in, accumulating into non-zero buffers."""
     import ctypes
     from nvsf import _hip
@@ -796,7 +800,8 @@ def test_dynamic_hash_gradient_through_lds_keeps_non_finite_gradients(dev, poiso
                                           (331 * 211, (True, True)), (70001, (False, True))])  # >= 2^16 rows: time planes through the LDS image
 def test_planes_multi_node_equals_one_node_per_evaluation(dev, M, neighbours):
     """ops.PlanesMultiFn (round 5: the K-planes of one density query as ONE autograd node -- nvsf_planes_multi_fwd / nvsf_planes_multi_bwd)
-    against one PlanesFn per evaluation, which is pinned by the reference's autograd (test_planes4d_forward_backward): features bit for
+    against one PlanesFn per evaluation, which is pinned by the reference's autograd (test_planes4d_forward_backward) at the fixture's shape;
+    both nodes are pinned to the float64 restatement at edge shapes in tests/test_dynamic_f64_gpu.py::test_planes_fn / ::test_planes_multi_fn: features bit for
     bit, the gradient of the flow offsets bit for bit (same arithmetic per row), texel gradients up to the order of the fp32 additions
     (the fused scatter merges the evaluations' addends of one texel quad); first / last frame (a neighbour absent) and no neighbour at all."""
     from nvsf import field_ops as ops
@@ -886,7 +891,7 @@ def test_time_plane_gradient_through_the_lds_image_equals_the_run_merging_kernel
     """k_planes_multi_bwd_time_lds (production for >= 2^16 rows: the time-plane evaluations of nvsf_planes_multi_bwd accumulate in 1-D fp64
     images in LDS, planes.hip) against k_planes_multi_bwd_runs (testing.variant(planes_bwd="global"): every evaluation as run sums
     into memory-side fp32 atomics, itself pinned against one PlanesFn per evaluation above and through that against the reference's
-    autograd): same sums up to fp32 addition order, accumulating into a non-zero buffer, the same texels touched; first / last frame
+    autograd; both forms against the float64 restatement in tests/test_dynamic_f64_gpu.py::test_planes_multi_fn): same sums up to fp32 addition order, accumulating into a non-zero buffer, the same texels touched; first / last frame
     (t = 0, 1: the upper time row carries weight 0 / is the border row); and two runs of the production form agree to 2e-6 (the fp64 image
     does not care about arrival order at this precision, what is left is the order of the slice sums per texel), where the run-merging form is
     only good for ~1e-5 here."""

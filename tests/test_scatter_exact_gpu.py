@@ -5,6 +5,8 @@ show that a scatter is UNCHANGED.  Here every addend is a non-negative multiple 
 any order of fp32 additions, the fp64 LDS images and the 2^(33-e) fixed-point image of the binned scatter are then all exact, and every
 formulation of an operator must be `torch.equal` to every other and to an fp64 sum formed on the CPU.  The CPU side asserts both
 properties of the inputs (ExactSum) before anything is compared, so a wrong choice of inputs fails there and not as noise on the GPU.
+These tests pin the ADDITION; the addends -- bilinear and corner weights, blend factors, Lagrange weights, the product rule -- are pinned
+against float64 restatements on generic inputs in tests/test_dynamic_f64_gpu.py (space-time encoders) and tests/test_static_grad_f64_gpu.py.
 
   grids   per_level_scale = 2 and an integer base resolution: every scale_l is an integer; positions are multiples of 1/8 in [0, 1] and
           gradients integers 0..3, so the weights are multiples of 2^-9 (3-D) / 2^-6 (2-D);
