@@ -91,7 +91,9 @@ __global__ __launch_bounds__(kBlock) void k_density_dynamic(DynFeat f, uint32_t 
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float s = half_sum ? r16(b[j] + c[j]) : (b[j] + c[j]);
-                const float q = half_sum ? r16(0.25f * s) : 0.25f * s;
+                // the fp16 product as an fp16 multiply (same value: a power of two times an fp16 number rounds once either way).  Written as
+                // r16(0.25f * s) it compiles to v_fma_mixlo_f16 with a +0 addend, and (-0) + (+0) = +0 loses the sign PyTorch keeps
+                const float q = half_sum ? (float)((_Float16)s * (_Float16)0.25f) : 0.25f * s;
                 xf[3][j] = (_Float16)(0.5f * a[j] + q);
             }
         } else {
