@@ -791,6 +791,24 @@ int nvsf_urf_loss_fwd(const float* weights, const float* z_vals, const float* gt
 int nvsf_urf_loss_bwd(const float* weights, const float* z_vals, const float* gt_depth, uint32_t N, uint32_t T, float eps, float eps_lo,
                       const double* state, const float* grad_loss, float* grad_weights, nvsf_stream_t stream);
 
+/* ref: the distortion loss of mip-NeRF 360 (Barron et al. 2022, eq. 15), sketched and commented out at
+ * nvsf/nerf/models/renderer_dynamic.py:242-245 ("tmp: reg loss in mip-nerf 360").  weights, z_vals [N, T] fp32 (z non-decreasing along
+ * a row, ties allowed), nears, fars [N] fp32; T >= 1, N T <= 2^31.  Per ray, with the compositor's intervals and R = far - near:
+ *   delta_i = z_{i+1} - z_i (i < T - 1), delta_{T-1} = R / T;  m_i = (z_i + delta_i / 2 - near) / R;  d_i = delta_i / R
+ *   ray = sum_i sum_j w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i  =  2 sum_i w_i (m_i W_<i - M_<i) + 1/3 sum_i w_i^2 d_i
+ *   loss = alpha sum_n ray_n / N;  a ray whose R is not finite or not > 0 gives 0 (and counts in N); non-finite weights propagate
+ * (W_<i, M_<i: exclusive prefix sums of w and w m).  Every term and both scans in fp64 from the fp32 inputs; ray_loss ([N], may be NULL)
+ * and loss are rounded once, loss from the fp64 per-ray values: per-workgroup partials (four rays each) in `workspace` (8-byte aligned,
+ * >= 8 ceil(N / 4) bytes), then one fold in block order; no atomics, bit-identical between runs.  N = 0 writes loss = 0.
+ * state (double [N][2]) receives the row totals (W, M) for the backward, which is one pass:
+ *   grad_weights[n][k] = grad_loss alpha / N (2 [m_k (W_<k - W_>k) - M_<k + M_>k] + 2/3 w_k d_k), every element written (zero rows for
+ *   the rays that gave 0); nothing flows to z_vals, nears or fars. */
+int nvsf_distortion_loss_fwd(const float* weights, const float* z_vals, const float* nears, const float* fars, uint32_t N, uint32_t T,
+                             float alpha, void* workspace, size_t ws_bytes, float* ray_loss, float* loss, double* state,
+                             nvsf_stream_t stream);
+int nvsf_distortion_loss_bwd(const float* weights, const float* z_vals, const float* nears, const float* fars, uint32_t N, uint32_t T,
+                             float alpha, const double* state, const float* grad_loss, float* grad_weights, nvsf_stream_t stream);
+
 /* ref: torch_ema.ExponentialMovingAverage.update as used by the Trainer (trainer.py:112-114 construction with decay 0.95,
  * :1420-1421 one update per epoch): shadow -= one_minus_decay * (shadow - param), fp32 [n]. */
 int nvsf_ema_update(float* shadow, const float* param, uint64_t n, float one_minus_decay, nvsf_stream_t stream);

@@ -683,6 +683,151 @@ __global__ __launch_bounds__(kUrfBlock) void k_urf_bwd(const float* __restrict__
     }
     for (uint32_t e = 4 * chunks + tid; e < total; e += stride) grad_w[e] = (float)(k * urf_grad_elem(w[e], z[e], g[e / T], eps, inv2s2, E));
 }
+
+// ---- distortion loss of mip-NeRF 360 (Barron et al. 2022, eq. 15) over weights / z_vals [N, T]: `distortion_loss` ------------------
+// Per ray, with the compositor's intervals (uniform.hip: delta_i = z_{i+1} - z_i, delta_{T-1} = (far - near) / T), R = far - near,
+//   m_i = (z_i + delta_i / 2 - near) / R,  d_i = delta_i / R                              (normalised midpoint and width)
+//   ray = sum_i sum_j w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i,   loss = alpha sum_n ray_n / N
+// z is non-decreasing, so the midpoints are, and the double sum is 2 sum_i w_i (m_i W_<i - M_<i) with the exclusive prefix sums of w and
+// w m: one scan per ray.  d ray / d w_k = 2 [m_k (W_<k - W_>k) - M_<k + M_>k] + 2/3 w_k d_k with the suffix sums from the row totals
+// the forward leaves in `state`, so the backward is one pass as well.  m W - M cancels (a ray whose weight sits in a few samples at
+// the far end loses 2e-5 of the loss in fp32): every term and both scans are fp64, rounded once on store.
+// One wave per ray, four rays per workgroup, lane = sample in tiles of 64 (4-byte loads, any alignment; z_{i+1} is a second load shifted
+// by one); the running totals cross the tiles in a wave-uniform pair.  A ray whose R is not finite or not > 0 (a camera ray that misses
+// the box) gives 0 and a zero gradient row.  No atomics: per-workgroup partials, one fold in block order, two runs give the same bits.
+constexpr int kDistBlock = 256, kDistRays = kDistBlock / kWave;
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ double dpp_add_f64(double v) {  // v + the DPP source lane's v; a lane without a source adds +0.0
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, kCtrl, kRowMask, 0xF, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), kCtrl, kRowMask, 0xF, false);
+    return v + __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+// inclusive fp64 add-scan over the 64 lanes, six DPP steps as wave_scan_max_u32 (common.h); every lane must be active
+__device__ __forceinline__ double wave_scan_add_f64(double v) {
+    v = dpp_add_f64<0x111, 0xF>(v);  // row_shr:1
+    v = dpp_add_f64<0x112, 0xF>(v);  // row_shr:2
+    v = dpp_add_f64<0x114, 0xF>(v);  // row_shr:4
+    v = dpp_add_f64<0x118, 0xF>(v);  // row_shr:8
+    v = dpp_add_f64<0x142, 0xA>(v);  // row_bcast:15 -> rows 1 and 3
+    v = dpp_add_f64<0x143, 0xC>(v);  // row_bcast:31 -> rows 2 and 3
+    return v;
+}
+__device__ __forceinline__ double wave_last_f64(double v) {  // lane 63's value, wave-uniform
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), 63);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+struct DistRay { double near, R, last; bool ok; };  // last = delta_{T-1} = R / T
+__device__ __forceinline__ DistRay dist_ray(const float* __restrict__ nears, const float* __restrict__ fars, uint32_t n, uint32_t T) {
+    DistRay r;
+    r.near = (double)nears[n];
+    r.R = (double)fars[n] - r.near;
+    r.ok = r.R > 0.0 && r.R < (double)INFINITY;
+    r.last = r.R / (double)T;
+    return r;
+}
+// one tile of a row: this lane's weight, midpoint and width (zero past T) and the prefix sums of w and w m over the row up to the lane
+struct DistTile { double w, m, d, w_lt, m_lt, w_le, m_le; bool valid; };
+__device__ __forceinline__ DistTile dist_tile(const float* __restrict__ w, const float* __restrict__ z, uint32_t base, uint32_t T,
+                                              const DistRay& r, double& run_w, double& run_m) {
+    const uint32_t i = base + (uint32_t)lane_id();
+    DistTile t;
+    t.valid = i < T;
+    t.w = t.m = t.d = 0.0;
+    double wm = 0.0;
+    if (t.valid) {
+        const double zi = (double)z[i], delta = i + 1 < T ? (double)z[i + 1] - zi : r.last;
+        t.w = (double)w[i];
+        t.m = (zi + delta / 2.0 - r.near) / r.R;
+        t.d = delta / r.R;
+        wm = t.w * t.m;
+    }
+    const double sw = wave_scan_add_f64(t.w), sm = wave_scan_add_f64(wm);
+    double ew = __shfl_up(sw, 1, 64), em = __shfl_up(sm, 1, 64);
+    if (lane_id() == 0) ew = em = 0.0;
+    t.w_lt = run_w + ew;
+    t.m_lt = run_m + em;
+    t.w_le = run_w + sw;
+    t.m_le = run_m + sm;
+    run_w += wave_last_f64(sw);
+    run_m += wave_last_f64(sm);
+    return t;
+}
+__global__ __launch_bounds__(kDistBlock) void k_distortion_fwd(const float* __restrict__ weights, const float* __restrict__ z_vals,
+                                                               const float* __restrict__ nears, const float* __restrict__ fars, uint32_t N,
+                                                               uint32_t T, float* __restrict__ ray_loss, double* __restrict__ state,
+                                                               double* __restrict__ partials) {
+    __shared__ double part[kDistRays];
+    const uint32_t wave = threadIdx.x >> 6, n = blockIdx.x * kDistRays + wave;
+    double ray = 0.0;  // whole waves take each branch: n and the ray's range are wave-uniform
+    if (n < N) {
+        const DistRay r = dist_ray(nears, fars, n, T);
+        double run_w = 0.0, run_m = 0.0;
+        if (r.ok) {
+            const float* w = weights + (size_t)n * T;
+            const float* z = z_vals + (size_t)n * T;
+            double pair = 0.0, self = 0.0;
+            for (uint32_t base = 0; base < T; base += kWave) {
+                const DistTile t = dist_tile(w, z, base, T, r, run_w, run_m);
+                if (t.valid) {
+                    pair += t.w * (t.m * t.w_lt - t.m_lt);
+                    self += t.w * t.w * t.d;
+                }
+            }
+            ray = 2.0 * wave_sum(pair) + wave_sum(self) / 3.0;
+        }
+        if (lane_id() == 0) {
+            if (ray_loss) ray_loss[n] = (float)ray;
+            state[2 * (size_t)n] = run_w;
+            state[2 * (size_t)n + 1] = run_m;
+        }
+    }
+    if (lane_id() == 0) part[wave] = ray;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = part[0];
+        for (int q = 1; q < kDistRays; ++q) s += part[q];
+        partials[blockIdx.x] = s;
+    }
+}
+// folds the workgroups' partials: every thread its blocks in order, a wave by a fixed butterfly, thread 0 the waves in order
+__global__ __launch_bounds__(kBlock) void k_distortion_fold(const double* __restrict__ partials, uint32_t blocks, double scale, float* __restrict__ loss) {
+    __shared__ double part[kBlock / kWave];
+    double s = 0.0;
+    for (uint32_t b = threadIdx.x; b < blocks; b += kBlock) s += partials[b];
+    s = wave_sum(s);
+    if (lane_id() == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = part[0];
+        for (int q = 1; q < kBlock / kWave; ++q) r += part[q];
+        *loss = (float)(r * scale);
+    }
+}
+__global__ __launch_bounds__(kDistBlock) void k_distortion_bwd(const float* __restrict__ weights, const float* __restrict__ z_vals,
+                                                               const float* __restrict__ nears, const float* __restrict__ fars, uint32_t N,
+                                                               uint32_t T, double scale, const double* __restrict__ state,
+                                                               const float* __restrict__ g_loss, float* __restrict__ grad_w) {
+    const uint32_t n = blockIdx.x * kDistRays + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const DistRay r = dist_ray(nears, fars, n, T);
+    float* out = grad_w + (size_t)n * T;
+    if (!r.ok) {
+        for (uint32_t i = (uint32_t)lane_id(); i < T; i += kWave) out[i] = 0.0f;
+        return;
+    }
+    const float* w = weights + (size_t)n * T;
+    const float* z = z_vals + (size_t)n * T;
+    const double k = (double)*g_loss * scale, w_tot = state[2 * (size_t)n], m_tot = state[2 * (size_t)n + 1];
+    double run_w = 0.0, run_m = 0.0;
+    for (uint32_t base = 0; base < T; base += kWave) {
+        const DistTile t = dist_tile(w, z, base, T, r, run_w, run_m);
+        const double w_gt = w_tot - t.w_le, m_gt = m_tot - t.m_le;
+        const double g = 2.0 * (t.m * (t.w_lt - w_gt) - t.m_lt + m_gt) + 2.0 / 3.0 * (t.w * t.d);
+        if (t.valid) out[base + (uint32_t)lane_id()] = (float)(k * g);
+    }
+}
 }  // namespace
 
 // criterion codes 0 .. 4; Huber (2) and SmoothL1 (3) need their positive parameter
@@ -979,6 +1124,31 @@ NVSF_API int nvsf_urf_loss_bwd(const float* weights, const float* z_vals, const 
     const auto kernel = l.rows4 ? k_urf_bwd<true, true> : (l.vec ? k_urf_bwd<true, false> : k_urf_bwd<false, false>);
     hipLaunchKernelGGL(kernel, dim3(l.blocks), dim3(kUrfBlock), 0, stream, weights, z_vals, gt_depth, N, T, eps, l.inv2s2, state, grad_loss,
                        grad_weights);
+    return nvsf_launch_status();
+}
+
+// ---- distortion loss ------------------------------------------------------------------------------------------------------------
+NVSF_API int nvsf_distortion_loss_fwd(const float* weights, const float* z_vals, const float* nears, const float* fars, uint32_t N, uint32_t T,
+                                      float alpha, void* workspace, size_t ws_bytes, float* ray_loss, float* loss, double* state,
+                                      hipStream_t stream) {
+    REQUIRE(loss && T >= 1 && (uint64_t)N * T <= (1ull << 31));
+    if (N == 0) return hipMemsetAsync(loss, 0, 4, stream) == hipSuccess ? NVSF_OK : (int)hipGetLastError();
+    const uint32_t blocks = cdiv(N, kDistRays);
+    REQUIRE(weights && z_vals && nears && fars && state && workspace && ((uintptr_t)workspace & 7u) == 0);
+    REQUIRE(ws_bytes >= (size_t)blocks * sizeof(double));
+    double* partials = static_cast<double*>(workspace);
+    hipLaunchKernelGGL(k_distortion_fwd, dim3(blocks), dim3(kDistBlock), 0, stream, weights, z_vals, nears, fars, N, T, ray_loss, state, partials);
+    hipLaunchKernelGGL(k_distortion_fold, dim3(1), dim3(kBlock), 0, stream, partials, blocks, (double)alpha / (double)N, loss);
+    return nvsf_launch_status();
+}
+
+NVSF_API int nvsf_distortion_loss_bwd(const float* weights, const float* z_vals, const float* nears, const float* fars, uint32_t N, uint32_t T,
+                                      float alpha, const double* state, const float* grad_loss, float* grad_weights, hipStream_t stream) {
+    REQUIRE(T >= 1 && (uint64_t)N * T <= (1ull << 31));
+    if (N == 0) return NVSF_OK;
+    REQUIRE(weights && z_vals && nears && fars && state && grad_loss && grad_weights);
+    hipLaunchKernelGGL(k_distortion_bwd, dim3(cdiv(N, kDistRays)), dim3(kDistBlock), 0, stream, weights, z_vals, nears, fars, N, T,
+                       (double)alpha / (double)N, state, grad_loss, grad_weights);
     return nvsf_launch_status();
 }
 

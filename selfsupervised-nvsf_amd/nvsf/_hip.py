@@ -92,6 +92,8 @@ SIGNATURES = {
     "nvsf_crit_rows": [_P, _P, _U, _U, _F, _I, _F, _P, _P],
     "nvsf_urf_loss_fwd": [_P, _P, _P, _U, _U, _F, _F, _P, ctypes.c_size_t, _P, _P],
     "nvsf_urf_loss_bwd": [_P, _P, _P, _U, _U, _F, _F, _P, _P, _P],
+    "nvsf_distortion_loss_fwd": [_P, _P, _P, _P, _U, _U, _F, _P, ctypes.c_size_t, _P, _P, _P],
+    "nvsf_distortion_loss_bwd": [_P, _P, _P, _P, _U, _U, _F, _P, _P, _P],
     "nvsf_density_dynamic_f16planes_fwd": [_P, _P, _P, _P, _P, _I, _P, _I, _U, _P, _P, _P, _P, _P],
     "nvsf_density_dynamic_lm_fwd": [_P, _P, _P, _P, _P, _I, _P, _I, _U, _P, _P, _P, _P, _P],
     "nvsf_density_dynamic_lm32_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _U, _P, _P, _P, _P, _P],

@@ -16,7 +16,9 @@ nvsf/scripts/main_nvsf.py:60-97; nothing here depends on the step object:
   * the structural regularisation on LiDAR patches in its `grad_loss` form (trainer.py:296-470: first differences (or Sobel
     gradients) of the rendered / true range inside pH x pW patches, masked by the true ray-drop channel and the flatness of the true
     frame; criteria `--depth_grad_loss` l1 / mse / huber / smoothl1 / cos, `--sobel_grad`): `LidarGradLossFn`;
-  * the error maps the patch sampler draws from (trainer.py:552-630): `update_error_map`.
+  * the error maps the patch sampler draws from (trainer.py:552-630): `update_error_map`;
+  * the distortion loss of mip-NeRF 360 on the rows of both renders (sketched and commented out at renderer_dynamic.py:242-245):
+    `DistortionLossFn` on the device, `distortion_loss` on the host.
 """
 import math
 
@@ -111,6 +113,71 @@ class UrfLossFn(torch.autograd.Function):
         _hip.call("nvsf_urf_loss_bwd", _hip.ptr(w), _hip.ptr(z), _hip.ptr(g), w.shape[0], w.shape[1], *ctx.eps, _hip.ptr(state),
                   _hip.ptr(_f32_or_none(grad)), _hip.ptr(grad_w))
         return grad_w.view(ctx.shape), None, None, None
+
+
+def distortion_ray_losses(weights, z_vals, nears, fars):
+    """The per-ray distortion loss of mip-NeRF 360 (Barron et al. 2022, eq. 15; sketched at renderer_dynamic.py:242-245) in its O(T)
+    form, in the dtype of the inputs: weights, z_vals [N, T] (z non-decreasing along a row), nears, fars [N] -> [N].  With the
+    compositor's intervals delta_i = z_{i+1} - z_i, delta_{T-1} = R / T, R = far - near:
+      m_i = (z_i + delta_i / 2 - near) / R, d_i = delta_i / R,
+      ray = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i = 2 sum_i w_i (m_i W_<i - M_<i) + 1/3 sum_i w_i^2 d_i
+    (W_<i, M_<i: exclusive prefix sums of w and w m).  A ray whose R is not finite or not > 0 gives 0 and no gradient."""
+    N, T = weights.shape
+    near, R = nears.reshape(N, 1), (fars - nears).reshape(N, 1)
+    ok = torch.isfinite(R) & (R > 0)
+    zero = torch.zeros((), dtype=weights.dtype, device=weights.device)
+    w, z, near, R = torch.where(ok, weights, zero), torch.where(ok, z_vals, zero), torch.where(ok, near, zero), torch.where(ok, R, zero + 1)
+    delta = torch.cat([z[:, 1:] - z[:, :-1], R / T], dim=1)
+    m, d = (z + delta / 2 - near) / R, delta / R
+    head = torch.zeros(N, 1, dtype=w.dtype, device=w.device)
+    w_lt = torch.cat([head, torch.cumsum(w, dim=1)[:, :-1]], dim=1)
+    m_lt = torch.cat([head, torch.cumsum(w * m, dim=1)[:, :-1]], dim=1)
+    return 2 * (w * (m * w_lt - m_lt)).sum(dim=1) + (w * w * d).sum(dim=1) / 3
+
+
+def distortion_loss(weights, z_vals, nears, fars, alpha):
+    """alpha x the mean over the N rays of `distortion_ray_losses` (a ray that gives 0 still counts in N): the host branch of
+    `RenderTrainStep.losses`, and evaluated in float64 the formulation the device kernels are tested against."""
+    N = weights.shape[0]
+    if N == 0:
+        return weights.sum() * 0
+    return alpha * distortion_ray_losses(weights, z_vals, nears, fars).sum() / N
+
+
+class DistortionLossFn(torch.autograd.Function):
+    """distortion_loss on the device (nvsf_distortion_loss_fwd / _bwd, csrc/losses.hip): weights, z_vals [N, T], nears, fars [N] (any
+    shape with N elements), alpha a Python float -> scalar, or (scalar, per-ray losses [N]) with ray_losses=True.  One scan per ray each
+    way in fp64 (one wave per ray), the row totals kept for the backward.  Gradient to `weights` only."""
+
+    @staticmethod
+    def forward(ctx, weights, z_vals, nears, fars, alpha, ray_losses=False):
+        from nvsf import _hip
+        w, z, near, far = _f32(weights), _f32(z_vals), _f32(nears).view(-1), _f32(fars).view(-1)
+        if w.dim() != 2 or z.shape != w.shape or near.numel() != w.shape[0] or far.numel() != w.shape[0]:
+            raise ValueError(f"DistortionLossFn: weights {tuple(weights.shape)}, z_vals {tuple(z_vals.shape)}, nears {tuple(nears.shape)} and "
+                             f"fars {tuple(fars.shape)} do not describe one [N, T] sample batch")
+        N, T = w.shape
+        out = torch.empty((), dtype=torch.float32, device=w.device)
+        rays = torch.empty(N, dtype=torch.float32, device=w.device) if ray_losses else None
+        state = torch.empty(N, 2, dtype=torch.float64, device=w.device)
+        ws = torch.empty(max(1, (N + 3) // 4), dtype=torch.float64, device=w.device)  # one partial per workgroup of four rays
+        _hip.call("nvsf_distortion_loss_fwd", _hip.ptr(w), _hip.ptr(z), _hip.ptr(near), _hip.ptr(far), N, T, float(alpha), _hip.ptr(ws),
+                  8 * ws.numel(), _hip.ptr(rays), _hip.ptr(out), _hip.ptr(state))
+        ctx.save_for_backward(w, z, near, far, state)
+        ctx.alpha, ctx.shape = float(alpha), weights.shape
+        if ray_losses:
+            ctx.mark_non_differentiable(rays)
+            return out, rays
+        return out
+
+    @staticmethod
+    def backward(ctx, grad, _g_rays=None):
+        from nvsf import _hip
+        w, z, near, far, state = ctx.saved_tensors
+        grad_w = torch.empty_like(w)
+        _hip.call("nvsf_distortion_loss_bwd", _hip.ptr(w), _hip.ptr(z), _hip.ptr(near), _hip.ptr(far), w.shape[0], w.shape[1], ctx.alpha,
+                  _hip.ptr(state), _hip.ptr(_f32_or_none(grad)), _hip.ptr(grad_w))
+        return grad_w.view(ctx.shape), None, None, None, None, None
 
 
 class LidarLossFn(torch.autograd.Function):

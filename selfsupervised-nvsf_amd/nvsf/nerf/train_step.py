@@ -21,9 +21,10 @@ import warnings
 import torch
 
 from nvsf import frame_shard
-from nvsf.nerf.losses import (DEFAULT_CRITERIA, CameraCritLossFn, CameraLossFn, CritSumFn, LidarCritLossFn, LidarGradLossFn, LidarLossFn,
-                              MseSumFn, UrfLossFn, lidar_losses_host, per_ray_criterion, rgb_depth_loss_host, rgb_loss_host,
+from nvsf.nerf.losses import (DEFAULT_CRITERIA, CameraCritLossFn, CameraLossFn, CritSumFn, DistortionLossFn, LidarCritLossFn, LidarGradLossFn,
+                              LidarLossFn, MseSumFn, UrfLossFn, lidar_losses_host, per_ray_criterion, rgb_depth_loss_host, rgb_loss_host,
                               update_error_map, urf_line_of_sight_loss)
+from nvsf.nerf.losses import distortion_loss as distortion_loss_host
 
 
 class RenderTrainStep:
@@ -32,7 +33,8 @@ class RenderTrainStep:
                  flow_loss=False, pc_list=None, ema_decay=0.95, split_backward=True, ray_chunks=1, grad_loss=False, depth_grad_loss="l1",
                  alpha_grad=0.1, patch_size_lidar=1, change_patch_size_lidar=(2, 8), change_patch_size_epoch=2, use_error_map=False,
                  sobel_grad=False, grad_norm_smooth=False, spatial_smooth=False, tv_loss=False, use_rgbd_loss=False, rgb_depth_loss="l1",
-                 alpha_rd=1.0, depth_loss="l1", raydrop_loss="mse", intensity_loss="mse", rgb_loss="mse", upsample_steps=0):
+                 alpha_rd=1.0, depth_loss="l1", raydrop_loss="mse", intensity_loss="mse", rgb_loss="mse", upsample_steps=0, distortion_loss=False,
+                 alpha_dist=0.01):
         """Defaults = the reference's CLI defaults (main_nvsf.py:60-97).  `scale`: the scene scale the chamfer loss divides by
         (opt.scale); `pc_list`: {frame index: [P, 3] tensor} world-frame point clouds for the scene-flow loss
         (Trainer.process_pointcloud, trainer.py:1848-1912, builds them from the range images); `ema_decay=None` disables EMA.
@@ -48,8 +50,16 @@ class RenderTrainStep:
         entries of csrc/losses.hip (and the error maps follow).
         `upsample_steps` (main_nvsf.py:73) above 0: both modalities are rendered with `hierarchical=True, upsample_steps=...`
         (NeRFRenderer.run: that many more samples per ray, drawn from the coarse weights); the line-of-sight loss then reads the
-        merged rows.  0, the default, leaves the step as it is."""
+        merged rows.  0, the default, leaves the step as it is.
+        `distortion_loss`, `alpha_dist`: the distortion loss of mip-NeRF 360 (the regulariser the reference sketched and left commented
+        out at renderer_dynamic.py:242-245: O(T^2) as written there) on the rows both renders return, [N, T] or [N, T + U]:
+        parts "dist_lidar" and "dist", alpha_dist x the mean over the rays (losses.DistortionLossFn on the device, losses.distortion_loss
+        on the host).  Off, the default, leaves the step as it is."""
         self.model = model
+        self.distortion, self.alpha_dist = bool(distortion_loss), float(alpha_dist)
+        if self.distortion and getattr(model, "cuda_ray", False):
+            raise ValueError("distortion_loss=True reads the [N, T] rows of weights and z_vals, which the occupancy-grid path (run_cuda) "
+                             "does not return: train this model with distortion_loss=False, or without its occupancy grid")
         self.upsample_steps = int(upsample_steps)
         if self.upsample_steps < 0:
             raise ValueError(f"upsample_steps is a sample count, got {upsample_steps}")
@@ -175,6 +185,14 @@ class RenderTrainStep:
             merged[key] = torch.cat([o[key] for o in outs], dim=dim)
         return merged
 
+    def _distortion(self, r, rays_o, rays_d, lidar):
+        """The distortion term on the rows of the render `r` of the rays (rays_o, rays_d) [1, N, 3]; nears and fars as `run` forms them."""
+        m = self.model
+        o, d = rays_o.contiguous().view(-1, 3).float(), rays_d.contiguous().view(-1, 3).float()
+        nears, fars = m._near_far(o, d, lidar, m.aabb_train if m.training else m.aabb_infer)
+        term = DistortionLossFn.apply if r["weights"].is_cuda else distortion_loss_host
+        return term(r["weights"], r["z_vals"], nears, fars, self.alpha_dist)
+
     def _chamfer(self, a, b):
         if self._cham is None:
             from nvsf.nerf.chamfer3D.dist_chamfer_3D import chamfer_3DDist
@@ -244,6 +262,8 @@ class RenderTrainStep:
                 eps = 0.02 * 0.1 ** min(self.global_step / self.iters, 1)
                 # device: two streaming passes forward, one backward (UrfLossFn); host-side logic tests: the torch expression
                 out["los"] = (UrfLossFn.apply if on_device else urf_line_of_sight_loss)(r["weights"], r["z_vals"], gt_d * gt_rd, eps)
+            if self.distortion:
+                out["dist_lidar"] = self._distortion(r, batch["rays_o_lidar"], batch["rays_d_lidar"], True)
         if "rays_o" in batch:
             gt_rgb = batch["gt_rgb"] if "gt_rgb" in batch else batch["images"][..., :3]
             r = self._render(batch["rays_o"], batch["rays_d"], batch["time"], perturb=True, num_steps=self.num_steps, bg_color=1,
@@ -266,6 +286,8 @@ class RenderTrainStep:
                 else:  # host-side logic tests: the same terms as torch expressions
                     out["rgb"] = rgb_loss_host(r["image"], gt_rgb, self.alpha_rgb, self.criteria["rgb_loss"], self.scale)
                     out["rgb_depth"] = rgb_depth_loss_host(r["depth"], gt_m, self.scale, self.rgb_depth_loss, self.alpha_rd)
+            if self.distortion:
+                out["dist"] = self._distortion(r, batch["rays_o"], batch["rays_d"], False)
             if self.error_maps is not None and r["image"].is_cuda:
                 self._for_error_map["camera"] = (r["image"].detach(), gt_rgb)
         total = sum(out.values())

@@ -1,4 +1,5 @@
-"""Timing of the line-of-sight loss (`use_urf_loss`, trainer.py:276-294) alone and inside the training step.
+"""Timing of the line-of-sight loss (`use_urf_loss`, trainer.py:276-294) and of the distortion loss (`distortion_loss`), alone and inside
+the training step.
 
     python tools/bench_losses.py [--reps 20] [--steps 10] [--label NAME] [--out profiles/urf_loss_bench.json]
 
@@ -13,6 +14,11 @@ Legs, in milliseconds between device events on the current stream, median and mi
                    same over 8 TB/s;
   step_urf / step  `RenderTrainStep.step` at the config-4 shape (4096 LiDAR + 4096 camera rays x 768 samples) with and without the
                    switch, interleaved.
+  dist_torch / dist_kernel / dist_kernel_queued   the same three legs for the distortion loss: `distortion_loss` as torch expressions
+                   against `DistortionLossFn` (nvsf_distortion_loss_fwd / _bwd), and the two entries called directly.  Bytes the pair
+                   must move: the same 5 x 4 N T, plus the ranges twice, the row totals (16 N) written and read and the per-ray losses.
+                   `over_los_pair`: its median over that of `los_kernel_queued` measured in the same run;
+  step_dist        the config-4 step with `distortion_loss=True`, interleaved with the two above.
 `--label` names the tree that was measured; with --out the result is merged into that file under the label, so that a run on the parent
 commit (torch form inside the step) and one on the branch sit side by side.  `decided`: whether two medians differ by more than the two
 spreads (max - min) combined.
@@ -108,6 +114,44 @@ def los_legs(dev, reps):
     return res
 
 
+def dist_legs(dev, reps, los_queued):
+    g = torch.Generator().manual_seed(1)
+    nears = (0.05 + 0.1 * torch.rand(N, generator=g)).to(dev)
+    fars = nears + 1.0
+    z = (nears.cpu()[:, None] + torch.sort(0.001 + 0.99 * torch.rand(N, T, generator=g), dim=1).values).to(dev)
+    w = (torch.rand(N, T, generator=g) / T).to(dev).requires_grad_()
+    alpha = 0.01
+
+    def run(fn):
+        def leg():
+            (grad,) = torch.autograd.grad(fn(w, z, nears, fars, alpha), w)
+            return grad
+        return leg
+    legs = {"dist_torch": run(L.distortion_loss), "dist_kernel": run(L.DistortionLossFn.apply)}
+    res = interleaved(legs, reps)
+    wd, state, loss, ray = w.detach(), torch.empty(N, 2, dtype=torch.float64, device=dev), torch.empty((), device=dev), torch.empty(N, device=dev)
+    ws, grad, one = torch.empty((N + 3) // 4, dtype=torch.float64, device=dev), torch.empty_like(wd), torch.ones((), device=dev)
+    head = (_hip.ptr(wd), _hip.ptr(z), _hip.ptr(nears), _hip.ptr(fars), N, T, alpha)
+
+    def queue():
+        for _ in range(QUEUE):
+            _hip.call("nvsf_distortion_loss_fwd", *head, _hip.ptr(ws), 8 * ws.numel(), _hip.ptr(ray), _hip.ptr(loss), _hip.ptr(state))
+            _hip.call("nvsf_distortion_loss_bwd", *head, _hip.ptr(state), _hip.ptr(one), _hip.ptr(grad))
+    res["dist_kernel_queued"] = {k: v / QUEUE for k, v in interleaved({"q": queue}, reps)["q"].items()}
+    moved = 5 * 4 * N * T + 2 * 2 * 4 * N + 2 * 16 * N + 4 * N
+    sec = res["dist_kernel_queued"]["median"] * 1e-3
+    res["dist_kernel_queued"].update(pairs_per_timing=QUEUE, bytes_moved=moved, bandwidth_gb_s=moved / sec / 1e9,
+                                     fraction_of_hbm_peak=moved / sec / HBM_PEAK)
+    if los_queued is not None:
+        res["dist_kernel_queued"]["over_los_pair"] = res["dist_kernel_queued"]["median"] / los_queued["median"]
+    res["torch_over_kernel"] = res["dist_torch"]["median"] / res["dist_kernel"]["median"]
+    res["decided"] = decided(res["dist_torch"], res["dist_kernel"])
+    a, b = legs["dist_kernel"]().double(), legs["dist_torch"]().double()
+    res["kernel_vs_torch_max_abs_grad_diff"] = float((a - b).abs().max())
+    res["kernel_minus_torch_loss"] = float(L.DistortionLossFn.apply(w, z, nears, fars, alpha)) - float(L.distortion_loss(w, z, nears, fars, alpha))
+    return res
+
+
 def step_legs(dev, reps):
     rng = np.random.default_rng(0)
     lo, ld = S.lidar_rays(N, rng)
@@ -118,11 +162,11 @@ def step_legs(dev, reps):
              "gt_depth": torch.rand(1, N, generator=g).to(dev) * 0.5, "gt_raydrop": (torch.rand(1, N, generator=g) > 0.3).float().to(dev),
              "gt_intensity": torch.rand(1, N, generator=g).to(dev), "gt_rgb": torch.rand(1, N, 3, generator=g).to(dev)}
     legs = {}
-    for name, urf in (("step_urf", True), ("step", False)):
+    for name, urf, dist in (("step_urf", True, False), ("step_dist", False, True), ("step", False, False)):
         torch.manual_seed(0)
         m = NeRFNetworkStatic(bound=S.BOUND, min_near=S.MIN_NEAR, min_near_lidar=S.MIN_NEAR, lidar_max_depth=S.LIDAR_MAX_DEPTH,
                               num_frames=S.NUM_FRAMES).to(dev)
-        step = RenderTrainStep(m, num_steps=T, scale=S.SCALE, use_urf_loss=urf)
+        step = RenderTrainStep(m, num_steps=T, scale=S.SCALE, use_urf_loss=urf, **({"distortion_loss": True} if dist else {}))
 
         def leg(step=step):
             step.step(batch)
@@ -131,6 +175,8 @@ def step_legs(dev, reps):
     res = interleaved(legs, reps, warmup=2)
     res["urf_costs_ms"] = res["step_urf"]["median"] - res["step"]["median"]
     res["decided"] = decided(res["step_urf"], res["step"])
+    res["dist_costs_ms"] = res["step_dist"]["median"] - res["step"]["median"]
+    res["dist_decided"] = decided(res["step_dist"], res["step"])
     return res
 
 
@@ -143,7 +189,9 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     res = {"unit": "ms (device events)", "shape": [N, T], "reps": args.reps, "steps": args.steps, "device": torch.cuda.get_device_name(0),
-           "build_digest": _hip.build_digest(), "los": los_legs(dev, args.reps), "train_step": step_legs(dev, args.steps)}
+           "build_digest": _hip.build_digest(), "los": los_legs(dev, args.reps)}
+    res["dist"] = dist_legs(dev, args.reps, res["los"].get("los_kernel_queued"))
+    res["train_step"] = step_legs(dev, args.steps)
     print(json.dumps({args.label: res}))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -108,6 +108,9 @@ def main():
                         help=f"criterion of the {option} term (RenderTrainStep({option}_loss=...))")
     ap.add_argument("--urf-loss", action="store_true", help="line-of-sight loss of Urban Radiance Fields on the LiDAR samples "
                     "(RenderTrainStep(use_urf_loss=True): one HIP pass each way)")
+    ap.add_argument("--distortion-loss", action="store_true", help="distortion loss of mip-NeRF 360 on the samples of both renders "
+                    "(RenderTrainStep(distortion_loss=True): parts dist_lidar and dist, one HIP scan per ray each way)")
+    ap.add_argument("--alpha-dist", type=float, default=0.01, metavar="X", help="weight of the distortion loss")
     ap.add_argument("--annotations", default=None, metavar="PATH", help="JSON sidecar of the moving objects' 3-D boxes per frame id (world frame, "
                     "metres); --eval-table then also prints the static / dynamic tables (nvsf/nerf/object_masks.py)")
     ap.add_argument("--refine", action="store_true", help="fit the ray-drop refinement U-Net after training and evaluate with it as well "
@@ -182,7 +185,8 @@ def main():
                               use_error_map=not args.plain, change_patch_size_lidar=(1,) if args.plain else (2, 8),
                               flow_loss=args.flow_loss, pc_list=pc_list, use_rgbd_loss=args.rgbd_loss, use_urf_loss=args.urf_loss,
                               depth_loss=args.depth_loss, raydrop_loss=args.raydrop_loss, intensity_loss=args.intensity_loss,
-                              rgb_loss=args.rgb_loss, upsample_steps=args.upsample_steps)
+                              rgb_loss=args.rgb_loss, upsample_steps=args.upsample_steps, distortion_loss=args.distortion_loss,
+                              alpha_dist=args.alpha_dist)
     resample_kw = {"hierarchical": True, "upsample_steps": args.upsample_steps} if args.upsample_steps > 0 else {}
     if not args.plain:
         trainer.attach_error_maps(data)
