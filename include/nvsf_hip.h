@@ -237,6 +237,20 @@ int nvsf_hashgrid_bwd_binned(const float* x, uint32_t M, uint32_t x_stride, cons
                              float* grad_table_f32, uint32_t merge_from, uint32_t fine_from, void* workspace,
                              size_t workspace_bytes, nvsf_stream_t stream);
 
+/* gradient wrt the coordinates (what tcnn.Encoding returns for its input; the reference never asks for it: network_dynamic.py:245-265
+ * wraps its look-ups in no_grad).  The function differentiated is the piecewise-multilinear function nvsf_hashgrid_fwd evaluates, on the
+ * kernel's own cell: pos_d = fmaf(scale_l, x_d, 0.5f), cell_d = floorf(pos_d), frac_d = pos_d - cell_d, w_d(0) = 1 - frac_d, w_d(1) = frac_d,
+ *   grad_x[m][d] = sum_l scale_l sum_f grad_out[m, l, f] sum_{c in {0,1}^D} s_d(c) prod_{e != d} w_e(c_e) table[row(l, cell + c)][f],
+ *   s_d(c) = +1 if c_d = 1 else -1.
+ * Rows are addressed exactly as the forward addresses them (any x the forward accepts stays inside the table); table = the fp16 copy
+ * the forward reads.  x, cols, D, F, L as nvsf_hashgrid_fwd; grad_out fp16 (grad_is_f16 != 0) or fp32, rows [M, go_stride >= L F]
+ * (go_level_stride = 0) or level-major [L][M][F] (go_level_stride = elements between two levels, go_stride >= F: the column-block
+ * layout of nvsf_mlp_bwd); grad_x fp32 [M, gx_stride >= D], overwritten.  No atomics: the result is deterministic. */
+int nvsf_hashgrid_grad_x(const float* x, uint32_t M, uint32_t x_stride, const uint32_t* cols, uint32_t D, const void* table_f16,
+                         uint32_t L, uint32_t F, const float* h_scales, const uint32_t* h_res, const uint32_t* h_offsets,
+                         const void* grad_out, int grad_is_f16, uint32_t go_stride, uint32_t go_level_stride, float* grad_x,
+                         uint32_t gx_stride, nvsf_stream_t stream);
+
 /* ref: tcnn.Encoding("Frequency") network_dynamic.py:108-114.  x fp32 [M,n_dims] ->
  * out fp16 [M, out_stride >= 2*n_dims*n_freq], out[i*2K+2k] = sin(2^k pi x_i), [..+1] = cos. */
 int nvsf_freq_encode(const float* x, uint32_t M, uint32_t n_dims, uint32_t n_freq, void* out_f16,

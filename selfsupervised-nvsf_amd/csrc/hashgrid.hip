@@ -127,6 +127,102 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     }
 }
 
+// The F gradient elements of one (sample, level): one 8 / 16-byte load (two for 32 bytes) where the host found the matrix aligned for it
+// (`vec`, uniform), element loads otherwise -- the same values either way.
+template <int F, bool GRAD_F16>
+__device__ __forceinline__ void load_grad_row(const void* __restrict__ grad_out, size_t at, bool vec, float (&g)[F]) {
+    if (vec) {
+        if constexpr (GRAD_F16) {
+            load_feat<F>(reinterpret_cast<const _Float16*>(grad_out) + at, 0, g);
+        } else {
+            constexpr int V = F < 4 ? F : 4;
+            typedef float fv_t __attribute__((ext_vector_type(V)));
+#pragma unroll
+            for (int f = 0; f < F; f += V) {
+                const fv_t t = *reinterpret_cast<const fv_t*>(reinterpret_cast<const float*>(grad_out) + at + f);
+#pragma unroll
+                for (int j = 0; j < V; ++j) g[f + j] = t[j];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int f = 0; f < F; ++f) g[f] = load_grad<GRAD_F16>(grad_out, at + f);
+    }
+}
+
+// Coordinate gradient: dL/dx of the piecewise-multilinear function encode_level evaluates, on the kernel's own cell.
+// The forward's mapping: 64 consecutive samples per workgroup, lanes = samples, the four waves split the levels, all 2^D gathers of
+// a level in flight before the blend; every wave keeps [D] partial sums over its levels, the four are added through LDS in wave
+// order.  No atomics: reruns are bit-identical.  Per level and axis d the 2^(D-1) corner pairs along d are DIFFERENCED first
+// (t[c | d] - t[c], t[c] = sum_f g[f] table[row(c)][f]) and then blended with the other axes' weights: a feature that does not
+// change along d contributes an exact zero.
+template <int D, int F, bool GRAD_F16>
+__global__ __launch_bounds__(kBlock) void k_hashgrid_grad_x(const float* __restrict__ x, uint32_t M, uint32_t x_stride, uint32_t c0, uint32_t c1,
+                                                            uint32_t c2, const _Float16* __restrict__ table, uint32_t L, GridMeta meta,
+                                                            const void* __restrict__ grad_out, uint32_t go_stride, uint32_t go_level, uint32_t vec,
+                                                            float* __restrict__ grad_x, uint32_t gx_stride) {
+    __shared__ float part[kBlock / kWave][D][kWave];  // [wave][axis][lane]: a wave instruction writes / reads 64 consecutive floats
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t m = blockIdx.x * kSamplesPerBlock + lane;
+    const uint32_t mm = m < M ? m : M - 1;  // clamp: out-of-range lanes compute a valid sample and are dropped at the store
+    float xs[D];
+    {
+        const float* px = x + (size_t)mm * x_stride;
+        xs[0] = px[c0];
+        xs[1] = px[c1];
+        if constexpr (D == 3) xs[2] = px[c2];
+    }
+    float sum[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) sum[d] = 0.0f;
+    for (uint32_t l = wave; l < L; l += 4) {
+        float g[F];
+        load_grad_row<F, GRAD_F16>(grad_out, (size_t)mm * go_stride + (size_t)l * go_level, vec != 0u, g);
+        const float scale = meta.scale[l];
+        const uint32_t res = meta.res[l], row0 = meta.offset[l], hsize = meta.offset[l + 1] - row0;
+        float frac[D];
+        uint32_t cell[D];
+        grid_cell<D>(xs, scale, cell, frac);
+        float v[1 << D][F];
+#pragma unroll
+        for (int c = 0; c < (1 << D); ++c) {
+            uint32_t cc[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) cc[d] = cell[d] + ((c >> d) & 1u);
+            load_feat<F>(table, (size_t)row0 + grid_row<D>(cc, res, hsize), v[c]);
+        }
+        float t[1 << D];
+#pragma unroll
+        for (int c = 0; c < (1 << D); ++c) {
+            t[c] = 0.0f;
+#pragma unroll
+            for (int f = 0; f < F; ++f) t[c] = fmaf(g[f], v[c][f], t[c]);
+        }
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            float acc = 0.0f;
+#pragma unroll
+            for (int c = 0; c < (1 << D); ++c) {
+                if (c & (1 << d)) continue;
+                float w = 1.0f;
+#pragma unroll
+                for (int e = 0; e < D; ++e)
+                    if (e != d) w = w * ((c & (1 << e)) ? frac[e] : (1.0f - frac[e]));
+                acc = fmaf(w, t[c | (1 << d)] - t[c], acc);
+            }
+            sum[d] = fmaf(scale, acc, sum[d]);
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < D; ++d) part[wave][d][lane] = sum[d];
+    __syncthreads();
+    if (wave == 0 && m < M) {
+#pragma unroll
+        for (int d = 0; d < D; ++d)
+            grad_x[(size_t)m * gx_stride + d] = ((part[0][d][lane] + part[1][d][lane]) + part[2][d][lane]) + part[3][d][lane];
+    }
+}
+
 // Table gradient: one thread per (sample, level); fp32 atomics into grad_table.
 template <int D, int F, bool GRAD_F16>
 __global__ __launch_bounds__(kBlock) void k_hashgrid_bwd(const float* __restrict__ x, uint32_t M, uint32_t x_stride, uint32_t c0,
@@ -670,6 +766,32 @@ NVSF_API int nvsf_hashgrid_fwd_level_major(const float* x, uint32_t M, uint32_t 
     if (st != NVSF_OK) return st;
     if (!levels8_grid(L, F, h_res, h_offsets)) return NVSF_ERR_UNSUPPORTED;
     return launch_levels8(x, M, x_stride, table_f16, h_offsets[L], meta, out_f16, 0u, 1u, stream);
+}
+
+NVSF_API int nvsf_hashgrid_grad_x(const float* x, uint32_t M, uint32_t x_stride, const uint32_t* cols, uint32_t D, const void* table_f16,
+                                  uint32_t L, uint32_t F, const float* h_scales, const uint32_t* h_res, const uint32_t* h_offsets,
+                                  const void* grad_out, int grad_is_f16, uint32_t go_stride, uint32_t go_level_stride, float* grad_x,
+                                  uint32_t gx_stride, hipStream_t stream) {
+    if (M == 0) return NVSF_OK;
+    REQUIRE(x && cols && table_f16 && grad_out && grad_x && (D == 2 || D == 3) && gx_stride >= D);
+    REQUIRE((reinterpret_cast<uintptr_t>(table_f16) & 15u) == 0 && (reinterpret_cast<uintptr_t>(grad_x) & 3u) == 0);
+    // rows [M, go_stride >= L F] (go_level_stride = 0), or level-major [L][M][F]: go_level_stride elements between levels, go_stride >= F
+    REQUIRE(go_level_stride ? (go_stride >= F && (unsigned long long)go_level_stride >= (unsigned long long)M * go_stride) : go_stride >= L * F);
+    for (uint32_t d = 0; d < D; ++d) REQUIRE(cols[d] < x_stride);
+    GridMeta meta;
+    const int st = fill_meta(meta, L, h_scales, h_res, h_offsets);
+    if (st != NVSF_OK) return st;
+    const uint32_t go_level = go_level_stride ? go_level_stride : F;
+    const uint32_t c0 = cols[0], c1 = cols[1], c2 = D == 3 ? cols[2] : 0;
+    // whole-level loads of the gradient where every (sample, level) piece is aligned for them
+    const size_t elem = grad_is_f16 ? 2u : 4u, piece = F * elem < 16u ? F * elem : 16u;
+    const uint32_t vec = (reinterpret_cast<uintptr_t>(grad_out) % piece == 0 && (go_stride * elem) % piece == 0 && (go_level * elem) % piece == 0) ? 1u : 0u;
+    return dispatch_dfg(D, F, grad_is_f16, [&](auto d, auto f, auto g16) {
+        hipLaunchKernelGGL((k_hashgrid_grad_x<decltype(d)::value, decltype(f)::value, decltype(g16)::value>), dim3(cdiv(M, kSamplesPerBlock)),
+                           dim3(kBlock), 0, stream, x, M, x_stride, c0, c1, c2, reinterpret_cast<const _Float16*>(table_f16), L, meta, grad_out,
+                           go_stride, go_level, vec, grad_x, gx_stride);
+        return nvsf_launch_status();
+    });
 }
 
 namespace {

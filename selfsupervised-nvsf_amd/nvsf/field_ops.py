@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from nvsf import _hip
 from nvsf import testing as _testing
@@ -206,32 +207,79 @@ def hashgrid_backward(x, cols, spec, grad_out, grad_table=None, fine_from=None, 
     return grad_table
 
 
+def hashgrid_grad_x(x, cols, table_f16, spec, grad_out, out=None):
+    """d L / d x of the encoded columns: x fp32 [M, x_stride], grad_out [M, L*F] (row-strided views are read in place) or level-major
+    [L, M, F] (mlp_backward(grad_x_blocks=F)), fp16 or fp32 -> fp32 [M, D] (nvsf_hashgrid_grad_x: the derivative of the multilinear
+    blend on the forward's own cell; deterministic).  `out`: optional fp32 destination [M, >= D] with unit column stride (any view)."""
+    x = x.contiguous()
+    M = x.shape[0]
+    if grad_out.dtype not in (torch.float16, torch.float32):
+        grad_out = grad_out.float()
+    level_major = grad_out.dim() == 3
+    if level_major:
+        grad_out = grad_out.contiguous()
+        if tuple(grad_out.shape) != (spec.L, M, spec.F):
+            raise ValueError(f"hashgrid_grad_x: a level-major gradient is [L, M, F] = {(spec.L, M, spec.F)}, got {tuple(grad_out.shape)}")
+        go_ptr, go_stride, go_level = _hip.ptr(grad_out), spec.F, M * spec.F
+    else:
+        if grad_out.dim() != 2 or (grad_out.shape[1] > 1 and grad_out.stride(1) != 1) or grad_out.stride(0) < grad_out.shape[1]:
+            grad_out = grad_out.contiguous()
+        if grad_out.shape[0] != M or grad_out.shape[1] < spec.n_output_dims:
+            raise ValueError(f"hashgrid_grad_x: grad_out must be [M, >= L F] = [{M}, >= {spec.n_output_dims}], got {tuple(grad_out.shape)}")
+        go_ptr, go_stride, go_level = _hip.ptr_rows(grad_out), grad_out.stride(0) if M > 1 else max(grad_out.stride(0), grad_out.shape[1]), 0
+    if out is None:
+        out = torch.empty(M, spec.D, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != M or out.shape[1] < spec.D:
+        raise ValueError("hashgrid_grad_x: `out` must be fp32 [M, >= D]")
+    gx_stride = out.stride(0) if M > 1 else max(out.stride(0), spec.D)
+    _hip.call("nvsf_hashgrid_grad_x", _hip.ptr(x), M, x.shape[1], _hip.host_u32(cols), spec.D, _hip.ptr(table_f16), spec.L, spec.F,
+              spec.h_scales, spec.h_res, spec.h_offsets, go_ptr, 1 if grad_out.dtype == torch.float16 else 0, go_stride, go_level,
+              _hip.ptr_rows(out), gx_stride)
+    return out
+
+
 class HashGridFn(Function):
-    """fp16 features = encode(x; table).  Gradient flows to the (fp32 master) table only."""
+    """fp16 features = encode(x; table).  Gradient flows to the (fp32 master) table and, where the caller asks for it
+    (x.requires_grad), to the coordinates (hashgrid_grad_x; first order only: the returned gradient carries no graph)."""
 
     @staticmethod
     def forward(ctx, x, params, table_f16, spec, cols, rows_per_ray=None, train_ctx=None, level_major=False):
+        ctx.x_dtype = x.dtype
         x = x.float().contiguous()
         # level_major: fp16 [L, M, F] instead of rows [M, L F] (hashgrid_forward_level_major; the caller has checked level_major_eligible):
         # the gradient then comes back in the same layout, which is the one the binned scatter reads level by level
         out = hashgrid_forward_level_major(x, table_f16, spec) if level_major else hashgrid_forward(x, cols, table_f16, spec)
-        ctx.save_for_backward(x)
+        if ctx.needs_input_grad[0]:  # the coordinate gradient reads the table the forward read
+            ctx.save_for_backward(x, table_f16)
+        else:
+            ctx.save_for_backward(x)
         ctx.spec, ctx.cols, ctx.rows_per_ray = spec, cols, rows_per_ray
         announce(ctx, train_ctx, params)
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_out):
-        (x,) = ctx.saved_tensors
+        x = ctx.saved_tensors[0]
+        grad_x = None
+        if ctx.needs_input_grad[0]:
+            spec, cols = ctx.spec, tuple(int(c) for c in ctx.cols)
+            if cols == tuple(range(x.shape[1])):
+                grad_x = hashgrid_grad_x(x, cols, ctx.saved_tensors[1], spec, grad_out)
+            else:  # columns of a wider coordinate matrix: the others receive no gradient
+                grad_x = torch.zeros_like(x)
+                grad_x[:, list(cols)] = hashgrid_grad_x(x, cols, ctx.saved_tensors[1], spec, grad_out)
+            if grad_x.dtype != ctx.x_dtype:
+                grad_x = grad_x.to(ctx.x_dtype)
         if not ctx.needs_input_grad[1]:
-            return None, None, None, None, None, None, None, None
+            return grad_x, None, None, None, None, None, None, None
         fine = _bin_from(ctx.spec, x.shape[0], ctx.rows_per_ray)
         if grad_out.dim() == 3 and (fine is None or _hip.hashgrid_bwd_ws_bytes(x.shape[0], ctx.spec, fine[0], fine[1]) <= 0 or x.shape[0] > _BIN_ROWS_MAX):
             grad_out = grad_out.permute(1, 0, 2).reshape(x.shape[0], -1)  # only the binned entry point reads level-major gradients
         done = scatter_to_sink(ctx, (x, grad_out), lambda views, pool: hashgrid_backward(
             x, ctx.cols, ctx.spec, grad_out, grad_table=views[0].view(-1), fine_from=fine, ws_pool=pool))
         grad_params = None if done else hashgrid_backward(x, ctx.cols, ctx.spec, grad_out, fine_from=fine)
-        return None, grad_params, None, None, None, None, None, None
+        return grad_x, grad_params, None, None, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------

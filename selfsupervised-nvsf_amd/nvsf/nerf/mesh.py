@@ -232,12 +232,23 @@ def extract_geometry(bound_min, bound_max, xyz_res, threshold, query_func, smoot
     return vertices, t.cpu().numpy(), (pnts.cpu().numpy() if pnts is not None else None)
 
 
-def write_ply(path, vertices, triangles):
-    """Binary little-endian PLY: `double x y z` per vertex, `list uchar int vertex_indices` per face."""
+def write_ply(path, vertices, triangles, normals=None):
+    """Binary little-endian PLY: `double x y z` per vertex, `list uchar int vertex_indices` per face.  `normals` [V, 3]: every vertex
+    record gains `float nx ny nz` (36 bytes per vertex instead of 24); None: the file is byte for byte what it was without the argument."""
     v = np.ascontiguousarray(vertices, dtype="<f8").reshape(-1, 3)
     t = np.ascontiguousarray(triangles, dtype="<i4").reshape(-1, 3)
+    normal_props = ""
+    if normals is not None:
+        n = np.ascontiguousarray(normals, dtype="<f4").reshape(-1, 3)
+        if n.shape[0] != v.shape[0]:
+            raise ValueError(f"write_ply: {n.shape[0]} normals for {v.shape[0]} vertices")
+        normal_props = "property float nx\nproperty float ny\nproperty float nz\n"
+        records = np.empty(v.shape[0], dtype=[("p", "<f8", (3,)), ("n", "<f4", (3,))])
+        records["p"] = v
+        records["n"] = n
+        v = records
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {v.shape[0]}\nproperty double x\nproperty double y\nproperty double z\n"
+              f"element vertex {v.shape[0]}\nproperty double x\nproperty double y\nproperty double z\n{normal_props}"
               f"element face {t.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
     faces = np.empty(t.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
     faces["n"] = 3
@@ -248,19 +259,26 @@ def write_ply(path, vertices, triangles):
         f.write(faces.tobytes())
 
 
+_NORMAL_CHUNK = 1 << 18  # vertices per density_gradient call of export_mesh_density(normals=True)
+
+
 def _is_space_time(model):
     from nvsf.nerf.models.network_static import NeRFNetworkStatic
     return not isinstance(model, NeRFNetworkStatic)
 
 
 def export_mesh_density(model, save_path, bound_min=None, bound_max=None, xyz_res=(256, 256, 256), threshold=10, smoothing=False,
-                        time=None, cal_lidar_color=False):
+                        time=None, cal_lidar_color=False, normals=False):
     """Trainer.export_mesh_density (utils.py:559-608) as a function of the model: samples the raw density
     `model.density(pts, t, cal_lidar_color)["sigma"]` (no density_scale) under no_grad in evaluation mode -- the regime of eval_step --
     on the grid of extract_fields, runs marching cubes at `threshold` on the device and writes a binary PLY to `save_path`.
     Bounds default to model.aabb_infer and must lie inside it (the reference asserts [-1, 1] instead, which its own defaults fail at
     bound = 2).  `time` (float or tensor) is required for the space-time NeRFNetwork -- the reference calls density without one, which
-    that model cannot evaluate -- and ignored by the static network.  Returns (vertices, triangles) as written."""
+    that model cannot evaluate -- and ignored by the static network.  Returns (vertices, triangles) as written.
+    `normals` (static model only): the unit normals -grad sigma / |grad sigma| of the field at the vertices (nvsf.nerf.normals.density_gradient,
+    evaluated in chunks) are written with them and returned: (vertices, triangles, normals [V, 3] fp32)."""
+    if normals and _is_space_time(model):
+        raise NotImplementedError("export_mesh_density(normals=True): only the static hash field has a coordinate gradient")
     if smoothing:
         raise NotImplementedError("smoothing: mcubes.smooth (the reference's optional Laplacian-like smoothing of the field) is out of scope")
     res = _check_res(xyz_res)
@@ -294,6 +312,14 @@ def export_mesh_density(model, save_path, bound_min=None, bound_max=None, xyz_re
         model.train(was_training)
     d = os.path.dirname(os.path.abspath(save_path))
     os.makedirs(d, exist_ok=True)
-    write_ply(save_path, vertices, triangles)
-    return vertices, triangles
+    if not normals:
+        write_ply(save_path, vertices, triangles)
+        return vertices, triangles
+    from nvsf.nerf.normals import density_gradient
+    vertex_normals = np.empty((vertices.shape[0], 3), np.float32)
+    for i in range(0, vertices.shape[0], _NORMAL_CHUNK):
+        pts = torch.from_numpy(vertices[i:i + _NORMAL_CHUNK].astype(np.float32)).to(dev)
+        vertex_normals[i:i + _NORMAL_CHUNK] = density_gradient(model, pts, cal_lidar_color)["normal"].cpu().numpy()
+    write_ply(save_path, vertices, triangles, vertex_normals)
+    return vertices, triangles, vertex_normals
 

@@ -57,8 +57,9 @@ class NeRFNetworkStatic(NeRFRenderer):
         x = (x + self.bound) / (2 * self.bound)
         enc = self.hash_encoder_lidar if cal_lidar_color else self.hash_encoder_camera
         net = self.sigma_net
+        want_dx = x.requires_grad and torch.is_grad_enabled()  # d sigma / d x: the operator chain below carries it (ops.HashGridFn), DensityFn does not
         if (x.is_cuda and x.dim() == 2 and enc.spec.D == 3 and net.spec.n_hidden <= 2 and net.spec.hidden == 64
-                and net.spec.out_cols == 16 and testing.get("density_fn") == "fused"):
+                and net.spec.out_cols == 16 and testing.get("density_fn") == "fused" and not want_dx):
             # one autograd node for encode -> MLP -> trunc_exp / slice (ops.DensityFn): same forward kernels, leaner backward
             sigma, geo = ops.DensityFn.apply(x, enc.params, enc.table_f16(), enc.spec, net.params, net.weights_f16(), net.spec,
                                              activation._LO, activation._HI, ops.rows_hint(self), ops.train_context(self))
