@@ -40,6 +40,7 @@ enum NvsfVariantKey : int {
     kVarMlpBwd,         // nvsf_mlp_bwd: 0 by shape (wave-independent kernel, transposes on the matrix core; LDS-staged kernel for 32-64-16), 1 staged, 2 wave
     kVarLevelKinds,     // gathering render kernels on the config-2 grid: 0 the instance with the level kinds compiled in, 1 the general one
     kVarCornerShare,    // one-launch gathering render: 0 coarse level groups share a tile's corner gathers where the ray's step allows, 1 never (every lane gathers its own eight), 2 both groups try on every ray
+    kVarWavePriority,   // one-launch LiDAR render: 0 the issue priority goes round the four waves of a SIMD, 1 every wave at the default priority
     kVarCount
 };
 int nvsf_variant(int key);

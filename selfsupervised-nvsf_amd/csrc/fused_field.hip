@@ -1590,6 +1590,24 @@ struct RenderTrainOut {
     float* rgb;      // [M, C]
 };
 
+// Rotating issue priority of the one-launch LiDAR render (k_render_uniform<true, false, false, *>, the evaluation instance, the one it
+// was measured on; NOTES.md Round 10).  The four waves of a SIMD are four rays that start together, and the SIMD's arbiter favours its
+// oldest wave: they finish at 0.55 / 0.66 / 0.81 / 0.95 of the launch and the last one runs alone.  Every kPrioTiles tiles a wave takes
+// user priority ((tile / kPrioTiles) + its slot on the SIMD) mod 4, so that the top priority goes round the four waves and they
+// advance together.  The slot is HW_ID.WAVE_ID mod 4 (bits 3:0 of hardware register 4): on the 4096-ray launch, which fills every SIMD
+// once, the ids seen were 0 .. 3, one each; where freed slots are refilled two resident waves can share a phase, which costs balance,
+// not correctness.  Steers speed only: no value depends on it.  Bit 1 of the kernel's `use_bg` argument (kRenderNoPriority; tests:
+// nvsf_test_variant("wave_priority", 1)) leaves every wave at the default priority.
+constexpr int kRenderNoPriority = 2;
+constexpr uint32_t kPrioTilesLog2 = 3;
+__device__ __forceinline__ uint32_t simd_wave_slot() { return __builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & 3u; }
+__device__ __forceinline__ void set_wave_priority(uint32_t p) {  // s_setprio takes an immediate; p is wave-uniform
+    if (p == 0u) __builtin_amdgcn_s_setprio(0);
+    else if (p == 1u) __builtin_amdgcn_s_setprio(1);
+    else if (p == 2u) __builtin_amdgcn_s_setprio(2);
+    else __builtin_amdgcn_s_setprio(3);
+}
+
 template <bool LIDAR, bool FROM_FEATURES, bool TRAIN = false, int FH = -1>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_render_uniform(
     RayBatch rb, const _Float16* __restrict__ table, uint32_t table_bytes, GridMeta meta, uint32_t first_hashed,
@@ -1660,7 +1678,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         }
     };
     if constexpr (!FROM_FEATURES) request(0u);
+    constexpr bool PRIO = LIDAR && !FROM_FEATURES && !TRAIN;
+    const bool rotate = PRIO && (use_bg & kRenderNoPriority) == 0;
+    const uint32_t prio_slot = PRIO ? simd_wave_slot() : 0u;
     for (uint32_t i0 = 0; i0 < T; i0 += 16) {
+        if constexpr (PRIO) {
+            if (rotate && (i0 & ((16u << kPrioTilesLog2) - 1u)) == 0u) set_wave_priority(((i0 >> (4 + kPrioTilesLog2)) + prio_slot) & 3u);
+        }
         const uint32_t i = i0 + (uint32_t)c;
         const bool valid = i < T;
         const uint32_t ic = valid ? i : T - 1u;
@@ -1742,7 +1766,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             }
         }
     }
-    store_ray<C>(lane, ws, dp, img, bg0, bg1, bg2, use_bg, weights_sum + n, depth + n, image + (size_t)n * C);
+    store_ray<C>(lane, ws, dp, img, bg0, bg1, bg2, PRIO ? (use_bg & 1) : use_bg, weights_sum + n, depth + n, image + (size_t)n * C);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2202,6 +2226,7 @@ static int render_uniform_impl(const float* rays_o, const float* rays_d, const f
     // corner_share (tests): 1 never shares (the per-lane form on every tile), 2 tries both coarse groups on every ray
     const int cs = nvsf_variant(kVarCornerShare);
     const float share_thresh = cs == 1 ? -1.0f : cs == 2 ? INFINITY : kShareLambdaMax;
+    const int no_prio = nvsf_variant(kVarWavePriority) == 1 ? kRenderNoPriority : 0;  // wave_priority (tests): 1 no rotating priority in the LiDAR launch
 #define LAUNCH_RU_FH(LD, FF, FH)                                                                                                      \
     do {                                                                                                                              \
         if (train)                                                                                                                    \
@@ -2210,7 +2235,7 @@ static int render_uniform_impl(const float* rays_o, const float* rays_d, const f
                                weights, weights_sum, depth, image, share_thresh, rt);                                                               \
         else                                                                                                                          \
             hipLaunchKernelGGL((k_render_uniform<LD, FF, false, FH>), grid_dim, block, 0, stream, rb, w.table, (uint32_t)gi.table_bytes, gi.meta, \
-                               gi.first_hashed, fp, w.sigma, w.head_a, w.head_b, k_scale, w_thresh, w.bg[0], w.bg[1], w.bg[2], use_bg, z_vals,    \
+                               gi.first_hashed, fp, w.sigma, w.head_a, w.head_b, k_scale, w_thresh, w.bg[0], w.bg[1], w.bg[2], (LD && !FF) ? use_bg | no_prio : use_bg, z_vals, \
                                weights, weights_sum, depth, image, share_thresh, rt);                                                               \
     } while (0)
     // the gathering form has an instance for the grid of BASELINE config 2 (levels 0-4 dense, 5-15 hashed) beside the general one

@@ -25,6 +25,7 @@ _NATIVE = {
     "mlp_bwd": {"auto": 0, "staged": 1, "wave": 2},
     "level_kinds": {"compiled": 0, "runtime": 1},
     "corner_share": {"gated": 0, "never": 1, "always": 2},
+    "wave_priority": {"rotate": 0, "off": 1},
     "march_skew": {"off": 0, **{f"queue{q}": q + 1 for q in range(8)}},
 }
 # operator-side choices (Python): name -> allowed values, the first one is the production form
