@@ -824,46 +824,55 @@ class DensityFn(Function):
 
     @staticmethod
     def backward(ctx, g_sigma, g_geo):
-        return (None,) + _density_backward(ctx, g_sigma, g_geo) + (None, None)
+        grad_table, grad_w = static_density_backward(ctx, *ctx.saved_tensors, ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray,
+                                                     ctx.need_table, ctx.need_w, g_sigma, g_geo)
+        return None, grad_table, None, None, grad_w, None, None, None, None, None, None
 
 
-def _density_backward(ctx, g_sigma, g_geo):
-    """Backward shared by DensityFn and DensityRaysFn: -> (grad_table, None, None, grad_mlp_weights, None, None, None, None)."""
-    x01, feat, sigma, mlp_w16 = ctx.saved_tensors
-    spec, M = ctx.mlp_spec, x01.shape[0]
+def density_mlp_backward(x_rows, w16, spec, sigma, g_sigma, g_geo, g_geo_b, clamp, need_grad_x, grad_x_blocks=0):
+    """Backward of (sigma, geo_feat) = (trunc_exp(h[:, 0]), h[:, 1:]), h = density MLP(x_rows), for every density node (the static field's
+    and network_dynamic.DensityTailFn): -> (dL/dx_rows | None, dL/dW).  `g_geo_b`: a second geometry gradient to be summed with `g_geo`
+    (the second LiDAR head's); `clamp`: trunc_exp's (lo, hi); `grad_x_blocks`: as in mlp_backward."""
+    M = x_rows.shape[0]
     if g_sigma is not None:
         g_sigma = g_sigma.float().contiguous()
     if g_geo is not None and (g_geo.dtype != torch.float32 or g_geo.stride(1) != 1):
         g_geo = g_geo.float().contiguous()
     # the logit gradient [g_sigma clamp(sigma) | g_geo (+ g_geo_b)] is formed inside the MLP backward where the pieces have the layout it
     # reads (nvsf_mlp_bwd_density); otherwise (and as the test reference, testing.variant(density_grad="matrix")) by a pass of its own
-    g_geo_b = getattr(ctx, "g_geo_b", None)
-    parts = None
-    if _testing.get("density_grad") == "composed" and x01.is_cuda:
-        parts = density_logit_gradient_parts(g_sigma, sigma.view(-1), g_geo, g_geo_b, spec.n_out - 1, ctx.clamp, n_hidden=spec.n_hidden)
-    grad_h = None
+    parts = grad_h = None
+    if _testing.get("density_grad") == "composed" and x_rows.is_cuda:
+        parts = density_logit_gradient_parts(g_sigma, sigma.view(-1), g_geo, g_geo_b, spec.n_out - 1, clamp, n_hidden=spec.n_hidden)
     if parts is None:
         if g_geo_b is not None:
             g_geo = g_geo + g_geo_b
-        grad_h = torch.empty(M, 16, dtype=torch.float32, device=x01.device)
+        grad_h = torch.empty(M, 16, dtype=torch.float32, device=x_rows.device)
         _hip.call("nvsf_sigma_geo_bwd", None if g_sigma is None else _hip.ptr(g_sigma), _hip.ptr(sigma),
                   None if g_geo is None else _hip.ptr_rows(g_geo), 0 if g_geo is None else g_geo.stride(0), spec.n_out - 1, M,
-                  _hip.ptr(grad_h), 16, ctx.clamp[0], ctx.clamp[1])
-    need_table, need_w = ctx.need_table, ctx.need_w
+                  _hip.ptr(grad_h), 16, clamp[0], clamp[1])
+        grad_h = grad_h[:, :spec.n_out]
+    return mlp_backward(x_rows, w16, spec, grad_h, need_grad_x=need_grad_x, grad_x_blocks=grad_x_blocks, density_grad=parts)
+
+
+def static_density_backward(ctx, x01, feat, sigma, mlp_w16, grid_spec, mlp_spec, clamp, rows_per_ray, need_table, need_w, g_sigma, g_geo,
+                            g_geo_b=None):
+    """Backward of the static field's density shared by DensityFn, DensityRaysFn and RenderRaysFn: density MLP, then the table scatter ->
+    (grad_table | None, grad_mlp_weights | None).  `ctx`: the node's own autograd ctx, read only for the sink contract (ctx.train_ctx,
+    ctx.tables as `announce` left them)."""
+    M = x01.shape[0]
     # levels whose cells are shorter than a few ray steps go through the binned scatter (rows are ray-ordered with a known ray length);
     # the MLP then hands its input gradient over level by level ([L, M, F]): every pass of the scatter reads one contiguous column
-    fine = _bin_from(ctx.grid_spec, M, getattr(ctx, "rows_per_ray", None)) if need_table else None
-    blocks = ctx.grid_spec.F if (LEVEL_MAJOR_GRADIENT and fine is not None and M <= _BIN_ROWS_MAX and spec.n_in == ctx.grid_spec.L * ctx.grid_spec.F
-                                 and feat.dtype == torch.float16 and feat.stride(0) % 8 == 0
-                                 and _hip.hashgrid_bwd_ws_bytes(M, ctx.grid_spec, fine[0], fine[1]) > 0) else 0
-    grad_feat, grad_w = mlp_backward(feat, mlp_w16, spec, None if grad_h is None else grad_h[:, :spec.n_out], need_grad_x=need_table,
-                                     grad_x_blocks=blocks, density_grad=parts)
+    fine = _bin_from(grid_spec, M, rows_per_ray) if need_table else None
+    blocks = grid_spec.F if (LEVEL_MAJOR_GRADIENT and fine is not None and M <= _BIN_ROWS_MAX and mlp_spec.n_in == grid_spec.L * grid_spec.F
+                             and feat.dtype == torch.float16 and feat.stride(0) % 8 == 0
+                             and _hip.hashgrid_bwd_ws_bytes(M, grid_spec, fine[0], fine[1]) > 0) else 0
+    grad_feat, grad_w = density_mlp_backward(feat, mlp_w16, mlp_spec, sigma, g_sigma, g_geo, g_geo_b, clamp, need_table, grad_x_blocks=blocks)
     grad_table = None
     if need_table and not scatter_to_sink(ctx, (x01, grad_feat), lambda views, pool: hashgrid_backward(
-            x01, (0, 1, 2), ctx.grid_spec, grad_feat, grad_table=views[0].view(-1), fine_from=fine, ws_pool=pool)):
+            x01, (0, 1, 2), grid_spec, grad_feat, grad_table=views[0].view(-1), fine_from=fine, ws_pool=pool)):
         pool = ctx.train_ctx.ws_pool if ctx.train_ctx is not None else None
-        grad_table = hashgrid_backward(x01, (0, 1, 2), ctx.grid_spec, grad_feat, fine_from=fine, ws_pool=pool)
-    return grad_table, None, None, (grad_w if need_w else None), None, None, None, None
+        grad_table = hashgrid_backward(x01, (0, 1, 2), grid_spec, grad_feat, fine_from=fine, ws_pool=pool)
+    return grad_table, (grad_w if need_w else None)
 
 
 def _uniform_ray_args(rays_o, rays_d, nears, fars, T, noise, aabb_host, bound, table_f16, spec):
@@ -915,8 +924,9 @@ class DensityRaysFn(Function):
 
     @staticmethod
     def backward(ctx, _g_z, g_sigma, g_geo, _g_geo16):
-        g = _density_backward(ctx, g_sigma, g_geo)  # (grad_table, None, None, grad_w, ...)
-        return (None,) * 8 + (g[0], None, None, g[3], None, None, None, None, None, None)
+        grad_table, grad_w = static_density_backward(ctx, *ctx.saved_tensors, ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray,
+                                                     ctx.need_table, ctx.need_w, g_sigma, g_geo)
+        return (None,) * 8 + (grad_table, None, None, grad_w, None, None, None, None, None, None)
 
 
 def render_uniform_train_forward(rays_o, rays_d, nears, fars, T, aabb_host, bound, noise, table_f16, grid_spec, sigma_w16, lidar, head_a_w16,
@@ -951,7 +961,7 @@ class RenderRaysFn(Function):
     CompositeWeightsFn -> mask / count -> HeadsFn x 1-2 -> MaskedSigmoidFn -> CompositeImageFn) runs the same arithmetic as seven
     to nine launches that write and re-read the [M, 16] network outputs, the per-sample logits and the mask: 1.0 against 0.4 ms of
     device time for a LiDAR batch of 4096 x 768.  Backward = the chain's backward kernels in the chain's order: image -> sigmoid ->
-    heads (fused data + weight gradients on shared-prefix rows) -> compositor -> density MLP -> table scatter (_density_backward:
+    heads (fused data + weight gradients on shared-prefix rows) -> compositor -> density MLP -> table scatter (static_density_backward:
     side stream, gradient sink, level-major hand-over -- unchanged)."""
 
     @staticmethod
@@ -974,7 +984,6 @@ class RenderRaysFn(Function):
 
     @staticmethod
     def backward(ctx, _g_z, g_weights, g_ws, g_depth, g_image):
-        import types
         x01, feat, sigma, sigma_w16, geo16, rgbs, weights, z_vals, nears, fars, w16_a, w16_b, enc_ray = ctx.saved_tensors
         N, T, C, n_enc, lidar, k_scale, bg = ctx.dims
         M, dev = N * T, x01.device
@@ -1019,12 +1028,9 @@ class RenderRaysFn(Function):
         _hip.call("nvsf_composite_uniform_weights_bwd", _hip.ptr(sigma), _hip.ptr(z_vals), _hip.ptr(nears), _hip.ptr(fars), _hip.ptr(g_w), _hip.ptr(g_ws),
                   _hip.ptr(g_depth), N, T, k_scale, _hip.ptr(g_sigma))
         # ---- density MLP + table scatter: DensityFn's backward on what this node saved
-        dctx = types.SimpleNamespace(saved_tensors=(x01, feat, sigma, sigma_w16), mlp_spec=ctx.mlp_spec, clamp=ctx.clamp, grid_spec=ctx.grid_spec,
-                                     tables=ctx.tables, rows_per_ray=ctx.rows_per_ray, train_ctx=ctx.train_ctx, need_table=ctx.need_table,
-                                     need_w=ctx.need_w, g_geo_b=grad_geo_b)
-        d = _density_backward(dctx, g_sigma.view(-1), grad_geo)  # (grad_table, None, None, grad_w_sigma, ...)
         out = [None] * 29
-        out[8], out[11] = d[0], d[3]
+        out[8], out[11] = static_density_backward(ctx, x01, feat, sigma, sigma_w16, ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray,
+                                                  ctx.need_table, ctx.need_w, g_sigma.view(-1), grad_geo, grad_geo_b)
         if ctx.need_heads[0]:
             out[14] = gw_a
         if lidar and ctx.need_heads[1]:

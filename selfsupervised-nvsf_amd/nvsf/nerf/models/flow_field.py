@@ -137,22 +137,19 @@ class FlowField(nn.Module):
                 and lin[1].out_features == 64 and lin[2].out_features <= 16)
 
     def _mlp_weights_f16(self):
-        """fp16 copy of the Linear weights in the fused kernel's layout (W0 [64, in] ++ W1 [64, 64] ++ W2 zero-padded to
-        [16, 64], row-major = nn.Linear's [out, in]); rebuilt when a weight changes."""
+        """fp16 copy of the Linear weights in the fused kernel's layout (_pack_flow_weights); rebuilt when a weight changes."""
         lin = [m for m in self.mlp if isinstance(m, nn.Linear)]
         key = tuple((l.weight.data_ptr(), l.weight._version) for l in lin)
         if getattr(self, "_mlp_key", None) != key:
-            w2 = torch.zeros(16, 64, dtype=torch.float32, device=lin[2].weight.device)
-            w2[:lin[2].out_features] = lin[2].weight.detach().float()
-            self._mlp_w16 = torch.cat([lin[0].weight.detach().float().reshape(-1), lin[1].weight.detach().float().reshape(-1),
-                                       w2.reshape(-1)]).to(torch.float16).contiguous()
+            self._mlp_w16 = _pack_flow_weights(*[l.weight for l in lin])
             self._mlp_spec = ops.MlpSpec(lin[0].in_features, lin[2].out_features, hidden=64, n_hidden=2)
             self._mlp_key = key
         return self._mlp_w16
 
 
 def _pack_flow_weights(w0, w1, w2):
-    """nn.Linear weights [out, in] -> the fused kernels' fp16 layout W0 [64, in] ++ W1 [64, 64] ++ W2 zero-padded to [16, 64]."""
+    """nn.Linear weights [out, in] -> the fused kernels' fp16 layout W0 [64, in] ++ W1 [64, 64] ++ W2 zero-padded to [16, 64],
+    each row-major as nn.Linear keeps it."""
     w2p = torch.zeros(16, 64, dtype=torch.float32, device=w2.device)
     w2p[:w2.shape[0]] = w2.detach().float()
     return torch.cat([w0.detach().float().reshape(-1), w1.detach().float().reshape(-1), w2p.reshape(-1)]).to(torch.float16).contiguous()

@@ -15,6 +15,7 @@ because the same expressions are applied to the same operand types.  The referen
 device tensors and branches on `idx1 == idx2` (one device->host sync per plane per call); here the slice indices
 come from one host copy of t per call.
 """
+import collections
 import math
 
 import numpy as np
@@ -95,6 +96,27 @@ def lagrange_reduce(feat, t, n_levels, n_features, num_basis):
     return out.view(-1, n_levels * n_features // num_basis)
 
 
+TimeSlot = collections.namedtuple("TimeSlot", "k1 k2 idx b_lo b_hi same lag")
+
+
+def time_slot(t, t_host, time_resolution):
+    """Where the frame time falls among the `time_resolution` slices, for every caller of the space-time grids: the slices k1 = floor,
+    k2 = ceil of the fp32 `idx`, the blend factors of the two slices (Python floats of fp32 values), `same` (t is a slice time: one
+    slice, no blend) and the four Lagrange weights in the division form PyTorch would use for `t` (lagrange_weights_host)."""
+    idx = np.float32(t_host) * np.float32(time_resolution - 1)
+    k1, k2 = int(math.floor(idx)), int(math.ceil(idx))
+    on_device = torch.is_tensor(t) and t.is_cuda
+    return TimeSlot(k1, k2, idx, float(np.float32(k2) - idx), float(idx - np.float32(k1)), k1 == k2,
+                    lagrange_weights_host(t_host, 4, reciprocal_division=on_device))
+
+
+def neighbour_frames(frame_idx, num_frames):
+    """(next, previous) frame of `frame_idx` for the flow-warped evaluations: (t_n as the 0-dim CPU tensor of the reference (:244, :260:
+    the fp16 regime of HashGridT), its host value in fp32, first flow column: 0 forward | 3 backward), or None past either end."""
+    return [(torch.tensor(frame / num_frames), float(np.float32(frame / num_frames)), col) if 0 <= frame <= num_frames - 1 else None
+            for col, frame in ((0, frame_idx + 1), (3, frame_idx - 1))]
+
+
 class HashGridT(nn.Module):
     def __init__(self, time_resolution=25, base_resolution=512, max_resolution=32768, n_levels=8, n_features_per_level=4,
                  log2_hashmap_size=14, num_basis=4, cols=(0, 1)):
@@ -113,13 +135,13 @@ class HashGridT(nn.Module):
 
     def forward(self, x, t, t_host=None):
         """x: [N, >=2] (the two columns `self.cols` are encoded), t in [0, 1]."""
-        t_host = _host_time(t) if t_host is None else t_host
-        idx_host = np.float32(t_host) * np.float32(self.time_resolution - 1)
-        k1, k2 = int(math.floor(idx_host)), int(math.ceil(idx_host))
-        if k1 == k2:
+        R = self.time_resolution
+        slot = time_slot(t, _host_time(t) if t_host is None else t_host, R)
+        k1, k2 = slot.k1, slot.k2
+        if slot.same:
             feat = self._slice(k1, x)
         else:
-            idx = t * (self.time_resolution - 1)
+            idx = t * (R - 1)
             feat = (k2 - idx) * self._slice(k1, x) + (idx - k1) * self._slice(k2, x)
         return lagrange_reduce(feat, t, self.n_levels, self.n_features_per_level, self.num_basis)
 
@@ -179,32 +201,44 @@ class HashGrid4D(nn.Module):
                     and testing.get("hash4d_train") == "fused"):
                 # fused forward + fused table-gradient kernel (csrc/hashgrid4d.hip) instead of six per-slice encoder calls,
                 # their blends / Lagrange reductions and six backward launches
-                idx = np.float32(t_host) * np.float32(first.time_resolution - 1)
-                k1, k2 = int(math.floor(idx)), int(math.ceil(idx))
-                params = [pl.hash_t[k1].params for pl in self.hash_dynamic] + [pl.hash_t[k2].params for pl in self.hash_dynamic]
-                return self._reduce(HashDynFn.apply(self, x, t, t_host, k1, k2, _ops.train_context(self), *params))
+                slot = time_slot(t, t_host, first.time_resolution)
+                return self._reduce(HashDynFn.apply(self, x, t, slot, _ops.train_context(self), *self._slice_params(slot)))
             return self._reduce(torch.cat([plane(x, t, t_host) for plane in self.hash_dynamic], dim=-1))
-        return self._reduce(self._forward_dynamic_fused(x, t, t_host, offset, offset_col))
+        return self._reduce(self._forward_dynamic_fused(x, t, time_slot(t, t_host, self.hash_dynamic[0].time_resolution), offset, offset_col))
 
-    def _forward_dynamic_fused(self, x, t, t_host, offset, offset_col):
+    def _slice_params(self, slot):
+        """The parameters an evaluation in `slot` reads: the floor slice of the three pairs, then the ceil slice."""
+        return [pl.hash_t[k].params for k in (slot.k1, slot.k2) for pl in self.hash_dynamic]
+
+    def _slice_tables(self, slot):
+        """The fp16 tables of _slice_params, in that order."""
+        return [pl.hash_t[k].table_f16() for k in (slot.k1, slot.k2) for pl in self.hash_dynamic]
+
+    def pair_level_tables(self):
+        """(specs, h_scales, h_res, h_off) of the three pair grids: their level tables side by side as the host arrays the fused kernels
+        take.  Constant for the life of the specs, so built once and kept for as long as the specs are these objects (GridSpec holds
+        the same arrays of a single grid, h_scales / h_res / h_offsets)."""
+        specs = [pl.hash_t[0].spec for pl in self.hash_dynamic]
+        cached = self.__dict__.get("_pair_tables")
+        if cached is None or any(a is not b for a, b in zip(cached[0], specs)):
+            from nvsf import _hip
+            flat = lambda attr: [v for s in specs for v in getattr(s, attr)]
+            cached = self.__dict__["_pair_tables"] = (specs, _hip.host_f32(flat("scales")), _hip.host_u32(flat("res")), _hip.host_u32(flat("offsets")))
+        return cached
+
+    def _check_fused_shape(self):
+        first = self.hash_dynamic[0]
+        if first.n_levels != 8 or first.n_features_per_level != 4 or first.num_basis != 4:
+            raise NotImplementedError("fused HashGridT kernel: 8 levels x 4 features, 4 Lagrange nodes")
+
+    def _forward_dynamic_fused(self, x, t, slot, offset, offset_col):
         from nvsf import _hip
         import ctypes
-        first = self.hash_dynamic[0]
-        R, L = first.time_resolution, first.n_levels
-        if L != 8 or first.n_features_per_level != 4 or first.num_basis != 4:
-            raise NotImplementedError("fused HashGridT kernel: 8 levels x 4 features, 4 Lagrange nodes")
-        idx = np.float32(t_host) * np.float32(R - 1)
-        k1, k2 = int(math.floor(idx)), int(math.ceil(idx))
+        self._check_fused_shape()
         fp16_regime = torch.is_tensor(t) and t.dim() == 0  # PyTorch promotion: a 0-dim t keeps the arithmetic in fp16
-        on_device = torch.is_tensor(t) and t.is_cuda
-        lag = lagrange_weights_host(t_host, 4, reciprocal_division=on_device)
-        h_time = _hip.host_f32([float(np.float32(k2) - idx), float(idx - np.float32(k1))] + lag)
-        tables = [pl.hash_t[k1].table_f16() for pl in self.hash_dynamic] + [pl.hash_t[k2].table_f16() for pl in self.hash_dynamic]
-        h_tables = (ctypes.c_void_p * 6)(*[tb.data_ptr() for tb in tables])
-        specs = [pl.hash_t[0].spec for pl in self.hash_dynamic]
-        h_scales = _hip.host_f32([v for s in specs for v in s.scales])
-        h_res = _hip.host_u32([v for s in specs for v in s.res])
-        h_off = _hip.host_u32([v for s in specs for v in s.offsets])
+        h_time = _hip.host_f32([slot.b_lo, slot.b_hi] + slot.lag)
+        h_tables = (ctypes.c_void_p * 6)(*[tb.data_ptr() for tb in self._slice_tables(slot)])
+        _, h_scales, h_res, h_off = self.pair_level_tables()
         x = x.float().contiguous()
         M = x.shape[0]
         out = torch.empty(M, 24, dtype=torch.float16 if fp16_regime else torch.float32, device=x.device)
@@ -214,7 +248,7 @@ class HashGrid4D(nn.Module):
             if off.dim() != 2 or off.stride(1) != 1:
                 off = off.contiguous()
         _hip.call("nvsf_hashgrid4d_dynamic_fwd", _hip.ptr(x), x.shape[1], None if off is None else _hip.ptr_rows(off), off.stride(0) if off is not None else 0,
-                  int(offset_col), M, h_tables, h_scales, h_res, h_off, h_time, 1 if k1 == k2 else 0, 1 if fp16_regime else 0, _hip.ptr(out))
+                  int(offset_col), M, h_tables, h_scales, h_res, h_off, h_time, 1 if slot.same else 0, 1 if fp16_regime else 0, _hip.ptr(out))
         return out
 
     def training_fused3(self, x, t, t_host, flow, frame_idx, num_frames):
@@ -224,27 +258,22 @@ class HashGrid4D(nn.Module):
         if not (torch.is_grad_enabled() and torch.is_tensor(t) and t.dim() > 0 and not x.requires_grad and first.n_levels == 8
                 and first.n_features_per_level == 4 and first.num_basis == 4 and testing.get("hash4d_train") == "fused"):
             return None
-        idx = np.float32(t_host) * np.float32(first.time_resolution - 1)
-        k1, k2 = int(math.floor(idx)), int(math.ceil(idx))
-        nb = []
-        for col, frame in ((0, frame_idx + 1), (3, frame_idx - 1)):
-            nb.append((torch.tensor(frame / num_frames), float(np.float32(frame / num_frames)), col) if 0 <= frame <= num_frames - 1 else None)
+        nb = neighbour_frames(frame_idx, num_frames)
         if nb[0] is None and nb[1] is None:
             return None
-        params = [pl.hash_t[k1].params for pl in self.hash_dynamic] + [pl.hash_t[k2].params for pl in self.hash_dynamic]
-        return tuple(o if o is None else self._reduce(o) for o in HashDyn3Fn.apply(self, x, t, t_host, k1, k2, flow, nb[0], nb[1], _ops.train_context(self), *params))
+        slot = time_slot(t, t_host, first.time_resolution)
+        outs = HashDyn3Fn.apply(self, x, t, t_host, slot, flow, nb[0], nb[1], _ops.train_context(self), *self._slice_params(slot))
+        return tuple(o if o is None else self._reduce(o) for o in outs)
 
-    def forward_dynamic3(self, x, t, t_host, offsets, neighbours):
+    def forward_dynamic3(self, x, t, t_host, offsets, neighbours, slot=None):
         """No-autograd: the dynamic features of one density query in one launch (csrc/hashgrid4d.hip, k_hash_dynamic3):
         at (x, t) [fp32 regime] and, for each entry (t_n 0-dim tensor, its host value, first offset column) | None of
         `neighbours`, at (x + offsets[:, col:col+3], t_n) [fp16 regime].  Returns (hash_d, hash_1 | None, hash_2 | None),
-        bit-identical to the separate forward_dynamic calls."""
+        bit-identical to the separate forward_dynamic calls.  `slot`: time_slot of (t, t_host) where the caller already has it."""
         from nvsf import _hip
         import ctypes
-        first = self.hash_dynamic[0]
-        R = first.time_resolution
-        if first.n_levels != 8 or first.n_features_per_level != 4 or first.num_basis != 4:
-            raise NotImplementedError("fused HashGridT kernel: 8 levels x 4 features, 4 Lagrange nodes")
+        self._check_fused_shape()
+        R = self.hash_dynamic[0].time_resolution
         assert neighbours[0] is None or neighbours[0][2] == 0
         assert neighbours[1] is None or neighbours[1][2] == 3
         evals = [(t, t_host)] + [None if n is None else (n[0], n[1]) for n in neighbours]
@@ -255,17 +284,13 @@ class HashGrid4D(nn.Module):
                 h_time += [0.0] * 6
                 flags += [0, 0, 0]
                 continue
-            te, te_host = ev
-            idx = np.float32(te_host) * np.float32(R - 1)
-            k1, k2 = int(math.floor(idx)), int(math.ceil(idx))
-            on_device = torch.is_tensor(te) and te.is_cuda
-            lag = lagrange_weights_host(te_host, 4, reciprocal_division=on_device)
-            tables += [pl.hash_t[k1].table_f16().data_ptr() for pl in self.hash_dynamic] + [pl.hash_t[k2].table_f16().data_ptr() for pl in self.hash_dynamic]
-            h_time += [float(np.float32(k2) - idx), float(idx - np.float32(k1))] + lag
+            s = slot if (e == 0 and slot is not None) else time_slot(ev[0], ev[1], R)
+            tables += [tb.data_ptr() for tb in self._slice_tables(s)]
+            h_time += [s.b_lo, s.b_hi] + s.lag
             if e == 0:
-                base = (k1, k2)
-            flags += [1, 1 if k1 == k2 else 0, 1 if (k1, k2) == base else 0]
-        specs = [pl.hash_t[0].spec for pl in self.hash_dynamic]
+                base = (s.k1, s.k2)
+            flags += [1, 1 if s.same else 0, 1 if (s.k1, s.k2) == base else 0]
+        _, h_scales, h_res, h_off = self.pair_level_tables()
         x = x.float().contiguous()
         M, dev = x.shape[0], x.device
         off = offsets.float()
@@ -275,9 +300,7 @@ class HashGrid4D(nn.Module):
         out1 = torch.empty(M, 24, dtype=torch.float16, device=dev) if neighbours[0] is not None else None
         out2 = torch.empty(M, 24, dtype=torch.float16, device=dev) if neighbours[1] is not None else None
         _hip.call("nvsf_hashgrid4d_dynamic3_fwd", _hip.ptr(x), x.shape[1], _hip.ptr_rows(off), off.stride(0), M, (ctypes.c_void_p * 18)(*tables),
-                  _hip.host_f32([v for s in specs for v in s.scales]), _hip.host_u32([v for s in specs for v in s.res]),
-                  _hip.host_u32([v for s in specs for v in s.offsets]), _hip.host_f32(h_time), _hip.host_i32(flags), _hip.ptr(out0),
-                  _hip.ptr(out1), _hip.ptr(out2))
+                  h_scales, h_res, h_off, _hip.host_f32(h_time), _hip.host_i32(flags), _hip.ptr(out0), _hip.ptr(out1), _hip.ptr(out2))
         return tuple(o if o is None else self._reduce(o) for o in (out0, out1, out2))
 
     def forward(self, x, t, t_host=None):
@@ -291,34 +314,26 @@ class HashDynFn(torch.autograd.Function):
     gradients reach exactly the tensors the per-slice path would have touched."""
 
     @staticmethod
-    def forward(ctx, enc, x, t, t_host, k1, k2, train_ctx, *params):
+    def forward(ctx, enc, x, t, slot, train_ctx, *params):
         x = x.float().contiguous()
-        out = enc._forward_dynamic_fused(x, t, t_host, None, 0)
+        out = enc._forward_dynamic_fused(x, t, slot, None, 0)
         ctx.save_for_backward(x)
-        ctx.enc, ctx.t, ctx.t_host, ctx.k1, ctx.k2, ctx.params = enc, t, t_host, k1, k2, params
+        ctx.enc, ctx.slot, ctx.params = enc, slot, params
         _ops.announce(ctx, train_ctx, params)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        return (None,) * 7 + HashDynFn._backward(ctx, grad_out)
+        return (None,) * 5 + HashDynFn._backward(ctx, grad_out)
 
     @staticmethod
     def _backward(ctx, grad_out):
-        """-> the gradients of ctx.params."""
+        """-> the gradients of ctx.params, in the time slot the forward evaluated (ctx.slot)."""
         from nvsf import _hip
         import ctypes
         (x,) = ctx.saved_tensors
-        enc, t_host, k1, k2 = ctx.enc, ctx.t_host, ctx.k1, ctx.k2
-        first = enc.hash_dynamic[0]
-        idx = np.float32(t_host) * np.float32(first.time_resolution - 1)
-        lag = lagrange_weights_host(t_host, 4, reciprocal_division=torch.is_tensor(ctx.t) and ctx.t.is_cuda)
-        h_time = _hip.host_f32([float(np.float32(k2) - idx), float(idx - np.float32(k1))] + lag)
-        specs = [pl.hash_t[0].spec for pl in enc.hash_dynamic]
-        h_scales = _hip.host_f32([v for s in specs for v in s.scales])
-        h_res = _hip.host_u32([v for s in specs for v in s.res])
-        h_off = _hip.host_u32([v for s in specs for v in s.offsets])
-        same = k1 == k2
+        same, b_lo, b_hi = ctx.slot.same, ctx.slot.b_lo, ctx.slot.b_hi
+        specs, h_scales, h_res, h_off = ctx.enc.pair_level_tables()
         # The two slices of a pair see the same cells and corner weights; their gradients differ by the scalar blend factors
         # only (dL/dtable_lo = blend_lo G, dL/dtable_hi = blend_hi G with G = sum g lag_i w_c).  G is scattered ONCE -- half the
         # atomics, which are what bounds this pass -- and scaled into the two gradients afterwards (tables of ~1 M floats).
@@ -327,8 +342,7 @@ class HashDynFn(torch.autograd.Function):
         col_major = (grad_out.dtype == torch.float32 and grad_out.dim() == 2 and grad_out.shape[1] == 24 and grad_out.stride() == (1, M)
                      and M >= (1 << 16) and testing.get("hash4d_train") == "fused")
         g_out = grad_out if col_major else grad_out.float().contiguous()
-        lag_t = _ops.device_constant(lag, x.device)
-        b_lo, b_hi = float(np.float32(k2) - idx), float(idx - np.float32(k1))
+        lag_t = _ops.device_constant(ctx.slot.lag, x.device)
 
         # ... and the four features of an entry are the four Lagrange chunks: dL/dtable[row][i] = lag_i * blend * G[row] with ONE
         # scalar sum per entry (nvsf_hashgrid4d_dynamic_bwd_scalar), expanded afterwards
@@ -372,11 +386,11 @@ class HashDyn3Fn(torch.autograd.Function):
     evaluates them under no_grad), the table gradients of hash_d come from the fused backward kernel."""
 
     @staticmethod
-    def forward(ctx, enc, x, t, t_host, k1, k2, offsets, nb1, nb2, train_ctx, *params):
+    def forward(ctx, enc, x, t, t_host, slot, offsets, nb1, nb2, train_ctx, *params):
         x = x.float().contiguous()
-        out0, out1, out2 = enc.forward_dynamic3(x, t, t_host, offsets.detach(), [nb1, nb2])
+        out0, out1, out2 = enc.forward_dynamic3(x, t, t_host, offsets.detach(), [nb1, nb2], slot)
         ctx.save_for_backward(x)
-        ctx.enc, ctx.t, ctx.t_host, ctx.k1, ctx.k2, ctx.params = enc, t, t_host, k1, k2, params
+        ctx.enc, ctx.slot, ctx.params = enc, slot, params
         _ops.announce(ctx, train_ctx, params)
         outs = [out0, out1 if out1 is not None else out0.new_zeros(0), out2 if out2 is not None else out0.new_zeros(0)]
         ctx.mark_non_differentiable(outs[1], outs[2])
@@ -384,4 +398,4 @@ class HashDyn3Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out, _g1, _g2):
-        return (None,) * 10 + HashDynFn._backward(ctx, grad_out)
+        return (None,) * 9 + HashDynFn._backward(ctx, grad_out)

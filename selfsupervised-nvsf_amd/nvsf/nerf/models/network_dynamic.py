@@ -26,7 +26,7 @@ from nvsf import field_ops as ops
 from nvsf import testing
 from nvsf.nerf.activation import trunc_exp
 from nvsf.nerf.models.flow_field import FlowField
-from nvsf.nerf.models.hash_field import HashGrid4D, _host_time
+from nvsf.nerf.models.hash_field import HashGrid4D, _host_time, neighbour_frames
 from nvsf.nerf.models.planes_field import Planes4D
 from nvsf.nerf.models.renderer_dynamic import NeRFRenderer
 
@@ -98,14 +98,14 @@ class NeRFNetwork(NeRFRenderer):
         # (ops.PlanesMultiFn: one forward launch, one texel-scatter launch, one launch for the flow gradients) where it is built
         planes_node = (torch.is_grad_enabled() and testing.get("planes_train") == "fused" and x.is_cuda and t.shape[0] == 1
                        and len(planes_enc.multiscale_res) == 4 and not x.requires_grad)
-        nb_time = [float(np.float32(f / self.num_frames)) if 0 <= f <= self.num_frames - 1 else None for f in (frame_idx + 1, frame_idx - 1)]
+        nb = neighbour_frames(frame_idx, self.num_frames)  # (next, previous): (0-dim CPU tensor t_n, its host value, flow column) | None
         if planes_node:
             planes_enc.wait_pending_update()
             # where the fused density tail consumes them, the three dynamic evaluations leave the node already blended (0.5 d + 0.25 (d1 +
             # d2), network_dynamic.py:273): the tail's own blend of (v, v, v) is v exactly, its gradient comes back as one slice
             planes_blend = self._tail_fused_in_training()
             plane_s, plane_d, pm_1, pm_2 = ops.PlanesMultiFn.apply(x, flow, planes_enc.planes_cl, planes_enc._res_host, float(np.float32(t_host)),
-                                                                   nb_time[0], nb_time[1], ops.train_context(planes_enc), planes_blend)
+                                                                   *[n and n[1] for n in nb], ops.train_context(planes_enc), planes_blend)
             if planes_blend:
                 pm_1 = pm_2 = plane_d
         else:
@@ -118,17 +118,17 @@ class NeRFNetwork(NeRFRenderer):
         else:
             hash_s, hash_d = hash_enc(x, t, t_host)
 
-        def neighbour(offset, frame):
-            """dynamic features at the flow-warped position in an adjacent frame (:242-271)"""
-            tn = torch.tensor(frame / self.num_frames)
-            xn = None if (fused3 is not None and planes_node) else x + offset  # (both fused nodes read x + flow inside their kernels)
+        def neighbour(which):
+            """dynamic features at the flow-warped position in an adjacent frame (:242-271); which = 0: the next frame, 1: the previous"""
+            tn, tn_host, col = nb[which]
+            xn = None if (fused3 is not None and planes_node) else x + flow[:, col:col + 3]  # (both fused nodes read x + flow inside their kernels)
             if fused3 is not None:
-                hn = hash_1f if frame > frame_idx else hash_2f
+                hn = (hash_1f, hash_2f)[which]
             else:
                 with torch.no_grad():
-                    hn = hash_enc.forward_dynamic(xn, tn, float(np.float32(frame / self.num_frames)))
+                    hn = hash_enc.forward_dynamic(xn, tn, tn_host)
             if planes_node:
-                return hn, (pm_1 if frame > frame_idx else pm_2)
+                return hn, (pm_1, pm_2)[which]
             # the reference builds this column on the host and copies it (t1.repeat(N, 1).to(device), :250): a pageable
             # multi-megabyte H2D copy that also drains the stream; the same fp32 value is written on the device instead
             t_coln = torch.full((xn.shape[0], 1), float(tn), dtype=torch.float32, device=xn.device)
@@ -137,10 +137,10 @@ class NeRFNetwork(NeRFRenderer):
 
         hash_1 = hash_2 = hash_d
         plane_1 = plane_2 = plane_d
-        if frame_idx < self.num_frames - 1:
-            hash_1, plane_1 = neighbour(flow[:, :3], frame_idx + 1)
-        if frame_idx > 0:
-            hash_2, plane_2 = neighbour(flow[:, 3:], frame_idx - 1)
+        if nb[0] is not None:
+            hash_1, plane_1 = neighbour(0)
+        if nb[1] is not None:
+            hash_2, plane_2 = neighbour(1)
         return plane_s, plane_d, plane_1, plane_2, hash_s, hash_d, hash_1, hash_2
 
     def _dynamic_features_fused(self, x, t, t_host, frame_idx, hash_enc, planes_enc, fp16=None):
@@ -149,14 +149,10 @@ class NeRFNetwork(NeRFRenderer):
         written once.  (A single K-planes launch for all three positions that keeps the base evaluation's texel quads in
         registers was measured and rejected: 0.90 ms against 3 x 0.21 ms -- the quads cost the occupancy that hides the
         gather latency, and the neighbours' re-gathers hit L1 anyway.)"""
-        F = self.num_frames
         xt = torch.cat([x, t.float().expand(x.shape[0], 1)], dim=-1)
         flow = self.flow_net(xt, t_host, fp16=fp16)
         hash_s = hash_enc.forward_static(x, level_major=True)  # [8, M, 4] where available: _density_tail_fused reads either layout
-        nb = []
-        for col, frame in ((0, frame_idx + 1), (3, frame_idx - 1)):
-            # 0-dim CPU tensor as in the reference (:244, :260): the fp16 regime of HashGridT
-            nb.append((torch.tensor(frame / F), float(np.float32(frame / F)), col) if 0 <= frame <= F - 1 else None)
+        nb = neighbour_frames(frame_idx, self.num_frames)
         # ONE launch for the three space-time evaluations: a neighbour re-uses the base gathers wherever its cell coincides
         hash_d, hash_1, hash_2 = hash_enc.forward_dynamic3(x, t, t_host, flow, nb)
         # ONE launch for the K-planes: static + dynamic at (x, t) + dynamic at the flow-warped positions of the neighbour
@@ -219,16 +215,16 @@ class NeRFNetwork(NeRFRenderer):
         M, dev = plane_s.shape[0], plane_s.device
         c = lambda a: a.contiguous()
         hash_d = hash_d.float()
-        entry = "nvsf_density_dynamic_fwd"
         planes = [_hip.ptr(c(plane_s)), _hip.ptr(c(plane_d)), _hip.ptr(c(plane_1)), _hip.ptr(c(plane_2))]
-        if plane_s.dtype == torch.float16:  # rows of forward_multi(..., out_f16=True): plane_d is the blend already
+        f16_planes = plane_s.dtype == torch.float16  # rows of forward_multi(..., out_f16=True): plane_d is the blend already
+        if f16_planes:
             if plane_d.dtype != torch.float16 or plane_1 is not plane_d or plane_2 is not plane_d:
                 raise ValueError("fp16 plane rows come blended (plane_1 = plane_2 = plane_d)")
-            entry, planes = "nvsf_density_dynamic_f16planes_fwd", planes[:2]
-        if hash_s.dim() == 3:  # level-major static hash features (hash_field.forward_static(level_major=True))
-            if tuple(hash_s.shape) != (8, M, 4) or hash_s.dtype != torch.float16:
-                raise ValueError("level-major static hash features come as fp16 [8, M, 4]")
-            entry = "nvsf_density_dynamic_lm_fwd" if entry == "nvsf_density_dynamic_f16planes_fwd" else "nvsf_density_dynamic_lm32_fwd"
+            planes = planes[:2]
+        level_major = hash_s.dim() == 3  # level-major static hash features (hash_field.forward_static(level_major=True))
+        if level_major and (tuple(hash_s.shape) != (8, M, 4) or hash_s.dtype != torch.float16):
+            raise ValueError("level-major static hash features come as fp16 [8, M, 4]")
+        entry = _DENSITY_TAIL_ENTRIES[f16_planes, level_major]
         args = planes + [_hip.ptr(c(hash_s)), _hip.ptr(c(hash_d)),
                          _hip.ptr(c(hash_1)), 1 if hash_1.dtype == torch.float16 else 0, _hip.ptr(c(hash_2)), 1 if hash_2.dtype == torch.float16 else 0,
                          M, _hip.ptr(self.sigma_net.weights_f16())]
@@ -291,6 +287,11 @@ class NeRFNetwork(NeRFRenderer):
         return params
 
 
+# the density tail's entry points (csrc/density_dynamic.hip) by (planes are fp16 blended rows, hash_s is level-major)
+_DENSITY_TAIL_ENTRIES = {(False, False): "nvsf_density_dynamic_fwd", (True, False): "nvsf_density_dynamic_f16planes_fwd",
+                         (False, True): "nvsf_density_dynamic_lm32_fwd", (True, True): "nvsf_density_dynamic_lm_fwd"}
+
+
 class DensityTailFn(torch.autograd.Function):
     """h = sigma_net([plane_s | 0.5 plane_d + 0.25 (plane_1 + plane_2) | hash_s | 0.5 hash_d + 0.25 (hash_1 + hash_2)])
     (network_dynamic.py:273-287) with autograd: forward = csrc/density_dynamic.hip (also writes the rounded input),
@@ -323,27 +324,9 @@ class DensityTailFn(torch.autograd.Function):
         spec = ctx.spec
         need = ctx.needs_input_grad
         need_x = any(need[1:9])
-        # logit gradient [g_sigma * clamp(sigma) | g_geo] in one pass (ops.DensityFn does the same for the static field)
+        # logit gradient [g_sigma * clamp(sigma) | g_geo] and the MLP backward: the static field's (ops.DensityFn), on the rounded input
         M = x16.shape[0]
-        if g_sigma is not None:
-            g_sigma = g_sigma.float().contiguous()
-        if g_geo is not None and (g_geo.dtype != torch.float32 or g_geo.stride(1) != 1):
-            g_geo = g_geo.float().contiguous()
-        # the logit gradient formed inside the MLP backward where the pieces have the layout it reads (ops.mlp_backward(density_grad=...),
-        # as the static field's node does), else by a pass of its own
-        parts = None
-        if testing.get("density_grad") == "composed" and x16.is_cuda:
-            parts = ops.density_logit_gradient_parts(g_sigma, sigma, g_geo, None, spec.n_out - 1, (activation._LO, activation._HI),
-                                                     n_hidden=spec.n_hidden)
-        if parts is not None:
-            grad_x, gw = ops.mlp_backward(x16[:, :spec.n_in], w16, spec, None, need_grad_x=need_x, density_grad=parts)
-        else:
-            grad_h = torch.empty(M, 16, dtype=torch.float32, device=x16.device)
-            _hip.call("nvsf_sigma_geo_bwd", None if g_sigma is None else _hip.ptr(g_sigma), _hip.ptr(sigma),
-                      None if g_geo is None else _hip.ptr_rows(g_geo), 0 if g_geo is None else g_geo.stride(0), spec.n_out - 1, M,
-                      _hip.ptr(grad_h), 16, activation._LO, activation._HI)
-            grad_h = grad_h[:, :spec.n_out]
-            grad_x, gw = ops.mlp_backward(x16[:, :spec.n_in], w16, spec, grad_h, need_grad_x=need_x)
+        grad_x, gw = ops.density_mlp_backward(x16[:, :spec.n_in], w16, spec, sigma, g_sigma, g_geo, None, (activation._LO, activation._HI), need_x)
         out = [None] * 10
         if need_x and grad_x.is_cuda and grad_x.stride(1) == 1 and grad_x.stride(0) % 4 == 0 and grad_x.shape[1] >= 120:
             # the blend factors and the dtype of hash_s applied in ONE pass over the rows (nvsf_density_tail_grad_split)

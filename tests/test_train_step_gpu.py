@@ -680,7 +680,7 @@ def test_overflowing_step_is_skipped_for_every_parameter_with_the_last_table_def
 
 
 def test_density_gradient_composed_equals_the_matrix_form_in_the_step(dev, variants):
-    """RenderRaysFn.backward / _density_backward with the density network's logit gradient formed inside the MLP backward
+    """RenderRaysFn.backward / static_density_backward with the density network's logit gradient formed inside the MLP backward
     (nvsf_mlp_bwd_density; the second LiDAR head writes geometry-gradient rows of its own) against the sigma_geo pass + accumulating
     second head they replace: same gradients on every parameter (fp32 atomic order only)."""
     from nvsf import synthetic as S
