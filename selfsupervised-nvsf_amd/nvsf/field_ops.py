@@ -499,10 +499,8 @@ def heads(model, d01, geo_feat, cal_lidar_color, ray_dirs01=None, geo16=None):
     encoding is then evaluated N times and broadcast to the samples (same values: every sample of a ray has its direction).
     geo16: fp16 [M, 16] rows (geometry features, 1.0) that already hold fp16(geo_feat) -- the fused training forward writes them
     (DensityRaysFn) -- and serve as the MLP kernels' per-sample input as they are."""
-    if cal_lidar_color:
-        net_a, net_b, enc = model.raydrop_net, model.intensity_net, model.view_encoder_lidar
-    else:
-        net_a, net_b, enc = model.color_net, None, model.view_encoder_camera
+    m = model._modality(cal_lidar_color)
+    net_a, net_b, enc = m.head_a, m.head_b, m.venc
     spec = net_a.spec
     M = geo_feat.shape[0]
     n_enc_cols = enc.n_output_dims
@@ -527,9 +525,8 @@ def heads(model, d01, geo_feat, cal_lidar_color, ray_dirs01=None, geo16=None):
             _hip.call("nvsf_repeat_rows_f16", _hip.ptr(dst), src.shape[0], n_enc_cols, dst.stride(0), M // src.shape[0], _hip.ptr(buf),
                       buf.stride(0))
     x16 = geo16 if (prefix_mode and geo16 is not None and geo_feat.shape[1] == 15 and tuple(geo16.shape) == (M, 16)) else None
-    if net_b is None:
-        return HeadsFn.apply(buf, enc.n_output_dims, geo_feat, net_a.params, net_a.weights_f16(), spec, None, None, enc_ray, x16)
-    return HeadsFn.apply(buf, enc.n_output_dims, geo_feat, net_a.params, net_a.weights_f16(), spec, net_b.params, net_b.weights_f16(), enc_ray, x16)
+    w16_a, w16_b = net_a.weights_f16(), (None if net_b is None else net_b.weights_f16())
+    return HeadsFn.apply(geo_feat, net_a.params, None if net_b is None else net_b.params, buf, enc.n_output_dims, w16_a, spec, w16_b, enc_ray, x16)
 
 
 class HeadsFn(Function):
@@ -544,7 +541,7 @@ class HeadsFn(Function):
     afterwards."""
 
     @staticmethod
-    def forward(ctx, buf, n_enc, geo, params_a, w16_a, spec, params_b=None, w16_b=None, enc_ray=None, x16_ready=None):
+    def forward(ctx, geo, params_a, params_b, buf, n_enc, w16_a, spec, w16_b=None, enc_ray=None, x16_ready=None):
         n_geo = geo.shape[1]
         if buf is None:  # shared-prefix rows: x = [geometry | ones] fp16 [M, 16], the encoding stays one row per ray
             assert enc_ray is not None and n_enc + n_geo == spec.n_in
@@ -602,7 +599,7 @@ class HeadsFn(Function):
         spec, n_enc, n_geo = ctx.spec, ctx.n_enc, ctx.n_geo
         grad_h = grad_h.float().contiguous()
         M = buf.shape[0]
-        need_geo = ctx.needs_input_grad[2]
+        need_geo, need_a, need_b = ctx.needs_input_grad[:3]
         grad_geo = torch.empty(M, (n_geo + 3) // 4 * 4, dtype=torch.float32, device=buf.device)[:, :n_geo] if need_geo else None
         _, gw_a = mlp_backward(u, w16_a, spec, grad_h[:, :spec.n_out], need_grad_x=need_geo, grad_x=grad_geo, gx_col0=n_enc, prefix=prefix)
         gw_b = None
@@ -611,8 +608,7 @@ class HeadsFn(Function):
                                    gx_col0=n_enc, accumulate=True, prefix=prefix)
         if grad_geo is not None and grad_geo.dtype != ctx.geo_dtype:
             grad_geo = grad_geo.to(ctx.geo_dtype)
-        return (None, None, grad_geo, gw_a if ctx.needs_input_grad[3] else None, None, None,
-                gw_b if (w16_b is not None and ctx.needs_input_grad[6]) else None, None, None, None)
+        return (grad_geo, gw_a if need_a else None, gw_b if (w16_b is not None and need_b) else None) + (None,) * 7
 
 
 class MlpFn(Function):
@@ -810,23 +806,30 @@ class DensityFn(Function):
     leaves nvsf_mlp_bwd (the operator chain rounds it to fp16 in between, a pass over [M, 32])."""
 
     @staticmethod
-    def forward(ctx, x01, table_params, table_f16, grid_spec, mlp_params, mlp_w16, mlp_spec, sigma_lo, sigma_hi, rows_per_ray=None, train_ctx=None):
+    def forward(ctx, table_params, mlp_params, x01, copies, options):
+        table_f16, grid_spec, mlp_w16, mlp_spec = copies
+        sigma_lo, sigma_hi, rows_per_ray, train_ctx = options
         x01 = x01.float().contiguous()
         feat = hashgrid_forward(x01, (0, 1, 2), table_f16, grid_spec)
         h = mlp_forward(feat, mlp_w16, mlp_spec)
         sigma = torch.empty(h.shape[0], dtype=torch.float32, device=h.device)
         _hip.call("nvsf_exp_col", _hip.ptr(h), h.stride(0), 0, h.shape[0], _hip.ptr(sigma))
-        ctx.save_for_backward(x01, feat, sigma, mlp_w16)
-        ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray = grid_spec, mlp_spec, (float(sigma_lo), float(sigma_hi)), rows_per_ray
-        ctx.need_table, ctx.need_w = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
-        announce(ctx, train_ctx, table_params)
+        _keep_density(ctx, (x01, feat, sigma, mlp_w16), copies, (sigma_lo, sigma_hi), rows_per_ray, train_ctx, table_params)
         return sigma, h[:, 1:mlp_spec.n_out]
 
     @staticmethod
     def backward(ctx, g_sigma, g_geo):
-        grad_table, grad_w = static_density_backward(ctx, *ctx.saved_tensors, ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray,
-                                                     ctx.need_table, ctx.need_w, g_sigma, g_geo)
-        return None, grad_table, None, None, grad_w, None, None, None, None, None, None
+        return static_density_backward(ctx, *ctx.saved_tensors, ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray,
+                                       ctx.need_table, ctx.need_w, g_sigma, g_geo) + (None,) * 3
+
+
+def _keep_density(ctx, saved, copies, clamp, rows_per_ray, train_ctx, table_params):
+    """What static_density_backward reads, kept by the forward of every static density node (differentiable inputs: the table, then the
+    density weights): the saved tensors (x01, feat, sigma, mlp_w16 first), the specs, trunc_exp's clamp and the sink contract."""
+    ctx.save_for_backward(*saved)
+    ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray = copies[1], copies[3], (float(clamp[0]), float(clamp[1])), rows_per_ray
+    ctx.need_table, ctx.need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    announce(ctx, train_ctx, table_params)
 
 
 def density_mlp_backward(x_rows, w16, spec, sigma, g_sigma, g_geo, g_geo_b, clamp, need_grad_x, grad_x_blocks=0):
@@ -882,22 +885,30 @@ def _uniform_ray_args(rays_o, rays_d, nears, fars, T, noise, aabb_host, bound, t
             _hip.host_f32(aabb_host), float(bound), N, T, _hip.ptr(table_f16), spec.L, spec.F, spec.h_scales, spec.h_res, spec.h_offsets)
 
 
+def _feature_planes(N, T, dev, sliced):
+    """The encoded features between the two launches of the level-sliced form: 8 planes of 8 bytes per sample (None: one-launch form)."""
+    return torch.empty(16, N * T, dtype=torch.int32, device=dev) if sliced else None
+
+
+def _uniform_outputs(N, T, C, dev, *names):
+    """Uninitialised output buffers of the uniform-sampling entry points, by name: per ray (z_vals ... image) and per sample (M = N T)."""
+    M = N * T
+    shape = {"z_vals": (N, T), "weights": (N, T), "ws": (N,), "depth": (N,), "image": (N, C), "x01": (M, 3), "sigma": (M,), "rgbs": (M, C),
+             "h32": (M, 16), "feat": (M, 32), "geo16": (M, 16)}
+    # (sizes unpacked: torch.empty parses a shape tuple 0.7 us slower than separate sizes, and a training step allocates twenty of these)
+    return [torch.empty(*shape[n], dtype=torch.float16 if n in ("feat", "geo16") else torch.float32, device=dev) for n in names]
+
+
 def density_uniform_train_forward(rays_o, rays_d, nears, fars, T, aabb_host, bound, noise, table_f16, grid_spec, mlp_w16, sliced):
     """nvsf_field_density_uniform_train_fwd: rays -> z_vals [N, T], sigma [N T], geo16 [N T, 16] fp16 and what the backward reads:
     normalised positions x01 [N T, 3], feature rows [N T, 32] fp16, MLP outputs h32 [N T, 16] fp32.  `sliced`: the level-sliced
     (XCD-aware) encode pass + streaming MLP pass instead of the one-launch gather form; same values bit for bit."""
     N, dev = rays_o.shape[0], rays_o.device
-    M = N * T
-    z_vals = torch.empty(N, T, dtype=torch.float32, device=dev)
-    sigma = torch.empty(M, dtype=torch.float32, device=dev)
-    geo16 = torch.empty(M, 16, dtype=torch.float16, device=dev)
-    x01 = torch.empty(M, 3, dtype=torch.float32, device=dev)
-    feat = torch.empty(M, 32, dtype=torch.float16, device=dev)
-    h32 = torch.empty(M, 16, dtype=torch.float32, device=dev)
-    planes = torch.empty(16, M, dtype=torch.int32, device=dev) if sliced else None  # 8 planes of 8 bytes per sample
+    out = _uniform_outputs(N, T, 0, dev, "z_vals", "sigma", "geo16", "x01", "feat", "h32")
+    planes = _feature_planes(N, T, dev, sliced)
     _hip.call("nvsf_field_density_uniform_train_fwd", *_uniform_ray_args(rays_o, rays_d, nears, fars, T, noise, aabb_host, bound, table_f16, grid_spec),
-              _hip.ptr(mlp_w16), _hip.ptr(z_vals), _hip.ptr(sigma), _hip.ptr(geo16), _hip.ptr(x01), _hip.ptr(feat), _hip.ptr(h32), _hip.ptr(planes))
-    return z_vals, sigma, geo16, x01, feat, h32
+              _hip.ptr(mlp_w16), *map(_hip.ptr, out), _hip.ptr(planes))
+    return tuple(out)
 
 
 class DensityRaysFn(Function):
@@ -908,25 +919,23 @@ class DensityRaysFn(Function):
     unit-cube normalisation (two torch passes over [M, 3]), the hash-grid encoder, the density MLP and the exponential as seven:
     sample positions are formed in registers, the encoded features go from the gathers into the MFMA operand, and what the
     backward needs (positions, feature rows, outputs) is written once.  Same values as the chain (same kernels' arithmetic:
-    tests/test_train_step_gpu.py); the backward is DensityFn's."""
+    tests/test_train_step_gpu.py); the backward is DensityFn's.
+    `rays` = (rays_o, rays_d, nears, fars, T, aabb_host, bound, noise), `copies` = (table_f16, grid_spec, mlp_w16, mlp_spec),
+    `options` = (sigma_lo, sigma_hi, sliced, train_ctx)."""
 
     @staticmethod
-    def forward(ctx, rays_o, rays_d, nears, fars, T, aabb_host, bound, noise, table_params, table_f16, grid_spec, mlp_params, mlp_w16,
-                mlp_spec, sigma_lo, sigma_hi, sliced, train_ctx=None):
-        z_vals, sigma, geo16, x01, feat, h32 = density_uniform_train_forward(rays_o, rays_d, nears, fars, T, aabb_host, bound, noise, table_f16,
-                                                                             grid_spec, mlp_w16, sliced)
-        ctx.save_for_backward(x01, feat, sigma, mlp_w16)
-        ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray = grid_spec, mlp_spec, (float(sigma_lo), float(sigma_hi)), T
-        ctx.need_table, ctx.need_w = ctx.needs_input_grad[8], ctx.needs_input_grad[11]
-        announce(ctx, train_ctx, table_params)
+    def forward(ctx, table_params, mlp_params, rays, copies, options):
+        table_f16, grid_spec, mlp_w16, mlp_spec = copies
+        sigma_lo, sigma_hi, sliced, train_ctx = options
+        z_vals, sigma, geo16, x01, feat, h32 = density_uniform_train_forward(*rays, table_f16, grid_spec, mlp_w16, sliced)
+        _keep_density(ctx, (x01, feat, sigma, mlp_w16), copies, (sigma_lo, sigma_hi), rays[4], train_ctx, table_params)
         ctx.mark_non_differentiable(z_vals, geo16)
         return z_vals, sigma, h32[:, 1:mlp_spec.n_out], geo16
 
     @staticmethod
     def backward(ctx, _g_z, g_sigma, g_geo, _g_geo16):
-        grad_table, grad_w = static_density_backward(ctx, *ctx.saved_tensors, ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray,
-                                                     ctx.need_table, ctx.need_w, g_sigma, g_geo)
-        return (None,) * 8 + (grad_table, None, None, grad_w, None, None, None, None, None, None)
+        return static_density_backward(ctx, *ctx.saved_tensors, ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray,
+                                       ctx.need_table, ctx.need_w, g_sigma, g_geo) + (None,) * 3
 
 
 def render_uniform_train_forward(rays_o, rays_d, nears, fars, T, aabb_host, bound, noise, table_f16, grid_spec, sigma_w16, lidar, head_a_w16,
@@ -935,19 +944,14 @@ def render_uniform_train_forward(rays_o, rays_d, nears, fars, T, aabb_host, boun
     render reads: x01 [M, 3], feature rows [M, 32] fp16, geo16 [M, 16] fp16, sigma [M], masked per-sample colours [M, C].  `sliced`: the
     level-sliced encode pass + streaming tail instead of the one-launch gather form; same values bit for bit."""
     N, dev = rays_o.shape[0], rays_o.device
-    M, C = N * T, (2 if lidar else 3)
-    f32 = dict(dtype=torch.float32, device=dev)
-    z_vals, weights = torch.empty(N, T, **f32), torch.empty(N, T, **f32)
-    ws, depth, image = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(N, C, **f32)
-    x01, sigma, rgbs = torch.empty(M, 3, **f32), torch.empty(M, **f32), torch.empty(M, C, **f32)
-    feat = torch.empty(M, 32, dtype=torch.float16, device=dev)
-    geo16 = torch.empty(M, 16, dtype=torch.float16, device=dev)
-    planes = torch.empty(16, M, dtype=torch.int32, device=dev) if sliced else None  # 8 planes of 8 bytes per sample
+    z_vals, weights, ws, depth, image, x01, sigma, rgbs, feat, geo16 = _uniform_outputs(
+        N, T, 2 if lidar else 3, dev, "z_vals", "weights", "ws", "depth", "image", "x01", "sigma", "rgbs", "feat", "geo16")
+    out = (z_vals, weights, ws, depth, image, x01, feat, geo16, sigma, rgbs)  # the entry point's order
+    planes = _feature_planes(N, T, dev, sliced)
     _hip.call("nvsf_render_uniform_train_fwd", *_uniform_ray_args(rays_o, rays_d, nears, fars, T, noise, aabb_host, bound, table_f16, grid_spec),
               _hip.ptr(sigma_w16), 1 if lidar else 0, _hip.ptr(head_a_w16), _hip.ptr(head_b_w16), float(k_scale), float(w_thresh),
-              _hip.host_f32(bg_host) if bg_host is not None else None, _hip.ptr(planes), _hip.ptr(z_vals), _hip.ptr(weights), _hip.ptr(ws),
-              _hip.ptr(depth), _hip.ptr(image), _hip.ptr(x01), _hip.ptr(feat), _hip.ptr(geo16), _hip.ptr(sigma), _hip.ptr(rgbs))
-    return z_vals, weights, ws, depth, image, x01, feat, geo16, sigma, rgbs
+              _hip.host_f32(bg_host) if bg_host is not None else None, _hip.ptr(planes), *map(_hip.ptr, out))
+    return tuple(out)
 
 
 class RenderRaysFn(Function):
@@ -962,23 +966,21 @@ class RenderRaysFn(Function):
     to nine launches that write and re-read the [M, 16] network outputs, the per-sample logits and the mask: 1.0 against 0.4 ms of
     device time for a LiDAR batch of 4096 x 768.  Backward = the chain's backward kernels in the chain's order: image -> sigmoid ->
     heads (fused data + weight gradients on shared-prefix rows) -> compositor -> density MLP -> table scatter (static_density_backward:
-    side stream, gradient sink, level-major hand-over -- unchanged)."""
+    side stream, gradient sink, level-major hand-over -- unchanged).
+    `rays` as for DensityRaysFn, `copies` = (table_f16, grid_spec, sigma_w16, sigma_spec, head_a_w16, head_b_w16, head_spec, enc_ray [N, n_enc]
+    fp16), `options` = (n_enc, lidar, k_scale, bg_host, w_thresh, sigma_lo, sigma_hi, sliced, train_ctx)."""
 
     @staticmethod
-    def forward(ctx, rays_o, rays_d, nears, fars, T, aabb_host, bound, noise, table_params, table_f16, grid_spec, sigma_params, sigma_w16,
-                sigma_spec, head_a_params, head_a_w16, head_b_params, head_b_w16, head_spec, enc_ray, n_enc, lidar, k_scale, bg_host, w_thresh,
-                sigma_lo, sigma_hi, sliced, train_ctx):
-        N, C = rays_o.shape[0], (2 if lidar else 3)
+    def forward(ctx, table_params, sigma_params, head_a_params, head_b_params, rays, copies, options):
+        table_f16, grid_spec, sigma_w16, sigma_spec, head_a_w16, head_b_w16, head_spec, enc_ray = copies
+        n_enc, lidar, k_scale, bg_host, w_thresh, sigma_lo, sigma_hi, sliced, train_ctx = options
+        N, T, C, nears, fars = rays[0].shape[0], rays[4], (2 if lidar else 3), rays[2], rays[3]
         z_vals, weights, ws, depth, image, x01, feat, geo16, sigma, rgbs = render_uniform_train_forward(
-            rays_o, rays_d, nears, fars, T, aabb_host, bound, noise, table_f16, grid_spec, sigma_w16, lidar, head_a_w16, head_b_w16, k_scale, bg_host,
-            w_thresh, sliced)
-        ctx.save_for_backward(x01, feat, sigma, sigma_w16, geo16, rgbs, weights, z_vals, nears, fars, head_a_w16, head_b_w16, enc_ray)
+            *rays, table_f16, grid_spec, sigma_w16, lidar, head_a_w16, head_b_w16, k_scale, bg_host, w_thresh, sliced)
+        _keep_density(ctx, (x01, feat, sigma, sigma_w16, geo16, rgbs, weights, z_vals, nears, fars, head_a_w16, head_b_w16, enc_ray), copies,
+                      (sigma_lo, sigma_hi), T, train_ctx, table_params)
         ctx.dims = (N, T, C, int(n_enc), bool(lidar), float(k_scale), None if bg_host is None or lidar else tuple(float(v) for v in bg_host))
-        ctx.grid_spec, ctx.mlp_spec, ctx.head_spec, ctx.clamp = grid_spec, sigma_spec, head_spec, (float(sigma_lo), float(sigma_hi))
-        ctx.rows_per_ray = T
-        ctx.need_table, ctx.need_w = ctx.needs_input_grad[8], ctx.needs_input_grad[11]
-        ctx.need_heads = (ctx.needs_input_grad[14], ctx.needs_input_grad[16])
-        announce(ctx, train_ctx, table_params)
+        ctx.head_spec, ctx.need_heads = head_spec, ctx.needs_input_grad[2:4]
         ctx.mark_non_differentiable(z_vals)
         return z_vals, weights, ws, depth, image
 
@@ -1028,14 +1030,9 @@ class RenderRaysFn(Function):
         _hip.call("nvsf_composite_uniform_weights_bwd", _hip.ptr(sigma), _hip.ptr(z_vals), _hip.ptr(nears), _hip.ptr(fars), _hip.ptr(g_w), _hip.ptr(g_ws),
                   _hip.ptr(g_depth), N, T, k_scale, _hip.ptr(g_sigma))
         # ---- density MLP + table scatter: DensityFn's backward on what this node saved
-        out = [None] * 29
-        out[8], out[11] = static_density_backward(ctx, x01, feat, sigma, sigma_w16, ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray,
-                                                  ctx.need_table, ctx.need_w, g_sigma.view(-1), grad_geo, grad_geo_b)
-        if ctx.need_heads[0]:
-            out[14] = gw_a
-        if lidar and ctx.need_heads[1]:
-            out[16] = gw_b
-        return tuple(out)
+        grads = static_density_backward(ctx, x01, feat, sigma, sigma_w16, ctx.grid_spec, ctx.mlp_spec, ctx.clamp, ctx.rows_per_ray,
+                                        ctx.need_table, ctx.need_w, g_sigma.view(-1), grad_geo, grad_geo_b)
+        return grads + (gw_a if ctx.need_heads[0] else None, gw_b if lidar and ctx.need_heads[1] else None) + (None,) * 3
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1472,10 +1469,8 @@ def density_uniform(rays_o, rays_d, nears, fars, T, aabb_host, bound, table_f16,
     if _buffers is not None:  # (z_vals, sigmas, geo, feat) of an earlier call: per-pass timing in bench.py
         z_vals, sigmas, geo, feat = _buffers
     else:
-        z_vals = torch.empty(N, T, dtype=torch.float32, device=dev)
-        sigmas = torch.empty(N, T, dtype=torch.float32, device=dev)
-        geo = torch.empty(N, T, 16, dtype=torch.float16, device=dev)
-        feat = torch.empty(16, N * T, dtype=torch.int32, device=dev) if sliced else None  # 8 planes of 8 bytes per sample
+        z_vals, sigmas, geo = _uniform_outputs(N, T, 0, dev, "z_vals", "sigma", "geo16")
+        sigmas, geo, feat = sigmas.view(N, T), geo.view(N, T, 16), _feature_planes(N, T, dev, sliced)
     args = (*_uniform_ray_args(rays_o, rays_d, nears, fars, T, noise, aabb_host, bound, table_f16, spec), _hip.ptr(sigma_weights_f16),
             _hip.ptr(z_vals), _hip.ptr(sigmas), _hip.ptr(geo))
     if sliced:
@@ -1510,12 +1505,8 @@ def render_uniform(rays_o, rays_d, nears, fars, T, aabb_host, bound, table_f16, 
     if _buffers is not None:
         z_vals, weights, ws, depth, image, feat = _buffers
     else:
-        z_vals = torch.empty(N, T, dtype=torch.float32, device=dev)
-        weights = torch.empty(N, T, dtype=torch.float32, device=dev)
-        ws = torch.empty(N, dtype=torch.float32, device=dev)
-        depth = torch.empty(N, dtype=torch.float32, device=dev)
-        image = torch.empty(N, 2 if lidar else 3, dtype=torch.float32, device=dev)
-        feat = torch.empty(16, N * T, dtype=torch.int32, device=dev) if sliced else None  # 8 planes of 8 bytes per sample
+        z_vals, weights, ws, depth, image = _uniform_outputs(N, T, 2 if lidar else 3, dev, "z_vals", "weights", "ws", "depth", "image")
+        feat = _feature_planes(N, T, dev, sliced)
     if sliced and _stage != "tail":
         _hip.call("nvsf_field_density_uniform_sliced_fwd", *lead, _hip.ptr(sigma_weights_f16), _hip.ptr(z_vals), _hip.ptr(weights),
                   _hip.ptr(weights), _hip.ptr(feat), 1)  # passes = 1: encode only (the sigma / geo arguments are not touched)

@@ -55,33 +55,40 @@ class NeRFNetworkStatic(NeRFRenderer):
     # ---- operator path (signatures of network_dynamic.py:213, :290) ---------------------------------
     def density(self, x, t=None, cal_lidar_color=False, **kwargs):
         x = (x + self.bound) / (2 * self.bound)
-        enc = self.hash_encoder_lidar if cal_lidar_color else self.hash_encoder_camera
-        net = self.sigma_net
+        m = self._modality(cal_lidar_color)
+        enc, net = m.grid, m.net
         want_dx = x.requires_grad and torch.is_grad_enabled()  # d sigma / d x: the operator chain below carries it (ops.HashGridFn), DensityFn does not
         if (x.is_cuda and x.dim() == 2 and enc.spec.D == 3 and net.spec.n_hidden <= 2 and net.spec.hidden == 64
                 and net.spec.out_cols == 16 and testing.get("density_fn") == "fused" and not want_dx):
             # one autograd node for encode -> MLP -> trunc_exp / slice (ops.DensityFn): same forward kernels, leaner backward
-            sigma, geo = ops.DensityFn.apply(x, enc.params, enc.table_f16(), enc.spec, net.params, net.weights_f16(), net.spec,
-                                             activation._LO, activation._HI, ops.rows_hint(self), ops.train_context(self))
+            sigma, geo = ops.DensityFn.apply(enc.params, net.params, x, self._copies(m),
+                                             (activation._LO, activation._HI, ops.rows_hint(self), ops.train_context(self)))
             return {"sigma": sigma, "geo_feat": geo}
         h = net(enc(x))
         return {"sigma": trunc_exp(h[..., 0]), "geo_feat": h[..., 1:]}
+
+    @staticmethod
+    def _copies(m):
+        """The fp16 copies and specs of a modality's grid and density network, as the density nodes take them."""
+        return m.grid.table_f16(), m.grid.spec, m.net.weights_f16(), m.net.spec
+
+    def _prefer_sliced(self, m, N, T, coherent=False, whole_node=False):
+        """Whether a batch of N rays x T samples takes the level-sliced form of the fused kernels (ops.prefer_sliced).  `whole_node`:
+        for ops.RenderRaysFn, whose streaming tail walks 32 samples at a time."""
+        sliced = ops.prefer_sliced(m.grid.spec, N, T, m.ray_length, float(self.bound), coherent=coherent)
+        return sliced and T % 32 == 0 if whole_node else sliced
 
     def density_from_rays(self, rays_o, rays_d, nears, fars, T, noise, cal_lidar_color, **kwargs):
         """Training forward from the rays (NeRFRenderer.run asks for it when gradients are recorded): sampler + unit-cube
         normalisation + hash grid + density MLP + trunc_exp as ONE autograd node and one launch (ops.DensityRaysFn; two launches in
         the level-sliced form, chosen as for the no-grad render).  Returns None where the fused kernels are not built (the caller
         then runs the operator chain through `density`)."""
-        enc = self.hash_encoder_lidar if cal_lidar_color else self.hash_encoder_camera
-        net = self.sigma_net
-        if not (self.fused_train_forward and rays_o.is_cuda and ops.render_uniform_eligible(enc.spec, rays_o.shape[0] * T) and net.spec.n_hidden == 1
-                and net.spec.hidden == 64 and net.spec.in_cols == 32 and net.spec.out_cols == 16):
+        m, N = self._modality(cal_lidar_color), rays_o.shape[0]
+        if not (self.fused_train_forward and rays_o.is_cuda and ops.render_uniform_eligible(m.grid.spec, N * T) and m.density_from_rays_built()):
             return None
-        ray_length = float(self.lidar_max_depth - self.min_near_lidar) if cal_lidar_color else 2.0 * float(self.bound)
-        sliced = ops.prefer_sliced(enc.spec, rays_o.shape[0], T, ray_length, float(self.bound))
-        z_vals, sigma, geo, geo16 = ops.DensityRaysFn.apply(rays_o, rays_d, nears, fars, int(T), self._aabb_host, float(self.bound), noise,
-                                                            enc.params, enc.table_f16(), enc.spec, net.params, net.weights_f16(), net.spec,
-                                                            activation._LO, activation._HI, bool(sliced), ops.train_context(self))
+        z_vals, sigma, geo, geo16 = ops.DensityRaysFn.apply(
+            m.grid.params, m.net.params, (rays_o, rays_d, nears, fars, int(T), self._aabb_host, float(self.bound), noise), self._copies(m),
+            (activation._LO, activation._HI, bool(self._prefer_sliced(m, N, T)), ops.train_context(self)))
         return {"z_vals": z_vals, "sigma": sigma, "geo_feat": geo, "geo16": geo16}
 
     fused_train_forward = True  # False (tests): NeRFRenderer.run takes the operator chain (uniform_samples -> density)
@@ -91,29 +98,20 @@ class NeRFNetworkStatic(NeRFRenderer):
         """The whole training forward of a ray batch as ONE autograd node (ops.RenderRaysFn: the evaluation render's kernels in their
         TRAIN form; the chain's backward kernels).  Returns (z_vals, weights, weights_sum, depth, image) or None where the fused
         kernels are not built (NeRFRenderer.run then composes DensityRaysFn / the operator chain)."""
-        enc = self.hash_encoder_lidar if cal_lidar_color else self.hash_encoder_camera
-        net = self.sigma_net
-        if cal_lidar_color:
-            head_a, head_b, venc = self.raydrop_net, self.intensity_net, self.view_encoder_lidar
-        else:
-            head_a, head_b, venc = self.color_net, None, self.view_encoder_camera
-        hs = head_a.spec
-        n_enc = venc.n_output_dims
-        if not (self.fused_train_forward and self.fused_train_render and rays_o.is_cuda and ops.render_uniform_eligible(enc.spec, rays_o.shape[0] * T)
-                and (T % 32 == 0 or not ops.sliced_only(enc.spec)) and net.spec.n_hidden == 1 and net.spec.hidden == 64 and net.spec.in_cols == 32 and net.spec.out_cols == 16
-                and hs.n_hidden == 2 and hs.n_in == n_enc + 15 and n_enc % 8 == 0 and T % 16 == 0
-                and (head_b is None or (head_b.spec.n_in == hs.n_in and head_b.spec.n_out == hs.n_out and head_b.spec.n_hidden == 2))):
+        m, N = self._modality(cal_lidar_color), rays_o.shape[0]
+        venc, head_a, head_b = m.venc, m.head_a, m.head_b
+        if not (self.fused_train_forward and self.fused_train_render and rays_o.is_cuda and ops.render_uniform_eligible(m.grid.spec, N * T)
+                and (T % 32 == 0 or not ops.sliced_only(m.grid.spec)) and m.render_node_built(T)):
             return None
-        ray_length = float(self.lidar_max_depth - self.min_near_lidar) if cal_lidar_color else 2.0 * float(self.bound)
-        sliced = ops.prefer_sliced(enc.spec, rays_o.shape[0], T, ray_length, float(self.bound)) and T % 32 == 0
         with torch.no_grad():  # per-ray direction encoding: the prefix rows the heads' backward reads
             d01 = (rays_d + 1) / 2
             enc_ray = ops.freq_encode(d01, venc.n_frequencies) if venc.otype == "Frequency" else ops.sh4_encode(d01)
-        return ops.RenderRaysFn.apply(rays_o, rays_d, nears, fars, int(T), self._aabb_host, float(self.bound), noise, enc.params, enc.table_f16(),
-                                      enc.spec, net.params, net.weights_f16(), net.spec, head_a.params, head_a.weights_f16(),
-                                      None if head_b is None else head_b.params, None if head_b is None else head_b.weights_f16(), hs, enc_ray,
-                                      n_enc, bool(cal_lidar_color), self._k_scale(), None if cal_lidar_color else bg_host, ops.W_THRESH,
-                                      activation._LO, activation._HI, bool(sliced), ops.train_context(self))
+        return ops.RenderRaysFn.apply(
+            m.grid.params, m.net.params, head_a.params, None if head_b is None else head_b.params,
+            (rays_o, rays_d, nears, fars, int(T), self._aabb_host, float(self.bound), noise),
+            self._copies(m) + (head_a.weights_f16(), None if head_b is None else head_b.weights_f16(), head_a.spec, enc_ray),
+            (venc.n_output_dims, bool(cal_lidar_color), self._k_scale(), None if cal_lidar_color else bg_host, ops.W_THRESH, activation._LO,
+             activation._HI, bool(self._prefer_sliced(m, N, T, whole_node=True)), ops.train_context(self)))
 
     def color(self, x, d, cal_lidar_color=False, mask=None, geo_feat=None, **kwargs):
         ray_dirs = kwargs.get("ray_dirs")  # [N, 3] from NeRFRenderer.run: d is these rows, each repeated for its ray's samples
@@ -160,39 +158,31 @@ class NeRFNetworkStatic(NeRFRenderer):
 
     # ---- fused path ------------------------------------------------------------------------------------
     def fused_uniform_render(self, rays_o, rays_d, nears, fars, T, aabb, noise, cal_lidar_color, bg_host, **kwargs):
-        enc = self.hash_encoder_lidar if cal_lidar_color else self.hash_encoder_camera
+        m, N = self._modality(cal_lidar_color), rays_o.shape[0]
+        enc, bg = m.grid, (None if cal_lidar_color else bg_host)
         aabb_host = self._aabb_host  # host copy of the (constant) box: no device->host read on the hot path
-        # host-side estimate of far - near: exact for LiDAR (constant range), the box side for camera rays (AABB exit)
-        ray_length = float(self.lidar_max_depth - self.min_near_lidar) if cal_lidar_color else 2.0 * float(self.bound)
-        sliced = ops.prefer_sliced(enc.spec, rays_o.shape[0], T, ray_length, float(self.bound), coherent=bool(kwargs.get("rays_in_image_order", False)))
-        if ops.render_uniform_eligible(enc.spec, rays_o.shape[0] * T):
+        sliced = self._prefer_sliced(m, N, T, coherent=bool(kwargs.get("rays_in_image_order", False)))
+        if ops.render_uniform_eligible(enc.spec, N * T):
             # one launch per batch (plus the encode pass of the level-sliced path): sigma / geo never reach HBM
-            if cal_lidar_color:
-                head_a, head_b = self.raydrop_net.weights_f16(), self.intensity_net.weights_f16()
-            else:
-                head_a, head_b = self.color_net.weights_f16(), None
+            head_a, head_b = self._heads_f16(m)
             return ops.render_uniform(rays_o, rays_d, nears, fars, T, aabb_host, float(self.bound), enc.table_f16(), enc.spec,
-                                      self.sigma_net.weights_f16(), cal_lidar_color, head_a, head_b, self._k_scale(),
-                                      None if cal_lidar_color else bg_host, noise, sliced=sliced)
+                                      m.net.weights_f16(), cal_lidar_color, head_a, head_b, self._k_scale(), bg, noise, sliced=sliced)
         z_vals, sigmas, geo = ops.density_uniform(rays_o, rays_d, nears, fars, T, aabb_host, float(self.bound), enc.table_f16(),
-                                                  enc.spec, self.sigma_net.weights_f16(), noise, sliced=sliced)
+                                                  enc.spec, m.net.weights_f16(), noise, sliced=sliced)
         weights, weights_sum, depth = ops.CompositeWeightsFn.apply(sigmas, z_vals, nears, fars, self._k_scale())
-        if cal_lidar_color:
-            image = ops.heads_uniform(weights, geo, rays_d, weights_sum, True, self.raydrop_net.weights_f16(),
-                                      self.intensity_net.weights_f16(), None)
-        else:
-            image = ops.heads_uniform(weights, geo, rays_d, weights_sum, False, self.color_net.weights_f16(), None, bg_host)
+        image = ops.heads_uniform(weights, geo, rays_d, weights_sum, bool(cal_lidar_color), *self._heads_f16(m), bg)
         return z_vals, weights, weights_sum, depth, image
+
+    @staticmethod
+    def _heads_f16(m):
+        return m.head_a.weights_f16(), (None if m.head_b is None else m.head_b.weights_f16())
 
     def fused_occupancy_render(self, rays_o, rays_d, nears, fars, cal_lidar_color, dt_gamma, max_steps, T_thresh, bg_host):
         """Evaluation-mode occupancy render in one launch (NeRFRenderer.run_cuda hands over here when it can)."""
-        enc = self.hash_encoder_lidar if cal_lidar_color else self.hash_encoder_camera
-        if cal_lidar_color:
-            head_a, head_b = self.raydrop_net.weights_f16(), self.intensity_net.weights_f16()
-        else:
-            head_a, head_b = self.color_net.weights_f16(), None
+        m = self._modality(cal_lidar_color)
+        head_a, head_b = self._heads_f16(m)
         return ops.render_occupancy(rays_o, rays_d, nears, fars, self.density_bitfield, float(self.bound), dt_gamma, max_steps,
-                                    self.cascade, self.grid_size, enc.table_f16(), enc.spec, self.sigma_net.weights_f16(),
+                                    self.cascade, self.grid_size, m.grid.table_f16(), m.grid.spec, m.net.weights_f16(),
                                     cal_lidar_color, head_a, head_b, float(self.density_scale), T_thresh, bg_host)
 
     def get_params(self, lr):

@@ -21,6 +21,7 @@ reference -- on the operator chain: nvsf_resample_merge draws `upsample_steps` m
 merges them into the row, nvsf_merge_rows carries the field outputs into that order.
 """
 import math
+from typing import Any, NamedTuple
 
 import torch
 import torch.nn as nn
@@ -40,6 +41,42 @@ def sample_pdf(bins, weights, n_samples, det=False, u=None):
     elif int(u.shape[-1]) != int(n_samples):
         raise ValueError(f"u has {int(u.shape[-1])} draws per ray, n_samples is {int(n_samples)}")
     return ops.sample_pdf(bins, weights, u)
+
+
+class Modality(NamedTuple):
+    """What a field network evaluates one modality (LiDAR / camera) with -- NeRFRenderer._modality."""
+    grid: Any          # the modality's grid encoder
+    net: Any           # the density network
+    head_a: Any        # ray-drop (LiDAR) / colour head
+    head_b: Any        # intensity head (LiDAR), None for the camera
+    venc: Any          # direction encoder
+    ray_length: float  # host-side estimate of far - near: exact for LiDAR (constant range), the box side for camera rays (AABB exit)
+
+    def density_from_rays_built(self):
+        """The fused training forward of the density (ops.DensityRaysFn) is built for this density network's shape."""
+        s = self.net.spec
+        return s.n_hidden == 1 and s.hidden == 64 and s.in_cols == 32 and s.out_cols == 16
+
+    def render_node_built(self, T):
+        """... and the whole render of T samples per ray as one node (ops.RenderRaysFn) for these heads as well."""
+        hs, n_enc, b = self.head_a.spec, self.venc.n_output_dims, self.head_b
+        return (self.density_from_rays_built() and hs.n_hidden == 2 and hs.n_in == n_enc + 15 and n_enc % 8 == 0 and T % 16 == 0
+                and (b is None or (b.spec.n_in == hs.n_in and b.spec.n_out == hs.n_out and b.spec.n_hidden == 2)))
+
+
+def bg_host(bg_color, out_dim, lidar):
+    """The background colour (None = white, a number, a 1- or out_dim-element tensor, or one row per ray) as the fused kernels take it:
+    -> (out_dim host floats | None, per-ray rows [N, out_dim] | None).  LiDAR renders have no background: (None, None)."""
+    if lidar:
+        return None, None
+    if bg_color is None:
+        return [1.0] * out_dim, None
+    if not torch.is_tensor(bg_color):
+        return [float(bg_color)] * out_dim, None
+    if bg_color.numel() > out_dim:
+        return None, bg_color.reshape(-1, out_dim)
+    flat = bg_color.reshape(-1)
+    return [float(v) for v in (flat.expand(out_dim) if flat.numel() == 1 else flat).tolist()], None
 
 
 class NeRFRenderer(nn.Module):
@@ -164,17 +201,8 @@ class NeRFRenderer(nn.Module):
         elif (not perturb and not torch.is_grad_enabled() and hasattr(self, "fused_occupancy_render")
               and (bg_color is None or not torch.is_tensor(bg_color) or bg_color.numel() <= 3) and kwargs.get("fused", True)):
             # one launch for the whole survivor loop (static hash fields): nvsf_render_occupancy_fwd
-            if cal_lidar_color:
-                bg_host = None
-            elif bg_color is None:
-                bg_host = [1.0, 1.0, 1.0]
-            elif torch.is_tensor(bg_color):
-                bg_host = [float(v) for v in bg_color.reshape(-1).expand(3).tolist()] if bg_color.numel() == 1 \
-                    else [float(v) for v in bg_color.reshape(-1).tolist()]
-            else:
-                bg_host = [float(bg_color)] * 3
             weights_sum, depth, image = self.fused_occupancy_render(rays_o, rays_d, nears, fars, cal_lidar_color, dt_gamma, max_steps,
-                                                                    T_thresh, bg_host)
+                                                                    T_thresh, bg_host(bg_color, 3, cal_lidar_color)[0])
             suffix = "_lidar" if cal_lidar_color else ""
             return {"depth" + suffix: depth.view(*prefix), "image" + suffix: image.view(*prefix, out_dim), "weights_sum" + suffix: weights_sum}
         else:
@@ -227,6 +255,13 @@ class NeRFRenderer(nn.Module):
     def _k_scale(self):
         # alpha = 1 - exp(-delta * density_scale * sigma), doubled in the exponent for an active sensor (:185-189)
         return float(self.density_scale) * (2.0 if self.active_sensor else 1.0)
+
+    def _modality(self, cal_lidar_color):
+        """The sub-modules a field network (NeRFNetworkStatic, NeRFNetwork: same attribute names) evaluates LiDAR / camera samples with."""
+        if cal_lidar_color:
+            return Modality(self.hash_encoder_lidar, self.sigma_net, self.raydrop_net, self.intensity_net, self.view_encoder_lidar,
+                            float(self.lidar_max_depth - self.min_near_lidar))
+        return Modality(self.hash_encoder_camera, self.sigma_net, self.color_net, None, self.view_encoder_camera, 2.0 * float(self.bound))
 
     def _near_far(self, rays_o, rays_d, cal_lidar_color, aabb):
         N = rays_o.shape[0]
@@ -287,56 +322,45 @@ class NeRFRenderer(nn.Module):
             U = int(upsample_steps)
             u = torch.rand(N, U, dtype=torch.float32, device=rays_o.device) if perturb else ops.stratified_u(U, rays_o.device)
 
-        per_ray_bg = None
-        bg_host = None
-        if not cal_lidar_color:
-            if self.bg_radius > 0:
-                sph = raymarching.sph_from_ray(rays_o, rays_d, self.bg_radius)
-                per_ray_bg = self.background(sph, rays_d)
-            elif bg_color is None:
-                bg_host = [1.0] * self.out_dim
-            elif torch.is_tensor(bg_color) and bg_color.numel() > self.out_dim:
-                per_ray_bg = bg_color.reshape(-1, self.out_dim).to(rays_o.device, torch.float32)
-            elif torch.is_tensor(bg_color):
-                bg_host = [float(v) for v in bg_color.reshape(-1).expand(self.out_dim).tolist()] if bg_color.numel() == 1 \
-                    else [float(v) for v in bg_color.reshape(-1).tolist()]
-            else:
-                bg_host = [float(bg_color)] * self.out_dim
-
-        fused = getattr(self, "fused_uniform_render", None)
-        rendered = None
-        if hierarchical:
-            rendered = self._render_hierarchical(rays_o, rays_d, nears, fars, T, U, aabb, noise, u, time, cal_lidar_color, bg_host,
-                                                 **kwargs)
-        elif fused is not None and not torch.is_grad_enabled():
-            z_vals, weights, weights_sum, depth, image = fused(rays_o, rays_d, nears, fars, T, aabb, noise, cal_lidar_color,
-                                                               bg_host, time=time, **kwargs)
+        if not cal_lidar_color and self.bg_radius > 0:
+            bg, per_ray_bg = None, self.background(raymarching.sph_from_ray(rays_o, rays_d, self.bg_radius), rays_d)
         else:
-            whole = getattr(self, "render_from_rays_train", None)
-            rendered = whole(rays_o, rays_d, nears, fars, T, noise, cal_lidar_color, bg_host, **kwargs) if whole is not None else None
+            bg, per_ray_bg = bg_host(bg_color, self.out_dim, cal_lidar_color)
+            if per_ray_bg is not None:
+                per_ray_bg = per_ray_bg.to(rays_o.device, torch.float32)
+
+        # which form renders the batch: fields offer the fused ones (network_static.py); each returns None where its kernels are not built
+        fused = getattr(self, "fused_uniform_render", None)
+        whole = getattr(self, "render_from_rays_train", None)
+        density_rays = getattr(self, "density_from_rays", None)
+        record = fused is None or torch.is_grad_enabled()
+        rendered = density_outputs = None
+        if hierarchical:
+            rendered = self._render_hierarchical(rays_o, rays_d, nears, fars, T, U, aabb, noise, u, time, cal_lidar_color, bg, **kwargs)
+        elif not record:  # three fused kernels, nothing recorded
+            rendered = fused(rays_o, rays_d, nears, fars, T, aabb, noise, cal_lidar_color, bg, time=time, **kwargs)
+        elif whole is not None and (rendered := whole(rays_o, rays_d, nears, fars, T, noise, cal_lidar_color, bg, **kwargs)) is not None:
+            pass  # training forward of a field that renders a ray batch as ONE autograd node (network_static: ops.RenderRaysFn)
+        elif density_rays is not None and (density_outputs := density_rays(rays_o, rays_d, nears, fars, T, noise, cal_lidar_color, **kwargs)) is not None:
+            # training forward of a field that samples, encodes and evaluates its density MLP in one launch (network_static):
+            # the [N, T, 3] positions and the expanded directions are never materialised; `color` gets them on request
+            z_vals = density_outputs.pop("z_vals")
+            xyz_arg = dirs_arg = None
+        else:  # the operator chain
+            z_vals, xyzs = ops.uniform_samples(rays_o, rays_d, nears, fars, T, aabb, noise)
+            with self._rows_hint().rows(T):  # rows are T consecutive samples per ray: lets the table scatters pick their form
+                density_outputs = self.density(xyzs.view(-1, 3), time, cal_lidar_color, **kwargs)
+            xyz_arg, dirs_arg = xyzs.view(-1, 3), rays_d.view(-1, 1, 3).expand(N, T, 3).reshape(-1, 3)
         if rendered is not None:
-            # training forward of a field that renders a ray batch as ONE autograd node (network_static: ops.RenderRaysFn)
             z_vals, weights, weights_sum, depth, image = rendered
-        elif fused is None or torch.is_grad_enabled():
-            density_rays = getattr(self, "density_from_rays", None)
-            density_outputs = density_rays(rays_o, rays_d, nears, fars, T, noise, cal_lidar_color, **kwargs) if density_rays is not None else None
-            if density_outputs is not None:
-                # training forward of a field that samples, encodes and evaluates its density MLP in one launch (network_static):
-                # the [N, T, 3] positions and the expanded directions are never materialised; `color` gets them on request
-                z_vals = density_outputs.pop("z_vals")
-                xyz_arg = dirs_arg = None
-            else:
-                z_vals, xyzs = ops.uniform_samples(rays_o, rays_d, nears, fars, T, aabb, noise)
-                with self._rows_hint().rows(T):  # rows are T consecutive samples per ray: lets the table scatters pick their form
-                    density_outputs = self.density(xyzs.view(-1, 3), time, cal_lidar_color, **kwargs)
-                xyz_arg, dirs_arg = xyzs.view(-1, 3), rays_d.view(-1, 1, 3).expand(N, T, 3).reshape(-1, 3)
+        else:  # the compositing tail of the last two forms
             sigma = density_outputs["sigma"].view(N, T)
             weights, weights_sum, depth = ops.CompositeWeightsFn.apply(sigma, z_vals, nears, fars, self._k_scale())
             mask = weights > ops.W_THRESH
             extra = {k: v.view(N * T, -1) for k, v in density_outputs.items() if k != "sigma"}
             # ray_dirs: the per-ray rows `dirs` repeats -- lets the heads encode each direction once (ops.heads)
             rgbs = self.color(xyz_arg, dirs_arg, cal_lidar_color=cal_lidar_color, mask=mask.reshape(-1), ray_dirs=rays_d, **extra)
-            bg_dev = ops.device_constant(bg_host, rays_o.device) if bg_host is not None else None
+            bg_dev = ops.device_constant(bg, rays_o.device) if bg is not None else None
             image = ops.CompositeImageFn.apply(weights, rgbs.view(N, T, self.out_dim), weights_sum, bg_dev)
         if per_ray_bg is not None:
             image = image + (1 - weights_sum).unsqueeze(-1) * per_ray_bg

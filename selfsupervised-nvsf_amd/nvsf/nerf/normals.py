@@ -37,8 +37,7 @@ def density_gradient(model, x, cal_lidar_color=False):
         raise _hip.NvsfHipError("density_gradient needs points on a HIP device (got a CPU tensor); there is no CPU fallback")
     if x.dim() != 2 or x.shape[1] != 3:
         raise ValueError(f"density_gradient: x must be [M, 3] (got {tuple(x.shape)})")
-    enc = model.hash_encoder_lidar if cal_lidar_color else model.hash_encoder_camera
-    net = model.sigma_net
+    enc, net = model._modality(cal_lidar_color)[:2]
     with torch.no_grad():
         x01 = ((x.float() + model.bound) / (2 * model.bound)).contiguous()  # as NeRFNetworkStatic.density normalises
         M = x01.shape[0]

@@ -601,8 +601,9 @@ def test_fused_training_forward_equals_operator_chain(dev):
     nz = torch.rand(300, 96, device=dev)
     got = {}
     for sliced in (False, True):
-        z, sg, geo, g16 = ops.DensityRaysFn.apply(o, d, nears, fars, 96, big._aabb_host, float(big.bound), nz, enc.params, enc.table_f16(), enc.spec,
-                                                  net.params, net.weights_f16(), net.spec, activation._LO, activation._HI, sliced)
+        z, sg, geo, g16 = ops.DensityRaysFn.apply(enc.params, net.params, (o, d, nears, fars, 96, big._aabb_host, float(big.bound), nz),
+                                                  (enc.table_f16(), enc.spec, net.weights_f16(), net.spec),
+                                                  (activation._LO, activation._HI, sliced, None))
         node = sg.grad_fn
         got[sliced] = (z, sg.detach(), geo.detach(), g16, [t.clone() for t in node.saved_tensors[:2]])
     for a, b in zip(got[False][:4], got[True][:4]):
