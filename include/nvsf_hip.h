@@ -454,6 +454,27 @@ int nvsf_hashgrid4d_dynamic_bwd(const float* x, uint32_t x_stride, uint32_t M, c
                                 const uint32_t* h_offsets, const float* h_time, int same_slice, const float* grad_out,
                                 void* const* h_grad_tables_f32, nvsf_stream_t stream);
 
+/* Coordinate gradient of nvsf_hashgrid4d_dynamic_fwd (no reference counterpart: the reference evaluates its hash look-ups under
+ * no_grad, network_dynamic.py:245-265).  The arguments up to same_slice are the forward's (h_tables_f16[3..5] may be NULL when
+ * same_slice).  grad_out: fp32 rows of 24 floats, go_stride >= 24 floats apart (a column slice of a wider matrix is read in place);
+ * column 8 q + l belongs to pair q, level l.  grad_x fp32 [M, gx_stride >= 3], 4-byte aligned: written, or added to when
+ * accumulate != 0.  Definition: p = x[m, 0:3] (+ offset[m, off_col : off_col + 3], the forward's fp32 add); for pair q
+ * with axes (a, b) in {(x,y), (x,z), (y,z)} and level l take pos, cell, frac and rows as the forward forms them (positions outside the
+ * unit cube stay inside the table); then in fp32
+ *   s[c][i] = lo[row(c)][i] when same_slice, else b_lo lo[row(c)][i] + b_hi hi[row(c)][i]     (corner c, feature i)
+ *   e[c]    = sum_i w_i s[c][i],    G = grad_scale * grad_out[m, 8 q + l]
+ *   acc_a  += scale_l G ((1 - frac_b) (e[10] - e[00]) + frac_b (e[11] - e[01]))
+ *   acc_b  += scale_l G ((1 - frac_a) (e[01] - e[00]) + frac_a (e[11] - e[10]))
+ * (corner pairs differenced first: a table that does not vary along an axis gives an exact 0.0f) and grad_x[m, d] is the sum over
+ * the two pairs that contain axis d and their eight levels.  The function differentiated is the piecewise-bilinear one on the
+ * forward's own cell; the fp16 rounding points of both forward regimes pass the gradient straight through, so there is no `mode`.
+ * No atomics: reruns are bit-identical.  M = 0 returns 0 and launches nothing. */
+int nvsf_hashgrid4d_dynamic_grad_x(const float* x, uint32_t x_stride, const float* offset, uint32_t off_stride, uint32_t off_col,
+                                   uint32_t M, const void* const* h_tables_f16, const float* h_scales, const uint32_t* h_res,
+                                   const uint32_t* h_offsets, const float* h_time, int same_slice, const float* grad_out,
+                                   uint32_t go_stride, float grad_scale, float* grad_x, uint32_t gx_stride, int accumulate,
+                                   nvsf_stream_t stream);
+
 /* ref: FlowField.forward front end, nvsf/nerf/models/flow_field.py:123-128 (grid_enc -> .float() -> interpT):
  * 3-D hash grid with F = 8 followed by the Lagrange reduction over the 4 feature pairs of each level.
  * h_weights4 = w0..w3 (fp32, host) -> out fp32 [M, 2L]. */

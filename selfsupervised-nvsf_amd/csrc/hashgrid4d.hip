@@ -103,6 +103,82 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic(const float* __restrict
     }
 }
 
+// Coordinate gradient of the encoder above: dL/dp of the piecewise-bilinear function k_hash_dynamic evaluates, on its own
+// cell, p = x (+ offset).  The fp16 rounding points of both forward regimes pass the gradient straight through, so one derivative serves
+// mode 0 and mode 1.  Per (pair, level) item with axes (a, b), in fp32:
+//   s[c][i] = lo[row(c)][i]  (same_slice)   or   blend_lo lo[row(c)][i] + blend_hi hi[row(c)][i];   e[c] = sum_i lag_i s[c][i]
+//   G = grad_scale grad_out[m, 8 pair + level]
+//   acc_a += scale G ((1 - frac_b) (e[10] - e[00]) + frac_b (e[11] - e[01]))
+//   acc_b += scale G ((1 - frac_a) (e[01] - e[00]) + frac_a (e[11] - e[10]))
+// The corner pairs along an axis are differenced first (as k_hashgrid_grad_x does): a table that does not vary along an axis gives an
+// exact zero.  Mapping of k_hashgrid_grad_x: lanes = 64 consecutive samples, the four waves split the 24 items, the 2 x 4 gathers of an
+// item in flight before any arithmetic, three partial sums per wave, added through LDS in wave order.  No atomics: reruns are
+// bit-identical.
+__global__ __launch_bounds__(kBlock) void k_hash_dynamic_grad_x(const float* __restrict__ x, uint32_t x_stride, const float* __restrict__ offset,
+                                                                uint32_t off_stride, uint32_t off_col, uint32_t M, PlaneSet ps,
+                                                                const float* __restrict__ grad_out, uint32_t go_stride, float grad_scale,
+                                                                float* __restrict__ grad_x, uint32_t gx_stride, int accumulate) {
+    __shared__ float part[kBlock / 64][3][64];  // [wave][axis][lane]
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform by construction: level tables, pointers and loop control in SGPRs
+    const uint32_t m = blockIdx.x * kSamplesPerBlock + lane;
+    const uint32_t mm = m < M ? m : M - 1;  // clamp: out-of-range lanes compute a valid sample and are dropped at the store
+    float p[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        p[d] = x[(size_t)mm * x_stride + d];
+        if (offset) p[d] = p[d] + offset[(size_t)mm * off_stride + off_col + d];
+    }
+    float sum[3] = {0.0f, 0.0f, 0.0f};
+    for (int item = wave; item < 3 * kPlaneLevels; item += 4) {
+        const int pl = item / kPlaneLevels, l = item - pl * kPlaneLevels;
+        const int ia = pl == 2 ? 1 : 0, ib = pl == 0 ? 1 : 2;
+        const float xy[2] = {p[ia], p[ib]};
+        const GridMeta& g = ps.meta[pl];
+        const float scale = g.scale[l];
+        const uint32_t row0 = g.offset[l], rows = g.offset[l + 1] - row0;
+        const float G = grad_scale * grad_out[(size_t)mm * go_stride + item];
+        float frac[2];
+        uint32_t cell[2];
+        grid_cell<2>(xy, scale, cell, frac);
+        float v_lo[4][kF], v_hi[4][kF];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint32_t cc[2] = {cell[0] + (uint32_t)(c & 1), cell[1] + (uint32_t)(c >> 1)};
+            const size_t row = (size_t)row0 + grid_row<2>(cc, g.res[l], rows);
+            load_feat<kF>(ps.ts.table_lo[pl], row, v_lo[c]);
+            if (!ps.ts.same_slice) load_feat<kF>(ps.ts.table_hi[pl], row, v_hi[c]);
+        }
+        float e[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float s[kF];
+#pragma unroll
+            for (int i = 0; i < kF; ++i) s[i] = ps.ts.same_slice ? v_lo[c][i] : ps.ts.blend_lo * v_lo[c][i] + ps.ts.blend_hi * v_hi[c][i];
+            e[c] = ps.ts.lag[0] * s[0];
+#pragma unroll
+            for (int i = 1; i < kF; ++i) e[c] = e[c] + ps.ts.lag[i] * s[i];
+        }
+        const float da = (1.0f - frac[1]) * (e[1] - e[0]) + frac[1] * (e[3] - e[2]);
+        const float db = (1.0f - frac[0]) * (e[2] - e[0]) + frac[0] * (e[3] - e[1]);
+        const float sg = scale * G;
+        // the axes of a pair are wave-uniform: branched on, not indexed, so that sum[] stays in registers
+        if (pl == 0) { sum[0] = sum[0] + sg * da; sum[1] = sum[1] + sg * db; }
+        else if (pl == 1) { sum[0] = sum[0] + sg * da; sum[2] = sum[2] + sg * db; }
+        else { sum[1] = sum[1] + sg * da; sum[2] = sum[2] + sg * db; }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) part[wave][d][lane] = sum[d];
+    __syncthreads();
+    if (wave == 0 && m < M) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const float v = ((part[0][d][lane] + part[1][d][lane]) + part[2][d][lane]) + part[3][d][lane];
+            float* dst = grad_x + (size_t)m * gx_stride + d;
+            *dst = accumulate ? *dst + v : v;
+        }
+    }
+}
+
 // The three space-time evaluations of one density query (network_dynamic.py:220-271) in one launch: features at (x, t) in
 // regime 0 and at the flow-warped positions (x + f1, t1), (x + f2, t2) of the neighbour frames in regime 1.  The warped
 // positions are fractions of a cell away from x at the coarse levels (and everywhere the scene is static), and the
@@ -502,6 +578,28 @@ NVSF_API int nvsf_hashgrid4d_dynamic_fwd(const float* x, uint32_t x_stride, cons
     const dim3 grid(cdiv(M, kSamplesPerBlock)), block(kBlock);
     if (mode == 0) hipLaunchKernelGGL(k_hash_dynamic<0>, grid, block, 0, stream, x, x_stride, offset, off_stride, off_col, M, ps, out);
     else hipLaunchKernelGGL(k_hash_dynamic<1>, grid, block, 0, stream, x, x_stride, offset, off_stride, off_col, M, ps, out);
+    return nvsf_launch_status();
+}
+
+// Coordinate gradient of nvsf_hashgrid4d_dynamic_fwd (same arguments up to same_slice; the derivative is the same for both modes).
+// grad_out fp32 rows of 24 floats, go_stride >= 24 floats apart (column 8 pair + level); grad_x fp32 [M, gx_stride >= 3], 4-byte aligned:
+// written, or added to when accumulate != 0.
+NVSF_API int nvsf_hashgrid4d_dynamic_grad_x(const float* x, uint32_t x_stride, const float* offset, uint32_t off_stride, uint32_t off_col,
+                                            uint32_t M, const void* const* h_tables_f16, const float* h_scales, const uint32_t* h_res,
+                                            const uint32_t* h_offsets, const float* h_time, int same_slice, const float* grad_out,
+                                            uint32_t go_stride, float grad_scale, float* grad_x, uint32_t gx_stride, int accumulate,
+                                            hipStream_t stream) {
+    if (M == 0) return NVSF_OK;
+    REQUIRE(x && h_tables_f16 && h_time && grad_out && grad_x && x_stride >= 3 && go_stride >= 3u * kPlaneLevels && gx_stride >= 3);
+    REQUIRE(!offset || off_stride >= off_col + 3);
+    REQUIRE(((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(grad_x)) & 3u) == 0);
+    PlaneSet ps;
+    fill_time_set(ps.ts, h_tables_f16, h_time, same_slice);
+    REQUIRE(time_set_ok(ps.ts, 7u));
+    const int st = fill_pair_metas(ps.meta, h_scales, h_res, h_offsets);
+    if (st != NVSF_OK) return st;
+    hipLaunchKernelGGL(k_hash_dynamic_grad_x, dim3(cdiv(M, kSamplesPerBlock)), dim3(kBlock), 0, stream, x, x_stride, offset, off_stride, off_col,
+                       M, ps, grad_out, go_stride, grad_scale, grad_x, gx_stride, accumulate);
     return nvsf_launch_status();
 }
 

@@ -66,6 +66,7 @@ SIGNATURES = {
     "nvsf_planes_multi_bwd": [_P, _U, _U, _P, _U, _U, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "nvsf_planes_bwd": [_P, _U, _P, _U, _U, _P, _I, _P, _P, _P, _P],
     "nvsf_hashgrid4d_dynamic_fwd": [_P, _U, _P, _U, _U, _U, _P, _P, _P, _P, _P, _I, _I, _P],
+    "nvsf_hashgrid4d_dynamic_grad_x": [_P, _U, _P, _U, _U, _U, _P, _P, _P, _P, _P, _I, _P, _U, _F, _P, _U, _I],
     "nvsf_hashgrid4d_dynamic3_fwd": [_P, _U, _P, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "nvsf_hashgrid4d_dynamic_bwd_scalar": [_P, _U, _U, _P, _P, _P, _P, _P],
     "nvsf_hashgrid4d_dynamic_bwd_scalar_t": [_P, _U, _U, _P, _P, _P, _P, _P],

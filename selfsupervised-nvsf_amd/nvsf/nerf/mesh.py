@@ -275,10 +275,11 @@ def export_mesh_density(model, save_path, bound_min=None, bound_max=None, xyz_re
     Bounds default to model.aabb_infer and must lie inside it (the reference asserts [-1, 1] instead, which its own defaults fail at
     bound = 2).  `time` (float or tensor) is required for the space-time NeRFNetwork -- the reference calls density without one, which
     that model cannot evaluate -- and ignored by the static network.  Returns (vertices, triangles) as written.
-    `normals` (static model only): the unit normals -grad sigma / |grad sigma| of the field at the vertices (nvsf.nerf.normals.density_gradient,
-    evaluated in chunks) are written with them and returned: (vertices, triangles, normals [V, 3] fp32)."""
-    if normals and _is_space_time(model):
-        raise NotImplementedError("export_mesh_density(normals=True): only the static hash field has a coordinate gradient")
+    `normals`: the unit normals -grad sigma / |grad sigma| of the field at the vertices (nvsf.nerf.normals.density_gradient, evaluated in
+    chunks; for the space-time model at `time`, on a HIP device only) are written with them and returned: (vertices, triangles,
+    normals [V, 3] fp32)."""
+    if normals and _is_space_time(model) and not model.aabb_infer.is_cuda:
+        raise NotImplementedError("export_mesh_density(normals=True): the space-time model's coordinate gradient has no CPU form")
     if smoothing:
         raise NotImplementedError("smoothing: mcubes.smooth (the reference's optional Laplacian-like smoothing of the field) is out of scope")
     res = _check_res(xyz_res)
@@ -319,7 +320,7 @@ def export_mesh_density(model, save_path, bound_min=None, bound_max=None, xyz_re
     vertex_normals = np.empty((vertices.shape[0], 3), np.float32)
     for i in range(0, vertices.shape[0], _NORMAL_CHUNK):
         pts = torch.from_numpy(vertices[i:i + _NORMAL_CHUNK].astype(np.float32)).to(dev)
-        vertex_normals[i:i + _NORMAL_CHUNK] = density_gradient(model, pts, cal_lidar_color)["normal"].cpu().numpy()
+        vertex_normals[i:i + _NORMAL_CHUNK] = density_gradient(model, pts, cal_lidar_color, time=t)["normal"].cpu().numpy()
     write_ply(save_path, vertices, triangles, vertex_normals)
     return vertices, triangles, vertex_normals
 

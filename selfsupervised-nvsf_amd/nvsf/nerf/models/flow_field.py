@@ -62,11 +62,12 @@ class FlowField(nn.Module):
         self.mlp = nn.Sequential(*layers)
         torch.nn.init.normal_(self.mlp[-1].weight.data, 0, 0.001)
 
-    def forward(self, xt, t_host=None, fp16=None):
+    def forward(self, xt, t_host=None, fp16=None, keep=None):
         """xt: [N, 4] = (x, y, z, t) in [0, 1]; all rows share one t (the reference reads xt[0, 3], :125).
         Without autograd the grid lookup and the Lagrange reduction are one fused kernel (csrc/hashgrid4d.hip);
         `t_host` (the value of t, if the caller already has it on the host) avoids a device->host read.
-        `fp16`: True / False selects the MLP's arithmetic for this call, None follows the regime (module docstring)."""
+        `fp16`: True / False selects the MLP's arithmetic for this call, None follows the regime (module docstring).
+        `keep`: a dict that receives "reduced", the MLP's input [N, 2 L] (normals.density_gradient differentiates the MLP there)."""
         t = xt[0, 3]
         fused_mlp = self.mlp_mode(fp16) == "fused" and self._fused_mlp_ok()
         training = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
@@ -86,6 +87,8 @@ class FlowField(nn.Module):
                 t_host = float(t) if t_host is None else t_host
                 h.append(self._grid_lagrange(xt.float().contiguous(), t_host))
         red = h[0] if len(h) == 1 else torch.cat(h, dim=-1)
+        if keep is not None:
+            keep["reduced"] = red
         if training:
             if fused_mlp:
                 # the mixed-precision training run: the Linear layers on the fused MFMA forward / backward kernels (what

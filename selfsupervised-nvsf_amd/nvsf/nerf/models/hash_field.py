@@ -251,6 +251,51 @@ class HashGrid4D(nn.Module):
                   int(offset_col), M, h_tables, h_scales, h_res, h_off, h_time, 1 if slot.same else 0, 1 if fp16_regime else 0, _hip.ptr(out))
         return out
 
+    def dynamic_grad_x(self, x, t, t_host, grad_out, grad_scale=1.0, offset=None, offset_col=0, out=None, accumulate=False):
+        """Coordinate gradient of forward_dynamic (nvsf_hashgrid4d_dynamic_grad_x): grad_scale * sum over the 24 features
+        of grad_out[:, j] * d feature_j / d p at p = x[:, :3] (+ offset[:, offset_col:offset_col+3]) -> fp32 [M, 3], written to `out`
+        (fp32 [M, >= 3], unit column stride, rows of a wider buffer allowed) or added to it with `accumulate`.  grad_out: fp32 [M, 24],
+        unit column stride; a column slice of a wider matrix is read in place.  One derivative serves both forward regimes.  'concat'
+        reduction only: grad_out is the gradient of the three pairs' features side by side."""
+        from nvsf import _hip
+        import ctypes
+        self._check_fused_shape()
+        if self.reduction != "concat":
+            raise NotImplementedError("dynamic_grad_x: the gradient of the pair features side by side ('concat' reduction)")
+        for name, v in (("x", x), ("grad_out", grad_out), ("offset", offset), ("out", out)):
+            if v is not None and not (torch.is_tensor(v) and v.is_cuda):
+                raise _hip.NvsfHipError(f"dynamic_grad_x needs `{name}` on a HIP device (got a CPU tensor); there is no CPU fallback")
+        slot = time_slot(t, _host_time(t) if t_host is None else t_host, self.hash_dynamic[0].time_resolution)
+        h_time = _hip.host_f32([slot.b_lo, slot.b_hi] + slot.lag)
+        h_tables = (ctypes.c_void_p * 6)(*[tb.data_ptr() for tb in self._slice_tables(slot)])
+        _, h_scales, h_res, h_off = self.pair_level_tables()
+
+        def rows(v, n_cols, what, writable=False):
+            """fp32 rows with unit column stride that do not overlap: read / written where they are (columns of a wider buffer keep its
+            row stride); an input of another kind is copied, a destination of another kind is refused."""
+            if v.dim() != 2 or v.shape[1] < n_cols:
+                raise ValueError(f"dynamic_grad_x: {what} must be [M, >= {n_cols}] (got {tuple(v.shape)})")
+            in_place = v.dtype == torch.float32 and v.stride(1) == 1 and v.stride(0) >= v.shape[1]
+            if writable and not in_place:
+                raise ValueError(f"dynamic_grad_x: `{what}` must be fp32 [M, >= {n_cols}] with unit column stride")
+            return v if in_place else v.float().contiguous()
+        x = rows(x, 3, "x")
+        M = x.shape[0]
+        g = rows(grad_out, 24, "grad_out")
+        off = None if offset is None else rows(offset, int(offset_col) + 3, "offset")
+        if g.shape[0] != M or (off is not None and off.shape[0] != M):
+            raise ValueError("dynamic_grad_x: x, grad_out and offset must have the same number of rows")
+        if out is None:
+            if accumulate:
+                raise ValueError("dynamic_grad_x: accumulate needs `out`")
+            out = torch.empty(M, 3, dtype=torch.float32, device=x.device)
+        elif rows(out, 3, "out", writable=True).shape[0] != M:
+            raise ValueError("dynamic_grad_x: `out` must have one row per row of x")
+        _hip.call("nvsf_hashgrid4d_dynamic_grad_x", _hip.ptr_rows(x), x.stride(0), None if off is None else _hip.ptr_rows(off),
+                  0 if off is None else off.stride(0), int(offset_col), M, h_tables, h_scales, h_res, h_off, h_time, 1 if slot.same else 0,
+                  _hip.ptr_rows(g), g.stride(0), float(grad_scale), _hip.ptr_rows(out), out.stride(0), 1 if accumulate else 0)
+        return out
+
     def training_fused3(self, x, t, t_host, flow, frame_idx, num_frames):
         """With autograd recording: (hash_d, hash_1, hash_2) of one density query from one forward launch + the fused
         table-gradient kernel (HashDyn3Fn), or None when the fused training path does not apply."""

@@ -143,14 +143,17 @@ class NeRFNetwork(NeRFRenderer):
             hash_2, plane_2 = neighbour(1)
         return plane_s, plane_d, plane_1, plane_2, hash_s, hash_d, hash_1, hash_2
 
-    def _dynamic_features_fused(self, x, t, t_host, frame_idx, hash_enc, planes_enc, fp16=None):
+    def _dynamic_features_fused(self, x, t, t_host, frame_idx, hash_enc, planes_enc, fp16=None, keep=None):
         """The no-autograd form of _dynamic_features: same values, fewer launches and temporaries -- the neighbour hash
         evaluations read `x + flow` inside the kernel instead of from an [M, 3] temporary, the neighbour time columns are
         written once.  (A single K-planes launch for all three positions that keeps the base evaluation's texel quads in
         registers was measured and rejected: 0.90 ms against 3 x 0.21 ms -- the quads cost the occupancy that hides the
-        gather latency, and the neighbours' re-gathers hit L1 anyway.)"""
+        gather latency, and the neighbours' re-gathers hit L1 anyway.)
+        `keep`: a dict that receives what normals.density_gradient differentiates through: "xt", "flow" and the flow MLP's input "reduced"."""
         xt = torch.cat([x, t.float().expand(x.shape[0], 1)], dim=-1)
-        flow = self.flow_net(xt, t_host, fp16=fp16)
+        flow = self.flow_net(xt, t_host, fp16=fp16, keep=keep)
+        if keep is not None:
+            keep["xt"], keep["flow"] = xt, flow
         hash_s = hash_enc.forward_static(x, level_major=True)  # [8, M, 4] where available: _density_tail_fused reads either layout
         nb = neighbour_frames(frame_idx, self.num_frames)
         # ONE launch for the three space-time evaluations: a neighbour re-uses the base gathers wherever its cell coincides

@@ -1,6 +1,8 @@
-"""Timing of the hash grid's coordinate gradient and of the four-launch density gradient.
+"""Timing of the hash grid's coordinate gradient and of the four-launch density gradient, and -- with --dynamic --
+of the space-time model's (section 9m).
 
     python tools/bench_normals.py [--reps 20] [--label NAME] [--out profiles/normals_bench.json]
+    python tools/bench_normals.py --dynamic [--reps 20] [--label NAME] [--out profiles/normals_dynamic_bench.json]
 
 Legs, in milliseconds between device events on the current stream, median and min .. max of the repeats after warm-up, at 4096 x 768
 ray-ordered samples (LiDAR rays of the synthetic scene, the config-2 batch), interleaved rep by rep so that a busy neighbour hits all:
@@ -13,6 +15,16 @@ ray-ordered samples (LiDAR rays of the synthetic scene, the config-2 batch), int
 Per leg `bytes_per_sample` is what the launch must move if every table read hits a cache (positions, gradient or feature rows, result)
 and `fraction_of_hbm_peak` that figure over the median at 8 TB/s: the gathers themselves are cache traffic, so the share says how far
 from a streaming kernel the leg is, not how well it uses HBM.  `--label` names the tree; with --out the result is merged into that file.
+--dynamic: the config-5 space-time model (bench.py's dynamic leg: time_resolution 8, 93.6 M parameters; random hash tables, the flow field
+as initialised) at the same samples, frame time 0.5, the flow MLP in the fp16 regime:
+  hash4d_fwd / hash4d_grad_x    nvsf_hashgrid4d_dynamic_fwd (mode 0) next to nvsf_hashgrid4d_dynamic_grad_x on the same inputs, the gradient
+                        read in place as columns 96..119 of a 120-column matrix (what density_gradient passes): the two make
+                        the same gathers;
+  density / density_gradient / density_gradient_no_flow_jacobian    NeRFNetwork.density under no_grad next to density_gradient with and
+                        without the J_f^T term;
+  lagrange_expansion / flow_grid_jtp    the [M, 2 L] -> [M, 8 L] expansion of the flow grid's gradient alone and the whole product
+                        (expansion + hashgrid_grad_x at D = 3, F = 8); `expansion_share_of_density_gradient` is the first over
+                        density_gradient's median.
 """
 import argparse
 import json
@@ -104,14 +116,58 @@ def density_legs(model, xyz, reps):
     return res
 
 
+def dynamic_result(dev, reps):
+    from nvsf.nerf.models.hash_field import lagrange_weights_host, time_slot
+    from nvsf.nerf.models.network_dynamic import NeRFNetwork
+    model = NeRFNetwork(time_resolution=8, num_frames=S.NUM_FRAMES, bound=S.BOUND, min_near=S.MIN_NEAR, min_near_lidar=S.MIN_NEAR,
+                        lidar_max_depth=S.LIDAR_MAX_DEPTH)
+    with torch.no_grad():
+        for p in model.hash_encoder_lidar.parameters():
+            p.normal_(0.0, 0.1)
+    model = model.to(dev).eval()
+    x01, xyz = sample_positions(model, dev)
+    M = x01.shape[0]
+    t_host = 0.5
+    t = torch.tensor([[t_host]], dtype=torch.float32, device=dev)
+    enc = model.hash_encoder_lidar
+    slot = time_slot(t, t_host, enc.hash_dynamic[0].time_resolution)
+    g24 = torch.randn(M, 120, device=dev)[:, 96:120]  # as the chain hands it over: columns of the density MLP's input gradient, rows 480 B apart
+    gx = torch.empty(M, 3, device=dev)
+    flow_net = model.flow_net
+    L = flow_net.grid_enc.spec.L
+    g_red = torch.randn(M, 2 * L, device=dev)
+    w4 = lagrange_weights_host(t_host, 4, True)
+    xt = torch.cat([x01, t.expand(M, 1)], -1).contiguous()
+    with torch.no_grad():
+        kernel = interleaved({"hash4d_fwd": lambda: enc._forward_dynamic_fused(x01, t, slot, None, 0),
+                              "hash4d_grad_x": lambda: enc.dynamic_grad_x(x01, t, t_host, g24, out=gx)}, reps)
+        # forward: 12 position + 96 features; grad_x: 12 + 96 gradient (of rows of 480: every line of them is touched) + 12; the gathers (2 slices x 4 corners x 8 bytes per item) are cache traffic
+        kernel = with_bytes(kernel, {"hash4d_fwd": 12 + 96, "hash4d_grad_x": 12 + 96 + 12}, M)
+        kernel["gather_bytes_per_sample"] = 24 * (1 if slot.same else 2) * 4 * 8
+        kernel["same_slice"] = bool(slot.same)
+        kernel["grad_x_over_fwd"] = kernel["hash4d_grad_x"]["median"] / kernel["hash4d_fwd"]["median"]
+        chain = interleaved({"density": lambda: model.density(xyz, t, True, fp16=True),
+                             "density_gradient": lambda: normals.density_gradient(model, xyz, True, time=t, fp16=True),
+                             "density_gradient_no_flow_jacobian": lambda: normals.density_gradient(model, xyz, True, time=t, fp16=True, flow_jacobian=False),
+                             "lagrange_expansion": lambda: normals.expand_lagrange_gradient(g_red, w4),
+                             "flow_grid_jtp": lambda: normals.flow_grid_jtp(flow_net, xt, t_host, g_red)}, reps)
+    chain["gradient_over_density"] = chain["density_gradient"]["median"] / chain["density"]["median"]
+    chain["expansion_share_of_density_gradient"] = chain["lagrange_expansion"]["median"] / chain["density_gradient"]["median"]
+    return {"unit": "ms (device events)", "shape": [N, T], "reps": reps, "device": torch.cuda.get_device_name(0), "build_digest": _hip.build_digest(),
+            "frame_time": t_host, "parameters_M": sum(p.numel() for p in model.parameters()) / 1e6, "hash4d": kernel, "chain": chain}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--label", default="branch")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dynamic", action="store_true", help="the space-time model's legs (DESIGN.md 9m) instead of the static field's")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if args.dynamic:
+        return emit(args, dynamic_result(dev, args.reps))
     model = NeRFNetworkStatic(bound=S.BOUND, min_near=S.MIN_NEAR, min_near_lidar=S.MIN_NEAR, lidar_max_depth=S.LIDAR_MAX_DEPTH)
     with torch.no_grad():
         model.hash_encoder_lidar.params.normal_(0.0, 0.1)
@@ -121,6 +177,10 @@ def main():
     res = {"unit": "ms (device events)", "shape": [N, T], "reps": args.reps, "device": torch.cuda.get_device_name(0), "build_digest": _hip.build_digest(),
            "config2_L16_F2": grid_legs(model.hash_encoder_lidar.spec, x01, dev, args.reps), "L8_F4": grid_legs(l8f4, x01, dev, args.reps),
            "density": density_legs(model, xyz, args.reps)}
+    emit(args, res)
+
+
+def emit(args, res):
     print(json.dumps({args.label: res}))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -40,8 +40,8 @@ gets two more rows) and --lidar-columns columns, other fields of view; the camer
 exported ray-drop plane is the U-Net's.
 --mesh-normals (with --export-mesh) writes the unit normals -grad sigma / |grad sigma| of the density field with the mesh's vertices;
 --normal-maps DIR writes, for each evaluation frame, normal_lidar_XXXX.png and normal_XXXX.png: the composited normals sum_i w_i n_i of
-the LiDAR and the camera rays as (n + 1) / 2 in RGB (nvsf/nerf/normals.py).  Both need the static model: the space-time model's 4-D
-encoders and flow warp have no coordinate gradient.
+the LiDAR and the camera rays as (n + 1) / 2 in RGB (nvsf/nerf/normals.py).  Both work for either model: with --dynamic the gradient is
+taken at each frame's time, through the space-time encoders and the flow warp.
 """
 import argparse
 import os
@@ -103,9 +103,9 @@ def main():
                     "(marching cubes on the device, at the time of the first evaluation frame; nvsf/nerf/mesh.py)")
     ap.add_argument("--mesh-res", type=int, nargs=3, default=[256, 256, 256], metavar=("NX", "NY", "NZ"))
     ap.add_argument("--mesh-threshold", type=float, default=10.0, help="density at the surface (inside: sigma >= threshold)")
-    ap.add_argument("--mesh-normals", action="store_true", help="write vertex normals (-grad sigma / |grad sigma|) with --export-mesh; static model only")
+    ap.add_argument("--mesh-normals", action="store_true", help="write vertex normals (-grad sigma / |grad sigma|) with --export-mesh (with --dynamic: at the mesh's frame time)")
     ap.add_argument("--normal-maps", default=None, metavar="DIR", help="after training, write normal_lidar_XXXX.png / normal_XXXX.png of every "
-                    "evaluation frame: the rendered normals as (n + 1) / 2 (nvsf/nerf/normals.py); static model only")
+                    "evaluation frame: the rendered normals as (n + 1) / 2 (nvsf/nerf/normals.py; with --dynamic: at each frame's time)")
     ap.add_argument("--eval-table", action="store_true", help="after training, print the report lines of the reference's evaluation table "
                     "(device-side meters, nvsf/nerf/meters.py)")
     ap.add_argument("--rgbd-loss", action="store_true", help="camera depth supervision from the LiDAR-projected depth map (FrameSet(camera_depth=True), "
@@ -143,9 +143,6 @@ def main():
         ap.error("--flow-loss supervises the flow head of the space-time model: add --dynamic")
     if args.mesh_normals and not args.export_mesh:
         ap.error("--mesh-normals adds normals to the exported mesh: add --export-mesh PATH")
-    if args.dynamic and (args.mesh_normals or args.normal_maps):
-        ap.error("--mesh-normals / --normal-maps need the static model: the space-time model (--dynamic) has no coordinate gradient "
-                 "(its 4-D hash encoders and flow warp are not differentiated with respect to position)")
     from nvsf.nerf.dataset.formats import SensorChange
     sensor = SensorChange(delta_position=tuple(args.delta_position), delta_orientation=tuple(args.delta_orientation), H_lidar_new=args.lidar_channels,
                           W_lidar_new=args.lidar_columns, intrinsics_lidar_new=tuple(args.intrinsics_lidar_new),
@@ -277,7 +274,7 @@ def main():
             for lidar, stem, hw in ((True, "normal_lidar", ("H_lidar", "W_lidar")), (False, "normal", ("H", "W"))):
                 sfx = "_lidar" if lidar else ""
                 out = render_normals(model, data["rays_o" + sfx].reshape(-1, 3), data["rays_d" + sfx].reshape(-1, 3), cal_lidar_color=lidar,
-                                     num_steps=args.num_steps)
+                                     num_steps=args.num_steps, time=data["time"] if args.dynamic else None)
                 plane = ((out["normal"] + 1) / 2).reshape(int(data[hw[0]]), int(data[hw[1]]), 3)
                 write_png(os.path.join(args.normal_maps, f"{stem}_{i:04d}.png"), quantize_u8(plane).cpu().numpy())
         model.train(was_training)
