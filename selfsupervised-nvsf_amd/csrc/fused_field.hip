@@ -78,12 +78,20 @@ template <int F>
 __global__ __launch_bounds__(kBlock) void k_density_uniform(RayBatch rb, const _Float16* __restrict__ table, GridMeta meta,
                                                             const _Float16* __restrict__ w_sigma, float* __restrict__ z_vals,
                                                             float* __restrict__ sigmas, _Float16* __restrict__ geo) {
-    constexpr int kLevelsPerGroup = 8 / F;
     const int lane = lane_id(), g = lane >> 4, sl = lane & 15;
-    // sigma net: 32 -> 64 -> 16
+    // sigma net: 32 -> 64 -> 16.  Lane group g holds the column PAIRS g, g + 4, g + 8, g + 12 of the feature row (pair v = features 2 v,
+    // 2 v + 1: level v for F = 2, half v & 1 of level v >> 1 for F = 4) and W0's columns permuted alike: the MFMA operand order of
+    // k_density_uniform_v2 and of the level-sliced passes, so that every formulation sums in the same order (bit-identical sigma / geo)
     half8_t w0[kHidTiles];
 #pragma unroll
-    for (int t = 0; t < kHidTiles; ++t) w0[t] = load_w_natural(w_sigma, 32, t, 0, lane);
+    for (int t = 0; t < kHidTiles; ++t) {
+        const _Float16* row = w_sigma + (size_t)(16 * t + sl) * 32;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            w0[t][2 * i] = row[2 * (g + 4 * i)];
+            w0[t][2 * i + 1] = row[2 * (g + 4 * i) + 1];
+        }
+    }
     // output rows rotated by one: accumulator row r holds network output (r+1)%16, i.e. rows 0..14 are the
     // geometry features h1..h15 and row 15 is the density logit h0 -> every lane stores an aligned half4.
     OutLayerW wout;
@@ -101,15 +109,16 @@ __global__ __launch_bounds__(kBlock) void k_density_uniform(RayBatch rb, const _
         const float near = rb.nears[n], range = rb.fars[n] - near;
         float x[3];
         const float z = sample_point(rb, rb.rays_o + 3 * (size_t)n, rb.rays_d + 3 * (size_t)n, near, range, rb.lin[i], rb.noise + s, x);
-        // hash-grid encode: this lane's 8 features = levels g*kLevelsPerGroup .. +kLevelsPerGroup-1
+        // hash-grid encode: this lane's 8 features = the column pairs g, g + 4, g + 8, g + 12 (F = 4: a level is encoded by the two lane
+        // groups that hold its halves -- the reference form pays for that)
         half8_t xf;
 #pragma unroll
-        for (int q = 0; q < kLevelsPerGroup; ++q) {
-            const int l = g * kLevelsPerGroup + q;
+        for (int j = 0; j < 4; ++j) {
+            const int v = g + 4 * j, l = v / (F / 2), f0 = 2 * (v % (F / 2));
             float acc[F];
             encode_level<3, F>(x, table, meta.scale[l], meta.res[l], meta.offset[l], meta.offset[l + 1] - meta.offset[l], acc);
-#pragma unroll
-            for (int f = 0; f < F; ++f) xf[q * F + f] = (_Float16)acc[f];
+            xf[2 * j] = (_Float16)(f0 ? acc[F - 2] : acc[0]);  // F = 2: f0 == 0
+            xf[2 * j + 1] = (_Float16)(f0 ? acc[F - 1] : acc[1]);
         }
         // sigma MLP
         float4_t acc1[kHidTiles];
@@ -136,15 +145,16 @@ __global__ __launch_bounds__(kBlock) void k_density_uniform(RayBatch rb, const _
 
 // ------------------------------------------------------------------------------------------------
 // Density kernel, second formulation (same arithmetic, same results bit for bit in the encoding):
-//   * lane group g takes levels {g, 4+g, 8+g, ...} (interleaved) instead of a contiguous block, so that in
-//     unrolled step q all four lane groups work on levels 4q..4q+3: "all dense" / "all hashed" becomes a
-//     wave-uniform branch (levels are dense up to `first_hashed` and hashed from there on) and only one
-//     index formula is evaluated per step.  The feature order seen by the MLP changes, which is undone by
-//     permuting the columns of W0 when its fragment is fetched;
+//   * lane group g takes levels {g, 4+g, 8+g, ...} (interleaved: the operand order of k_density_uniform above), and the levels
+//     are walked in unrolled steps q in which all four lane groups work on levels 4q..4q+3: "all dense" / "all hashed" becomes
+//     a wave-uniform branch (levels are dense up to `first_hashed` and hashed from there on) and only one index formula is
+//     evaluated per step.  The feature order seen by the MLP is not the row's, which is undone by permuting the columns of W0
+//     when its fragment is fetched;
 //   * per-lane level constants are read once from an LDS copy of the level table and stay in registers;
 //   * gathers are buffer loads with 32-bit byte offsets (no 64-bit address arithmetic per corner);
 //   * the corner hashes share their y/z partial terms; the dense index wraps by a conditional subtract
-//     (index < 2*rows there) instead of an integer division.
+//     (index < 2*rows there) instead of an integer division: hashed_rows / dense_rows of hashgrid_device.h, which the sliced
+//     passes and the SHARE form call and density_encode restates for its eight rows (its comment says why).
 template <int F>
 struct LaneLevels {
     static constexpr int Q = 8 / F;
@@ -168,13 +178,30 @@ __device__ __forceinline__ uint32_t gather_raw<2>(__amdgpu_buffer_rsrc_t rsrc, u
     return __builtin_amdgcn_raw_buffer_load_b32(rsrc, byte_off, 0, 0);
 }
 // F = 4: a table entry is 8 bytes (two dwords of two fp16 features), one 8-byte gather
-typedef uint32_t entry4_t __attribute__((ext_vector_type(2)));
+typedef u32x2_t entry4_t;
 template <int F> struct EntryOf { typedef uint32_t type; };
 template <> struct EntryOf<4> { typedef entry4_t type; };
 template <>
 __device__ __forceinline__ uint32_t gather_raw<4>(__amdgpu_buffer_rsrc_t, uint32_t) = delete;
 __device__ __forceinline__ entry4_t gather_raw4(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off) {
     return __builtin_amdgcn_raw_buffer_load_b64(rsrc, byte_off, 0, 0);
+}
+
+// Trilinear blend of the eight gathered entries of a cell: the specification's corner order and fma chain (corner_weight, fma_entry)
+template <int F>
+__device__ __forceinline__ void blend_corners(const float (&frac)[3], const typename EntryOf<F>::type (&r)[8], float (&a)[F]) {
+#pragma unroll
+    for (int f = 0; f < F; ++f) a[f] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float w = corner_weight(k, frac);
+        if constexpr (F == 2) {
+            fma_entry(w, r[k], a[0], a[1]);
+        } else {
+            fma_entry(w, r[k][0], a[0], a[1]);
+            fma_entry(w, r[k][1], a[2], a[3]);
+        }
+    }
 }
 
 // Per-wave constants of the v2 kernel: level table slice, permuted W0 fragment, rotated output fragment.
@@ -248,6 +275,9 @@ __device__ __forceinline__ half8_t density_encode(const DensityCtx<F>& cx, const
     uint32_t share_sel[2] = {0u, 0u}, share_one[2] = {0u, 0u};
 #pragma unroll
     for (int q = q0; q < q0 + QG; ++q) {
+        // grid_cell<3> and, below, dense_rows<8> / hashed_rows<8> (hashgrid_device.h), restated: through either helper every kernel that
+        // calls density_encode changed (k_density_uniform_v2 -10 instructions / +3 VGPRs, k_render_uniform<*, false, *, -1> -15 ... -18 and
+        // its SGPR spills) and k_render_uniform<false, false, *, -1> failed the timing rule on a camera batch (+1.6 % / +0.5 %)
         uint32_t c[3];
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
@@ -272,22 +302,19 @@ __device__ __forceinline__ half8_t density_encode(const DensityCtx<F>& cx, const
                     const uint32_t col = (uint32_t)lane_id() & 15u;
                     const bool of_a = col < 8u;
                     const uint32_t cc[3] = {(of_a ? a[0] : b[0]) + (col & 1u), (of_a ? a[1] : b[1]) + ((col >> 1) & 1u), (of_a ? a[2] : b[2]) + ((col >> 2) & 1u)};
-                    uint32_t v = 0;
-                    if (all_dense || !all_hashed) {
-                        v = cc[0] + cc[1] * lv.res[q] + cc[2] * lv.res2[q];
-                        v = v >= lv.rows[q] ? v - lv.rows[q] : v;
-                    }
+                    uint32_t v[1] = {0u}, h[1];
+                    if (all_dense || !all_hashed) dense_rows<1>(cc, 0u, lv.res[q], lv.res2[q], lv.rows[q], v);
                     if (all_hashed || !all_dense) {
-                        const uint32_t h = (cc[0] ^ (cc[1] * 2654435761u) ^ (cc[2] * 805459861u)) & (lv.rows[q] - 1u);
-                        v = (all_hashed || (uint32_t)(4 * q + g) >= first_hashed) ? h : v;
+                        hashed_rows<1>(cc, 0u, lv.rows[q] - 1u, h);
+                        v[0] = (all_hashed || (uint32_t)(4 * q + g) >= first_hashed) ? h[0] : v[0];
                     }
-                    share_one[q] = gather_raw<2>(cx.rsrc, lv.boff[q] + v * (uint32_t)(F * sizeof(_Float16)));
+                    share_one[q] = gather_raw<2>(cx.rsrc, lv.boff[q] + v[0] * (uint32_t)(F * sizeof(_Float16)));
                 }
             }
         }
         if (!SHARE || q >= 2 || !shared[q]) {
         uint32_t idx[8];
-        if (all_dense || !all_hashed) {  // dense rows: c0 + c1*res + c2*res^2, wrapped once
+        if (all_dense || !all_hashed) {  // dense_rows<8>: c0 + c1*res + c2*res^2, wrapped once
             const uint32_t b00 = c[0] + c[1] * lv.res[q] + c[2] * lv.res2[q];
             const uint32_t b10 = b00 + lv.res[q], b01 = b00 + lv.res2[q], b11 = b10 + lv.res2[q];
             const uint32_t base[4] = {b00, b10, b01, b11};
@@ -298,7 +325,7 @@ __device__ __forceinline__ half8_t density_encode(const DensityCtx<F>& cx, const
                 idx[k] = v;
             }
         }
-        if (all_hashed || !all_dense) {
+        if (all_hashed || !all_dense) {  // hashed_rows<8>, and the per-lane select of a mixed group
             const uint32_t hy0 = c[1] * 2654435761u, hy1 = hy0 + 2654435761u;
             const uint32_t hz0 = c[2] * 805459861u, hz1 = hz0 + 805459861u;
             const uint32_t yz[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
@@ -319,30 +346,10 @@ __device__ __forceinline__ half8_t density_encode(const DensityCtx<F>& cx, const
     }
     // phase 2: trilinear blend (corner order and fma chain of the specification)
     auto blend = [&](int q, const typename EntryOf<F>::type (&r)[8]) {
-        const float fx = frac[q][0], fy = frac[q][1], fz = frac[q][2];
-        const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy}, wz[2] = {1.0f - fz, fz};
-        if constexpr (F == 2) {
-            float a0 = 0.0f, a1 = 0.0f;
+        float a[F];
+        blend_corners<F>(frac[q], r, a);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const float w = (wx[k & 1] * wy[(k >> 1) & 1]) * wz[k >> 2];
-                fma_entry(w, r[k], a0, a1);
-            }
-            xf[q * F] = (_Float16)a0;
-            xf[q * F + 1] = (_Float16)a1;
-        } else {
-            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const float w = (wx[k & 1] * wy[(k >> 1) & 1]) * wz[k >> 2];
-                fma_entry(w, r[k][0], a0, a1);
-                fma_entry(w, r[k][1], a2, a3);
-            }
-            xf[q * F] = (_Float16)a0;
-            xf[q * F + 1] = (_Float16)a1;
-            xf[q * F + 2] = (_Float16)a2;
-            xf[q * F + 3] = (_Float16)a3;
-        }
+        for (int f = 0; f < F; ++f) xf[q * F + f] = (_Float16)a[f];
     };
     if constexpr (SHARE) {
         // behind the gathers of the fine groups, which stay in flight: a row's 16 dwords -> the 8 of every lane's cell.  Each coarse group
@@ -577,58 +584,24 @@ __global__ __launch_bounds__(kBlock) void k_density_uniform_v2(RayBatch rb, cons
 // streaming kernel turns 32 features -> sigma MLP -> sigma / geo; its lane group g reads planes 2g and 2g+1, i.e.
 // levels {g, g+4, g+8, g+12} -- the assignment of the fused kernel, so the MFMA sums in the same order (bit-identical).  If the dispatcher placed blocks differently the result is the same,
 // only slower.
-template <int F>
-struct SliceLevel {
-    float scale;
-    uint32_t res, res2, boff, rows;
-    bool hashed;
-};
-
+// The cell of x at a level of a slice, its eight gathers issued (slice_level, grid_cell, dense_rows / hashed_rows of hashgrid_device.h)
 template <int F>
 __device__ __forceinline__ void slice_issue(const SliceLevel<F>& lv, __amdgpu_buffer_rsrc_t rsrc, const float (&x)[3], float (&frac)[3],
                                             uint32_t (&raw)[8]) {
-    uint32_t c[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float pos = fmaf(lv.scale, x[d], 0.5f);
-        const float fl = floorf(pos);
-        frac[d] = pos - fl;
-        c[d] = (uint32_t)(int32_t)fl;
-    }
-    uint32_t idx[8];
-    if (!lv.hashed) {  // block-uniform
-        const uint32_t b00 = c[0] + c[1] * lv.res + c[2] * lv.res2;
-        const uint32_t b10 = b00 + lv.res, b01 = b00 + lv.res2, b11 = b10 + lv.res2;
-        const uint32_t base[4] = {b00, b10, b01, b11};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            uint32_t v = base[k >> 1] + (uint32_t)(k & 1);
-            idx[k] = v >= lv.rows ? v - lv.rows : v;
-        }
-    } else {
-        const uint32_t hy0 = c[1] * 2654435761u, hy1 = hy0 + 2654435761u;
-        const uint32_t hz0 = c[2] * 805459861u, hz1 = hz0 + 805459861u;
-        const uint32_t yz[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
-        const uint32_t mask = lv.rows - 1u;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) idx[k] = ((c[0] + (uint32_t)(k & 1)) ^ yz[k >> 1]) & mask;
-    }
+    uint32_t c[3], idx[8];
+    grid_cell<3>(x, lv.scale, c, frac);
+    if (!lv.hashed) dense_rows<8>(c, 0u, lv.res, lv.res2, lv.rows, idx);  // block-uniform
+    else hashed_rows<8>(c, 0u, lv.rows - 1u, idx);
 #pragma unroll
     for (int k = 0; k < 8; ++k) raw[k] = gather_raw<F>(rsrc, lv.boff + idx[k] * (uint32_t)(F * sizeof(_Float16)));
 }
 
 __device__ __forceinline__ uint32_t slice_blend(const float (&frac)[3], const uint32_t (&raw)[8]) {
-    const float fx = frac[0], fy = frac[1], fz = frac[2];
-    const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy}, wz[2] = {1.0f - fz, fz};
-    float a0 = 0.0f, a1 = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float w = (wx[k & 1] * wy[(k >> 1) & 1]) * wz[k >> 2];
-        fma_entry(w, raw[k], a0, a1);
-    }
+    float a[2];
+    blend_corners<2>(frac, raw, a);
     h2_t o;
-    o[0] = (_Float16)a0;
-    o[1] = (_Float16)a1;
+    o[0] = (_Float16)a[0];
+    o[1] = (_Float16)a[1];
     return __builtin_bit_cast(uint32_t, o);
 }
 
@@ -640,34 +613,16 @@ __device__ __forceinline__ uint32_t slice_blend(const float (&frac)[3], const ui
 // order: bit-identical features.
 template <int F>
 __device__ __forceinline__ void slice_issue_half(const SliceLevel<F>& lv, __amdgpu_buffer_rsrc_t rsrc, const float (&x)[3], uint32_t xb,
-                                                 float (&frac)[3], uint32_t (&raw)[4]) {
-    uint32_t c[3];
+                                                 float (&frac)[3], typename EntryOf<F>::type (&raw)[4]) {
+    uint32_t c[3], idx[4];
+    grid_cell<3>(x, lv.scale, c, frac);
+    if (!lv.hashed) dense_rows<4>(c, xb, lv.res, lv.res2, lv.rows, idx);  // block-uniform
+    else hashed_rows<4>(c, xb, lv.rows - 1u, idx);
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float pos = fmaf(lv.scale, x[d], 0.5f);
-        const float fl = floorf(pos);
-        frac[d] = pos - fl;
-        c[d] = (uint32_t)(int32_t)fl;
+    for (int p = 0; p < 4; ++p) {
+        if constexpr (F == 2) raw[p] = gather_raw<2>(rsrc, lv.boff + idx[p] * (uint32_t)(F * sizeof(_Float16)));
+        else raw[p] = gather_raw4(rsrc, lv.boff + idx[p] * (uint32_t)(F * sizeof(_Float16)));
     }
-    uint32_t idx[4];
-    if (!lv.hashed) {  // block-uniform
-        const uint32_t b00 = c[0] + c[1] * lv.res + c[2] * lv.res2;
-        const uint32_t base[4] = {b00, b00 + lv.res, b00 + lv.res2, b00 + lv.res + lv.res2};
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const uint32_t v = base[p] + xb;
-            idx[p] = v >= lv.rows ? v - lv.rows : v;
-        }
-    } else {
-        const uint32_t hy0 = c[1] * 2654435761u, hy1 = hy0 + 2654435761u;
-        const uint32_t hz0 = c[2] * 805459861u, hz1 = hz0 + 805459861u;
-        const uint32_t yz[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
-        const uint32_t mask = lv.rows - 1u;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) idx[p] = ((c[0] + xb) ^ yz[p]) & mask;
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) raw[p] = gather_raw<F>(rsrc, lv.boff + idx[p] * (uint32_t)(F * sizeof(_Float16)));
 }
 
 // Which workgroups encode which units of which slice.  Workgroup b belongs to group b % 8 (workgroups are dealt to the XCDs
@@ -754,17 +709,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     const uint32_t slice = plan.slice[group][item], unit_begin = plan.begin[group][item], unit_end = plan.end[group][item];
     const uint32_t grp = slice >> 1;
     const uint32_t lvl[2] = {(slice & 1u) ? grp + 4u : grp, (slice & 1u) ? grp + 8u : grp + 12u};
-    SliceLevel<F> lv[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const uint32_t l = lvl[a];
-        lv[a].scale = meta.scale[l];
-        lv[a].res = meta.res[l];
-        lv[a].res2 = meta.res[l] * meta.res[l];
-        lv[a].boff = meta.offset[l] * (uint32_t)(F * sizeof(_Float16));
-        lv[a].rows = meta.offset[l + 1] - meta.offset[l];
-        lv[a].hashed = l >= first_hashed;
-    }
+    const SliceLevel<F> lv[2] = {slice_level<F>(meta, lvl[0], first_hashed), slice_level<F>(meta, lvl[1], first_hashed)};
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(table), 0, (int)table_bytes, 0x00020000);
     const int lane = lane_id();
     const uint32_t xb = (uint32_t)(lane & 1), half_lane = (uint32_t)(lane >> 1);
@@ -784,7 +729,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         uint32_t half_raw[2][4];
         slice_issue_half<F>(lv[0], rsrc, x, xb, frac[0], half_raw[0]);
         slice_issue_half<F>(lv[1], rsrc, x, xb, frac[1], half_raw[1]);
-        // the even lane finishes level 0 of the slice, the odd lane level 1: each sends the partner the half it does not need
+        // the even lane finishes level 0 of the slice, the odd lane level 1: each sends the partner the half it does not need.  This is
+        // exchange_halves (hashgrid_device.h) on the entries {dword of level 0, dword of level 1}, restated: going through the helper
+        // cost k_encode_sliced_pairs 4 VGPRs and 4 - 7 instructions
         uint32_t raw[8];
         float fr[3];
 #pragma unroll
@@ -801,10 +748,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         const uint32_t other = lane_swap(mine);
         if (cur.in_range && xb == 0u) {
             feat[(size_t)slice * M + cur.s] = make_uint2(mine, other);
-            if (slice == 0u) {
-                z_vals[cur.s] = z;
-                if (x01) { x01[3 * (size_t)cur.s] = x[0]; x01[3 * (size_t)cur.s + 1] = x[1]; x01[3 * (size_t)cur.s + 2] = x[2]; }
-            }
+            if (slice == 0u) store_sample_inputs(z_vals, x01, cur.s, z, x);
         }
         cur = nxt;
     }
@@ -838,13 +782,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     const uint32_t group = blockIdx.x & 7u, sb = blockIdx.x >> 3, n_sb = gridDim.x >> 3;
     for (uint32_t item = 0; item < plan.n[group]; ++item) {
     const uint32_t level = plan.slice[group][item], unit_begin = plan.begin[group][item], unit_end = plan.end[group][item];
-    SliceLevel<4> lv;
-    lv.scale = meta.scale[level];
-    lv.res = meta.res[level];
-    lv.res2 = meta.res[level] * meta.res[level];
-    lv.boff = meta.offset[level] * 8u;
-    lv.rows = meta.offset[level + 1] - meta.offset[level];
-    lv.hashed = level >= first_hashed;
+    const SliceLevel<4> lv = slice_level<4>(meta, level, first_hashed);
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(table), 0, (int)table_bytes, 0x00020000);
     const int lane = lane_id();
     const uint32_t xb = (uint32_t)(lane & 1), half_lane = (uint32_t)(lane >> 1);
@@ -862,51 +800,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         float x[3];
         const float z = sample_point(rb, cur.o, cur.d, cur.near, cur.far - cur.near, cur.lin, &cur.noise, x);
         float frac[3];
-        uint32_t c[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float pos = fmaf(lv.scale, x[d], 0.5f);
-            const float fl = floorf(pos);
-            frac[d] = pos - fl;
-            c[d] = (uint32_t)(int32_t)fl;
-        }
-        uint32_t idx[4];
-        if (!lv.hashed) {  // block-uniform
-            const uint32_t b00 = c[0] + c[1] * lv.res + c[2] * lv.res2;
-            const uint32_t base[4] = {b00, b00 + lv.res, b00 + lv.res2, b00 + lv.res + lv.res2};
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const uint32_t v = base[p] + xb;
-                idx[p] = v >= lv.rows ? v - lv.rows : v;
-            }
-        } else {
-            const uint32_t hy0 = c[1] * 2654435761u, hy1 = hy0 + 2654435761u;
-            const uint32_t hz0 = c[2] * 805459861u, hz1 = hz0 + 805459861u;
-            const uint32_t yz[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
-            const uint32_t mask = lv.rows - 1u;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) idx[p] = ((c[0] + xb) ^ yz[p]) & mask;
-        }
-        typedef uint32_t u2v __attribute__((ext_vector_type(2)));
-        u2v raw[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) raw[p] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, lv.boff + (idx[p] << 3), 0, 0);
+        entry4_t raw[4];
+        slice_issue_half<4>(lv, rsrc, x, xb, frac, raw);
         // this lane's feature pair of all eight corners: its own entries' dword, and the partner's (the corners with the other x-bit)
         uint32_t mine[8];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const uint32_t own = xb ? raw[p][1] : raw[p][0], send = xb ? raw[p][0] : raw[p][1];
-            const uint32_t recv = lane_swap(send);
-            mine[2 * p] = xb ? recv : own;
-            mine[2 * p + 1] = xb ? own : recv;
-        }
+        exchange_halves<4>(raw, xb, mine);
         const uint32_t packed = slice_blend(frac, mine);
         if (cur.in_range) {
             feat_dw[pair_plane_dword(pair, M, cur.s)] = packed;
-            if (level == 0u && xb == 0u) {
-                z_vals[cur.s] = z;
-                if (x01) { x01[3 * (size_t)cur.s] = x[0]; x01[3 * (size_t)cur.s + 1] = x[1]; x01[3 * (size_t)cur.s + 2] = x[2]; }
-            }
+            if (level == 0u && xb == 0u) store_sample_inputs(z_vals, x01, cur.s, z, x);
         }
         cur = nxt;
     }

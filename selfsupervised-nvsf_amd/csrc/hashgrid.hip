@@ -58,9 +58,9 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_fwd(const float* __restrict
 // Here workgroup b works on level b % 8 for a share of ALL samples -- workgroups are dealt to the XCDs round-robin, so an XCD
 // keeps gathering from the same 4 MB level, which stays in its L2.  Two lanes per sample (lane = 2 * sample + x-bit), as in the
 // sliced pass of fused_field.hip: a gather instruction fetches both x-neighbours of 32 samples (the same 16-B pair for even
-// cells).  The even lane blends features 0, 1, the odd lane features 2, 3, each over all eight corners in the specification's
-// order (the partner's half of every entry arrives by a quad swap): the same fma chain as encode_level<3, 4>, bit-identical
-// features.  If the dispatcher placed workgroups differently the result is the same, only slower.
+// cells; hashed_rows<4>).  The even lane blends features 0, 1, the odd lane features 2, 3, each over all eight corners in the
+// specification's order (the partner's half of every entry arrives by a quad swap, exchange_halves; weights: corner_weight): the
+// same fma chain as encode_level<3, 4>, bit-identical features.  If the dispatcher placed workgroups differently the result is the same, only slower.
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_hashgrid_fwd_levels8(
     const float* __restrict__ x, uint32_t M, uint32_t x_stride, const _Float16* __restrict__ table, uint32_t table_bytes, GridMeta meta,
     _Float16* __restrict__ out, uint32_t out_stride, uint32_t planes = 0) {
@@ -86,30 +86,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         float xs[3] = {nxt[0], nxt[1], nxt[2]};
         fetch(unit + wave_count < n_units ? unit + wave_count : unit, nxt);
         float frac[3];
-        uint32_t c[3];
+        uint32_t c[3], idx[4];
         grid_cell<3>(xs, scale, c, frac);
-        const uint32_t hy0 = c[1] * 2654435761u, hy1 = hy0 + 2654435761u;
-        const uint32_t hz0 = c[2] * 805459861u, hz1 = hz0 + 805459861u;
-        const uint32_t yz[4] = {hy0 ^ hz0, hy1 ^ hz0, hy0 ^ hz1, hy1 ^ hz1};
-        typedef uint32_t u2v __attribute__((ext_vector_type(2)));
-        u2v raw[4];
+        hashed_rows<4>(c, xb, mask, idx);
+        u32x2_t raw[4];
 #pragma unroll
-        for (int p = 0; p < 4; ++p) raw[p] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, boff + ((((c[0] + xb) ^ yz[p]) & mask) << 3), 0, 0);
+        for (int p = 0; p < 4; ++p) raw[p] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, boff + (idx[p] << 3), 0, 0);
         // this lane's feature pair of all eight corners: its own corners' dword, and the partner's (the corners with the other x-bit)
         uint32_t mine[8];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const uint32_t own = xb ? raw[p][1] : raw[p][0], send = xb ? raw[p][0] : raw[p][1];
-            const uint32_t recv = lane_swap(send);
-            mine[2 * p] = xb ? recv : own;
-            mine[2 * p + 1] = xb ? own : recv;
-        }
-        const float wx[2] = {1.0f - frac[0], frac[0]}, wy[2] = {1.0f - frac[1], frac[1]}, wz[2] = {1.0f - frac[2], frac[2]};
+        exchange_halves<4>(raw, xb, mine);
         float a0 = 0.0f, a1 = 0.0f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const float w = (wx[k & 1] * wy[(k >> 1) & 1]) * wz[k >> 2];
-            const h2_t v = __builtin_bit_cast(h2_t, mine[k]);
+            const float w = corner_weight(k, frac);
+            const h2_t v = __builtin_bit_cast(h2_t, mine[k]);  // fmaf on converted halves: fma_entry (fused_field.hip) gives the same bits with another instruction mix
             a0 = fmaf(w, (float)v[0], a0);
             a1 = fmaf(w, (float)v[1], a1);
         }
@@ -516,8 +506,9 @@ __global__ __launch_bounds__(kBlock) void k_hashgrid_bwd_bin(const float* __rest
                     }
                 emit = tail && run_any;
             }
-            // rows of the eight vertices (grid_row<3> of hashgrid_device.h with the level's kind decided once: per-axis terms of the
-            // cell and of its upper neighbour, combined by xor + mask on a hashed level, by sums + one wrap on a dense one)
+            // rows of the eight vertices: what dense_rows<8> / hashed_rows<8> of hashgrid_device.h compute, kept apart because this
+            // kernel factors the terms per AXIS (tx, ty, tz live across the corners below) and carries grid_row's general modulo for
+            // positions outside the unit cube -- sharing would make the helpers branch on their caller
             uint32_t tx[2], ty[2], tz[2];
             tx[0] = cell[0];
             tx[1] = cell[0] + 1u;

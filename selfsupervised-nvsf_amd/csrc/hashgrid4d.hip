@@ -58,6 +58,29 @@ __device__ __forceinline__ float blend_reduce(const float (&f_lo)[kF], const flo
     return acc;
 }
 
+// Prologue of the sample-per-lane kernels: p = x[m, 0:3] (+ offset[m, off_col : off_col + 3] where there is one).  A lane past the end
+// takes the last sample: it computes a valid position and is dropped at the store.  Returns the clamped sample index.
+__device__ __forceinline__ uint32_t load_position(const float* __restrict__ x, uint32_t x_stride, const float* __restrict__ offset, uint32_t off_stride,
+                                              uint32_t off_col, uint32_t m, uint32_t M, float (&p)[3]) {
+    const uint32_t mm = m < M ? m : M - 1;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        p[d] = x[(size_t)mm * x_stride + d];
+        if (offset) p[d] = p[d] + offset[(size_t)mm * off_stride + off_col + d];
+    }
+    return mm;
+}
+
+// Epilogue: the workgroup's rows of a staging tile (`pitch` floats apart, filled before a barrier) leave as whole rows of n_cols values of T
+template <typename T>
+__device__ __forceinline__ void store_staged_rows(const float* stage, uint32_t pitch, uint32_t n_cols, uint32_t M, T* __restrict__ out) {
+    const uint32_t n_rows = min((uint32_t)kSamplesPerBlock, M - blockIdx.x * kSamplesPerBlock);
+    for (uint32_t c = threadIdx.x; c < n_rows * n_cols; c += kBlock) {
+        const uint32_t row = c / n_cols, col = c - row * n_cols;
+        out[(size_t)(blockIdx.x * kSamplesPerBlock + row) * n_cols + col] = (T)stage[row * pitch + col];
+    }
+}
+
 // x' = x[:, 0:3] (+ offset[:, off_col : off_col+3]); out [M, 24]: fp32 (MODE 0) or fp16 (MODE 1)
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_hash_dynamic(const float* __restrict__ x, uint32_t x_stride, const float* __restrict__ offset,
@@ -65,14 +88,8 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic(const float* __restrict
                                                          void* __restrict__ out) {
     __shared__ float stage[kSamplesPerBlock][3 * kPlaneLevels + 1];
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform by construction: level tables, pointers and loop control in SGPRs
-    const uint32_t m = blockIdx.x * kSamplesPerBlock + lane;
-    const uint32_t mm = m < M ? m : M - 1;
     float p[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        p[d] = x[(size_t)mm * x_stride + d];
-        if (offset) p[d] = p[d] + offset[(size_t)mm * off_stride + off_col + d];
-    }
+    load_position(x, x_stride, offset, off_stride, off_col, blockIdx.x * kSamplesPerBlock + lane, M, p);
     for (int item = wave; item < 3 * kPlaneLevels; item += 4) {
         const int pl = item / kPlaneLevels, l = item - pl * kPlaneLevels;
         const float xy[2] = {p[pl == 2 ? 1 : 0], p[pl == 0 ? 1 : 2]};
@@ -93,14 +110,8 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic(const float* __restrict
         stage[lane][item] = blend_reduce<MODE>(f_lo, f_hi, ps.ts);
     }
     __syncthreads();
-    const uint32_t n_rows = min((uint32_t)kSamplesPerBlock, M - blockIdx.x * kSamplesPerBlock);
-    constexpr int kOut = 3 * kPlaneLevels;
-    for (uint32_t c = threadIdx.x; c < n_rows * kOut; c += kBlock) {
-        const uint32_t row = c / kOut, col = c - row * kOut;
-        const size_t o = (size_t)(blockIdx.x * kSamplesPerBlock + row) * kOut + col;
-        if (MODE == 0) reinterpret_cast<float*>(out)[o] = stage[row][col];
-        else reinterpret_cast<_Float16*>(out)[o] = (_Float16)stage[row][col];
-    }
+    if (MODE == 0) store_staged_rows(&stage[0][0], 3 * kPlaneLevels + 1, 3 * kPlaneLevels, M, reinterpret_cast<float*>(out));
+    else store_staged_rows(&stage[0][0], 3 * kPlaneLevels + 1, 3 * kPlaneLevels, M, reinterpret_cast<_Float16*>(out));
 }
 
 // Coordinate gradient of the encoder above: dL/dp of the piecewise-bilinear function k_hash_dynamic evaluates, on its own
@@ -121,13 +132,8 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic_grad_x(const float* __r
     __shared__ float part[kBlock / 64][3][64];  // [wave][axis][lane]
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform by construction: level tables, pointers and loop control in SGPRs
     const uint32_t m = blockIdx.x * kSamplesPerBlock + lane;
-    const uint32_t mm = m < M ? m : M - 1;  // clamp: out-of-range lanes compute a valid sample and are dropped at the store
     float p[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        p[d] = x[(size_t)mm * x_stride + d];
-        if (offset) p[d] = p[d] + offset[(size_t)mm * off_stride + off_col + d];
-    }
+    const uint32_t mm = load_position(x, x_stride, offset, off_stride, off_col, m, M, p);  // also the row of grad_out
     float sum[3] = {0.0f, 0.0f, 0.0f};
     for (int item = wave; item < 3 * kPlaneLevels; item += 4) {
         const int pl = item / kPlaneLevels, l = item - pl * kPlaneLevels;
@@ -193,7 +199,7 @@ struct PlaneSet3 {
     int share[3];      // ev[e] reads the same slice tables as ev[0] (same k1, k2): its cells may re-use ev[0]'s gathers
 };
 
-typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
+typedef u32x2_t u2_t;
 
 // Two lanes per sample (lane = 2 * sample + x-bit, 32 samples per pass, two passes per item): a lane gathers the two corners with
 // its x-bit of a slice, so a gather instruction fetches BOTH x-neighbours of 32 samples -- the same 16-byte pair for even cells,
@@ -214,13 +220,7 @@ __device__ __forceinline__ void gather_pair(const float (&xy)[2], uint32_t xb, c
 // features (2 xb, 2 xb + 1) of the cell, blended over the four corners in encode_level's order, rounded to fp16 as the slice encoders return them
 __device__ __forceinline__ void blend_pair(const u2_t (&raw)[2], uint32_t xb, const float (&frac)[2], float (&f)[2]) {
     uint32_t mine[4];  // this lane's feature pair of corner c = x + 2 y
-#pragma unroll
-    for (int y = 0; y < 2; ++y) {
-        const uint32_t own = xb ? raw[y][1] : raw[y][0], send = xb ? raw[y][0] : raw[y][1];
-        const uint32_t recv = lane_swap(send);
-        mine[2 * y] = xb ? recv : own;
-        mine[2 * y + 1] = xb ? own : recv;
-    }
+    exchange_halves<2>(raw, xb, mine);
     f[0] = f[1] = 0.0f;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -258,6 +258,7 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic3(const float* __restric
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const uint32_t m = blockIdx.x * kSamplesPerBlock + 32u * h + (uint32_t)(lane >> 1);
+        // load_position, restated: one read of x serves the three evaluations (calling it per evaluation moved 2 VGPRs / 2 SGPRs in this kernel)
         const uint32_t mm = m < M ? m : M - 1;
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
@@ -319,6 +320,8 @@ __global__ __launch_bounds__(kBlock) void k_hash_dynamic3(const float* __restric
         }
     }
     __syncthreads();
+    // store_staged_rows, restated: the three tiles leave in ONE loop (a call per tile added 26 instructions and failed the timing rule in
+    // tools/bench_dynamic.py)
     const uint32_t n_rows = min((uint32_t)kSamplesPerBlock, M - blockIdx.x * kSamplesPerBlock);
     constexpr int kOut = 3 * kPlaneLevels;
     for (uint32_t c = threadIdx.x; c < n_rows * kOut; c += kBlock) {
@@ -337,10 +340,9 @@ __global__ __launch_bounds__(kBlock) void k_hash3d_lagrange(const float* __restr
                                                             float w2, float w3, float* __restrict__ out) {
     extern __shared__ float stage_dyn[];  // [64][2L + 1]
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform by construction: level tables, pointers and loop control in SGPRs
-    const uint32_t m = blockIdx.x * kSamplesPerBlock + lane;
-    const uint32_t mm = m < M ? m : M - 1;
     const uint32_t pitch = 2 * L + 1;
-    const float p[3] = {x[(size_t)mm * x_stride], x[(size_t)mm * x_stride + 1], x[(size_t)mm * x_stride + 2]};
+    float p[3];
+    load_position(x, x_stride, nullptr, 0u, 0u, blockIdx.x * kSamplesPerBlock + lane, M, p);
     const float w[4] = {w0, w1, w2, w3};
     for (uint32_t l = wave; l < L; l += 4) {
         float f[8];
@@ -355,11 +357,7 @@ __global__ __launch_bounds__(kBlock) void k_hash3d_lagrange(const float* __restr
         }
     }
     __syncthreads();
-    const uint32_t n_rows = min((uint32_t)kSamplesPerBlock, M - blockIdx.x * kSamplesPerBlock);
-    for (uint32_t c = threadIdx.x; c < n_rows * 2 * L; c += kBlock) {
-        const uint32_t row = c / (2 * L), col = c - row * 2 * L;
-        out[(size_t)(blockIdx.x * kSamplesPerBlock + row) * 2 * L + col] = stage_dyn[row * pitch + col];
-    }
+    store_staged_rows(stage_dyn, pitch, 2 * L, M, out);
 }
 
 // Table gradients of the fused space-time encoder, regime 0 (fp32 blend / reduction: the current frame, the only call that

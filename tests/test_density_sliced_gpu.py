@@ -24,6 +24,95 @@ def _batch(m, dev, lidar, N, rng):
     return o, d, nears, fars
 
 
+OVERSHOOT_T = (32, 48, 40)  # a wave-uniform ray (T % 32 == 0), whole tiles per ray (T % 16 == 0), ragged
+
+
+def _overshoot_rays(bound, N=64, seed=41):
+    """Rays that leave the box: origins within 0.2 bound of the centre; the six axis directions, the twelve in-plane diagonals, the eight
+    body diagonals, then seeded random directions; near = 0.05, far = 1.5 x the distance to the box exit.  The last third of every ray is
+    clamped onto a face, an edge or a corner of the box, where the index of a dense level wraps (cell + 1 == res).  fp32 numpy
+    (o, d, nears, fars)."""
+    rng = np.random.default_rng(seed)
+    axes = [s * np.eye(3)[k] for k in range(3) for s in (1.0, -1.0)]
+    planes = []
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        for sa in (1.0, -1.0):
+            for sb in (1.0, -1.0):
+                v = np.zeros(3)
+                v[a], v[b] = sa, sb
+                planes.append(v)
+    body = [np.array([sx, sy, sz]) for sx in (1.0, -1.0) for sy in (1.0, -1.0) for sz in (1.0, -1.0)]
+    d = np.array(axes + planes + body + list(rng.standard_normal((N - 26, 3))))
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    o = rng.uniform(-0.2 * bound, 0.2 * bound, (N, 3)).astype(np.float32)
+    o64, d64 = o.astype(np.float64), d.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(d64 > 0, (bound - o64) / d64, np.where(d64 < 0, (-bound - o64) / d64, np.inf))
+    return o, d, np.full(N, 0.05, np.float32), (1.5 * t.min(1)).astype(np.float32)
+
+
+def _overshoot_x01(o, d, nears, fars, T, bound, noise=None):
+    """sample_z / sample_x01 of fused_field.hip restated in fp32 numpy, operation by operation: unit-cube positions [N, T, 3]."""
+    f = np.float32
+    lin = torch.linspace(0.0, 1.0, T).numpy()
+    rng_ = fars - nears
+    z = nears[:, None] + rng_[:, None] * lin[None]
+    if noise is not None:
+        z = z + (noise - f(0.5)) * (rng_ / f(T))[:, None]
+    p = o[:, None, :] + d[:, None, :] * z[..., None]
+    p = np.minimum(np.maximum(p, f(-bound)), f(bound))
+    x = (p + f(bound)) * (f(1.0) / (f(2.0) * f(bound)))
+    assert x.dtype == np.float32
+    return x
+
+
+def _assert_on_faces(x01):
+    """What makes the batch a test of the wrap: enough samples on a face, on edges and corners too, at both ends of the cube."""
+    on = (x01 == 0.0) | (x01 == 1.0)
+    per = on.sum(-1)
+    assert (per >= 1).mean() >= 0.25, (per >= 1).mean()
+    for k in (1, 2, 3):
+        assert (per == k).any(), k
+    assert (x01 == 0.0).any() and (x01 == 1.0).any()
+
+
+def _overshoot_batch(bound, dev, T, noise):
+    """The overshoot rays on the device, their noise (or None), and the restated positions (checked to lie on the faces) as fp32 numpy."""
+    o, d, nears, fars = _overshoot_rays(bound)
+    nz = torch.rand(o.shape[0], T, generator=torch.Generator().manual_seed(T)) if noise else None
+    x01 = _overshoot_x01(o, d, nears, fars, T, bound, nz.numpy() if noise else None)
+    _assert_on_faces(x01)
+    return tuple(_t(a, dev) for a in (o, d, nears, fars)), (nz.to(dev) if noise else None), x01
+
+
+@pytest.mark.parametrize("noise", [False, True])
+@pytest.mark.parametrize("T", OVERSHOOT_T)
+def test_face_clamped_samples_sliced_equals_fused_and_the_oracle(dev, T, noise, variants):
+    """Rays that overshoot the box put samples at x01 == 0 or 1 exactly, where a dense level takes the wrap of its index (level 0 of the
+    config-2 grid: scale 15, res 16, cell + 1 == res).  The single-launch and the level-sliced density -- the two users of the fast index
+    forms on this grid -- agree bit for bit there.  The stand-alone encoder (the specification form, encode_level / grid_row, in both its
+    variants on this grid) equals the CPU oracle at the restated positions; what ties the fast forms to the specification on the faces is
+    the L8 F4 case of test_l8f4_fused_gpu.py (generic kernel against sliced pass)."""
+    import oracle_lib as O
+    from nvsf import field_ops as ops
+    m = _model(dev, 0.1)
+    (o, d, nears, fars), nz, x01 = _overshoot_batch(float(m.bound), dev, T, noise)
+    enc = m.hash_encoder_camera
+    args = (o, d, nears, fars, T, m._aabb_host, float(m.bound), enc.table_f16(), enc.spec, m.sigma_net.weights_f16(), nz)
+    a = ops.density_uniform(*args, sliced=False)
+    b = ops.density_uniform(*args, sliced=True)
+    for x, y, name in zip(a, b, ("z_vals", "sigmas", "geo")):
+        assert torch.equal(x, y), name
+    xs = x01.reshape(-1, 3)
+    exp = O.hashgrid_fwd(xs, (0, 1, 2), enc.table_f16().cpu().numpy(), enc.spec)
+    for form in (None, "generic"):
+        if form:
+            variants.set(hashgrid_fwd=form)
+        got = ops.hashgrid_forward(_t(xs, dev), (0, 1, 2), enc.table_f16(), enc.spec)
+        variants.clear("hashgrid_fwd")
+        assert np.array_equal(got.cpu().numpy().view(np.uint16), exp.view(np.uint16)), form
+
+
 @pytest.mark.parametrize("lidar", [True, False])
 @pytest.mark.parametrize("N,T,noise", [(64, 128, False), (37, 100, True), (1, 16, False), (300, 768, True), (5, 7, False)])
 def test_sliced_equals_fused_bitwise(dev, lidar, N, T, noise):

@@ -13,7 +13,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from test_render_static_gpu import _oracle, _t
-from test_density_sliced_gpu import _batch
+from test_density_sliced_gpu import OVERSHOOT_T, _batch, _overshoot_batch
 
 SHAPES = {
     "reference-default": dict(base_resolution=512, max_resolution=32768, log2_hashmap_size=19),  # every level hashed
@@ -66,6 +66,43 @@ def test_feature_planes_equal_the_encoder_rows(dev, shape, lidar, N, T, noise):
     # the no-grad sliced density (same two passes without the TRAIN outputs)
     z2, s2, g2 = ops.density_uniform(o, d, nears, fars, T, m._aabb_host, float(m.bound), enc.table_f16(), enc.spec, net.weights_f16(), nz, sliced=True)
     assert torch.equal(z2, z) and torch.equal(s2.view(-1), sigma) and torch.equal(g2.view(-1, 16), geo16)
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("noise", [False, True])
+@pytest.mark.parametrize("T", OVERSHOOT_T)
+def test_face_clamped_samples_generic_kernel_equals_the_sliced_pass(dev, shape, T, noise):
+    """Samples clamped onto the faces, edges and corners of the box (x01 == 0 or 1 exactly: the wrap of a dense level's index): the generic
+    single-launch density kernel (encode_level, the specification form) equals the sliced F = 4 pass bit for bit."""
+    from nvsf import field_ops as ops
+    m = _model(dev, shape)
+    (o, d, nears, fars), nz, _ = _overshoot_batch(float(m.bound), dev, T, noise)
+    enc = m.hash_encoder_camera
+    args = (o, d, nears, fars, T, m._aabb_host, float(m.bound), enc.table_f16(), enc.spec, m.sigma_net.weights_f16(), nz)
+    a = ops.density_uniform(*args, sliced=False)
+    b = ops.density_uniform(*args, sliced=True)
+    for x, y, name in zip(a, b, ("z_vals", "sigmas", "geo")):
+        assert torch.equal(x, y), name
+
+
+@pytest.mark.parametrize("noise", [False, True])
+@pytest.mark.parametrize("T", OVERSHOOT_T)
+def test_face_clamped_positions_one_level_per_xcd_equals_the_generic_forward(dev, T, noise, variants):
+    """The same positions, tiled up to the batch size at which hashgrid_forward takes the one-level-per-XCD kernel (two lanes per sample,
+    x-neighbour exchange): equal to the generic kernel bit for bit."""
+    from nvsf import field_ops as ops
+    from nvsf import synthetic as S
+    spec = ops.GridSpec(3, 8, 4, 19, 512, float(np.exp2(np.log2(32768 / 512) / 7)))
+    _, _, x01 = _overshoot_batch(float(S.BOUND), dev, T, noise)
+    M = (1 << 16) + 4099
+    xs = x01.reshape(-1, 3)
+    xd = _t(np.tile(xs, (-(-M // len(xs)), 1))[:M], dev)
+    table = (torch.randn(spec.n_params, generator=torch.Generator().manual_seed(3)) * 0.5).to(torch.float16).to(dev)
+    got = ops.hashgrid_forward(xd, (0, 1, 2), table, spec)
+    variants.set(hashgrid_fwd="generic")
+    ref = ops.hashgrid_forward(xd, (0, 1, 2), table, spec)
+    variants.clear("hashgrid_fwd")
+    assert torch.equal(got.view(torch.int16), ref.view(torch.int16))
 
 
 @pytest.mark.parametrize("shape", list(SHAPES))

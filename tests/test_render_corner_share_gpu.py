@@ -20,6 +20,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from test_render_static_gpu import _model, _t
+from test_density_sliced_gpu import OVERSHOOT_T, _overshoot_batch
 
 SHAPES = [(5, 7, False), (1, 16, False), (9, 48, False), (37, 100, True), (64, 128, False)]
 SET_ORDER = "dbcaef"  # ray i of a batch comes from set SET_ORDER[i % 6]
@@ -258,6 +259,34 @@ def test_shared_corner_gathers_are_bit_identical_to_the_per_lane_form(dev, field
     variants.clear("corner_share")
     variants.clear("level_kinds")
     assert len(res["never"]) == 15
+    for form in ("gated", "always"):
+        for k, (a, b) in enumerate(zip(res[form], res["never"])):
+            assert torch.equal(a, b), (form, k)
+    assert float(res["never"][1].abs().max()) > 0.0  # the render is not empty
+
+
+@pytest.mark.parametrize("grid", ["config2", "small_hash"])
+@pytest.mark.parametrize("lidar", [True, False])
+@pytest.mark.parametrize("noise", [False, True])
+@pytest.mark.parametrize("T", OVERSHOOT_T)
+def test_shared_corner_gathers_on_the_faces_of_the_box(dev, field, variants, T, noise, lidar, grid):
+    """Rays that overshoot the box (test_density_sliced_gpu._overshoot_rays): the clamped tail of a ray is whole tiles in ONE cell on a
+    face, an edge or a corner of the box, where the dense levels' index wraps and the shared form gathers one corner per lane.  The three
+    forms agree bit for bit; config2 runs the instance with the level kinds compiled in, small_hash the run-time one with a mixed group."""
+    from nvsf import field_ops as ops
+    m, small, small_table = field
+    enc = m.hash_encoder_lidar if lidar else m.hash_encoder_camera
+    spec, table = (enc.spec, enc.table_f16()) if grid == "config2" else (small, small_table)
+    (o, d, near, far), nz, _ = _overshoot_batch(float(m.bound), dev, T, noise)
+    heads = (m.raydrop_net.weights_f16(), m.intensity_net.weights_f16()) if lidar else (m.color_net.weights_f16(), None)
+    bg = None if lidar else [1.0, 0.5, 0.25]
+    args = (o, d, near, far, T, m._aabb_host, float(m.bound), table, spec, m.sigma_net.weights_f16(), lidar, heads[0], heads[1], m._k_scale(), bg, nz)
+    res = {}
+    for form in ("never", "gated", "always"):
+        variants.set(corner_share=form)
+        res[form] = tuple(ops.render_uniform(*args, sliced=False))
+    variants.clear("corner_share")
+    assert len(res["never"]) == 5
     for form in ("gated", "always"):
         for k, (a, b) in enumerate(zip(res[form], res["never"])):
             assert torch.equal(a, b), (form, k)
