@@ -1128,6 +1128,34 @@ int nvsf_merge_rows(const void* a, const void* b, const int32_t* src, uint32_t N
 int nvsf_split_rows(const void* merged, const int32_t* src, uint32_t N, uint32_t T, uint32_t U, uint32_t row_bytes, void* a, void* b,
                     nvsf_stream_t stream);
 
+/* ---- 16. order statistics of a ray's termination distribution -------------------------------------------------------------------- */
+
+/* Contract as sections 10 to 15.  DESIGN.md section 9n has the definitions these two entries implement. */
+
+/* ref: the statistics that stand beside `depth = torch.sum(weights * z_vals, dim=-1)` ("not real depth!!"),
+ * nvsf/nerf/models/renderer_dynamic.py:218-221: the range a sensor would report instead of the expectation.  weights, z_vals [N, T]
+ * fp32 (w >= 0, z non-decreasing along a row), nears, fars [N] fp32; T >= 1, N T <= 2^31.  q_levels: Q levels, doubles in HOST memory,
+ * 1 <= Q <= 4, each in (0, 1] (a level outside, or NaN, is refused before any launch).  Per ray, with the compositor's intervals
+ *   delta_i = z_{i+1} - z_i (i < T - 1), delta_{T-1} = (far - near) / T,  C_i the inclusive prefix sums of w, W = C_{T-1},
+ * and sample i's mass spread uniformly over [z_i, z_i + delta_i]:
+ *   quantiles[n][l] = z_i + delta_i (tau - C_{i-1}) / w_i at the first i with C_i >= tau;  tau = q_l W (normalize != 0) or q_l
+ *                     (normalize == 0: where the accumulated opacity reaches q_l; 0 for a row with W < q_l, "no return")
+ *   mode[n]         = z_i of the first i that attains max w (the strongest return, at the sample position as sum w z is)
+ *   std_dev[n]      = sqrt(sum_i w_i (z_i - mu)^2 / W),  mu = sum_i w_i z_i / W
+ * A row with W = 0 gives 0 everywhere.  Each of quantiles [N][Q], mode [N], std_dev [N] and state may be NULL.  Every sum and the scan
+ * in fp64 from the fp32 inputs, one rounding on store; one wave per ray, two walks over the row (the total first: tau = q W, and the
+ * crossing test must see the total its own scan ends in, not the compositor's fp32 weights_sum).  No atomics, bit-identical between
+ * runs.  N = 0 is a no-op.  state (double [N][Q][2]) receives (i or -1 where the level gave 0, tau - C_{i-1}) for the backward:
+ *   grad_weights[n][j] = sum_l grad_quantiles[n][l] (r (q_l - [j < i]) - [j == i] delta_i (tau - C_{i-1}) / w_i^2),  r = delta_i / w_i
+ * (normalize == 0: without the q_l term), every element written, zero rows for the levels that gave 0; nothing flows to z_vals, nears
+ * or fars.  One launch each. */
+int nvsf_ray_depth_stats_fwd(const float* weights, const float* z_vals, const float* nears, const float* fars, uint32_t N, uint32_t T,
+                             const double* q_levels, uint32_t Q, int normalize, float* quantiles, float* mode, float* std_dev,
+                             double* state, nvsf_stream_t stream);
+int nvsf_ray_depth_quantile_bwd(const float* weights, const float* z_vals, const float* nears, const float* fars, uint32_t N, uint32_t T,
+                                const double* q_levels, uint32_t Q, int normalize, const double* state, const float* grad_quantiles,
+                                float* grad_weights, nvsf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

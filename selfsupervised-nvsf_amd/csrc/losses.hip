@@ -696,28 +696,6 @@ __global__ __launch_bounds__(kUrfBlock) void k_urf_bwd(const float* __restrict__
 // by one); the running totals cross the tiles in a wave-uniform pair.  A ray whose R is not finite or not > 0 (a camera ray that misses
 // the box) gives 0 and a zero gradient row.  No atomics: per-workgroup partials, one fold in block order, two runs give the same bits.
 constexpr int kDistBlock = 256, kDistRays = kDistBlock / kWave;
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ double dpp_add_f64(double v) {  // v + the DPP source lane's v; a lane without a source adds +0.0
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, kCtrl, kRowMask, 0xF, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), kCtrl, kRowMask, 0xF, false);
-    return v + __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-// inclusive fp64 add-scan over the 64 lanes, six DPP steps as wave_scan_max_u32 (common.h); every lane must be active
-__device__ __forceinline__ double wave_scan_add_f64(double v) {
-    v = dpp_add_f64<0x111, 0xF>(v);  // row_shr:1
-    v = dpp_add_f64<0x112, 0xF>(v);  // row_shr:2
-    v = dpp_add_f64<0x114, 0xF>(v);  // row_shr:4
-    v = dpp_add_f64<0x118, 0xF>(v);  // row_shr:8
-    v = dpp_add_f64<0x142, 0xA>(v);  // row_bcast:15 -> rows 1 and 3
-    v = dpp_add_f64<0x143, 0xC>(v);  // row_bcast:31 -> rows 2 and 3
-    return v;
-}
-__device__ __forceinline__ double wave_last_f64(double v) {  // lane 63's value, wave-uniform
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), 63);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
 struct DistRay { double near, R, last; bool ok; };  // last = delta_{T-1} = R / T
 __device__ __forceinline__ DistRay dist_ray(const float* __restrict__ nears, const float* __restrict__ fars, uint32_t n, uint32_t T) {
     DistRay r;

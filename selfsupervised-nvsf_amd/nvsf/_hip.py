@@ -150,6 +150,9 @@ SIGNATURES = {
     "nvsf_resample_merge": [_P, _P, _P, _P, _P, _P, _U, _U, _U, _U, _P, _P, _P, _P],
     "nvsf_merge_rows": [_P, _P, _P, _U, _U, _U, _U, _P],
     "nvsf_split_rows": [_P, _P, _U, _U, _U, _U, _P, _P],
+    # section 16: order statistics of a ray's termination distribution
+    "nvsf_ray_depth_stats_fwd": [_P, _P, _P, _P, _U, _U, _P, _U, _I, _P, _P, _P, _P],
+    "nvsf_ray_depth_quantile_bwd": [_P, _P, _P, _P, _U, _U, _P, _U, _I, _P, _P, _P],
 }
 
 _lib = None

@@ -1431,6 +1431,98 @@ class MergeRowsFn(Function):
 
 
 # ------------------------------------------------------------------------------------------------
+# order statistics of a ray's termination distribution (include/nvsf_hip.h section 16)
+# ------------------------------------------------------------------------------------------------
+DEPTH_STATS_MAX_LEVELS = 4
+DEPTH_STATS = ("quantiles", "mode", "std")
+
+
+def depth_levels(q):
+    """The quantile levels of a call as a tuple of floats: a number or up to four of them, each in (0, 1].  ValueError otherwise."""
+    levels = tuple(float(v) for v in (q if isinstance(q, (tuple, list)) else (q,)))
+    if not 1 <= len(levels) <= DEPTH_STATS_MAX_LEVELS:
+        raise ValueError(f"depth statistics take 1 to {DEPTH_STATS_MAX_LEVELS} quantile levels per call, got {len(levels)}")
+    for v in levels:
+        if not 0.0 < v <= 1.0:  # NaN fails the comparison as well
+            raise ValueError(f"a quantile level lies in (0, 1], got {v}")
+    return levels
+
+
+def _depth_rows(weights, z_vals, nears, fars):
+    w, z, near, far = (t.float().contiguous() for t in (weights, z_vals, nears.reshape(-1), fars.reshape(-1)))
+    if w.dim() != 2 or z.shape != w.shape or near.numel() != w.shape[0] or far.numel() != w.shape[0]:
+        raise ValueError(f"depth statistics: weights {tuple(weights.shape)}, z_vals {tuple(z_vals.shape)}, nears {tuple(nears.shape)} and "
+                         f"fars {tuple(fars.shape)} do not describe one [N, T] sample batch")
+    if w.shape[1] < 1:
+        raise ValueError("depth statistics need at least one sample per ray")
+    return w, z, near, far
+
+
+def ray_depth_stats(weights, z_vals, nears, fars, q=(0.5,), normalize=True, want=DEPTH_STATS):
+    """Order statistics of the rows weights / z_vals [N, T] (nears, fars [N]) in one launch, without grad (nvsf_ray_depth_stats_fwd):
+    -> dict with the entries `want` names: "quantiles" [N, Q] (the range at which the accumulated weight reaches q W, or q itself with
+    normalize=False: 0 where the row never gets there), "mode" [N] (the depth of the strongest sample) and "std" [N]."""
+    levels = depth_levels(q)
+    unknown = [k for k in want if k not in DEPTH_STATS]
+    if unknown or not want:
+        raise ValueError(f"want names some of {DEPTH_STATS}, got {tuple(want)}")
+    with torch.no_grad():
+        w, z, near, far = _depth_rows(weights, z_vals, nears, fars)
+        ptrs = (_hip.ptr(w), _hip.ptr(z), _hip.ptr(near), _hip.ptr(far))  # a CPU tensor fails here
+        N, T = w.shape
+        shapes = {"quantiles": (N, len(levels)), "mode": (N,), "std": (N,)}
+        out = {k: torch.empty(shapes[k], dtype=torch.float32, device=w.device) for k in DEPTH_STATS if k in want}
+        _hip.call("nvsf_ray_depth_stats_fwd", *ptrs, N, T, _hip.host_f64(levels), len(levels), 1 if normalize else 0,
+                  *(_hip.ptr(out.get(k)) for k in DEPTH_STATS), None)
+    return out
+
+
+class DepthQuantileFn(Function):
+    """(weights [N,T], z_vals [N,T], nears [N], fars [N], q, normalize) -> quantile ranges [N, Q] as `ray_depth_stats` gives them, with
+    the gradient to `weights` (nvsf_ray_depth_quantile_bwd; z_vals, nears and fars get none)."""
+
+    @staticmethod
+    def forward(ctx, weights, z_vals, nears, fars, q=(0.5,), normalize=True):
+        levels = depth_levels(q)
+        w, z, near, far = _depth_rows(weights, z_vals, nears, fars)
+        ptrs = (_hip.ptr(w), _hip.ptr(z), _hip.ptr(near), _hip.ptr(far))
+        N, T = w.shape
+        quantiles = torch.empty(N, len(levels), dtype=torch.float32, device=w.device)
+        state = torch.empty(N, len(levels), 2, dtype=torch.float64, device=w.device)
+        _hip.call("nvsf_ray_depth_stats_fwd", *ptrs, N, T, _hip.host_f64(levels), len(levels), 1 if normalize else 0, _hip.ptr(quantiles),
+                  None, None, _hip.ptr(state))
+        ctx.save_for_backward(w, z, near, far, state)
+        ctx.levels, ctx.normalize, ctx.shape = levels, 1 if normalize else 0, weights.shape
+        return quantiles
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_quantiles):
+        w, z, near, far, state = ctx.saved_tensors
+        N, T = w.shape
+        grad_w = torch.empty_like(w)
+        _hip.call("nvsf_ray_depth_quantile_bwd", _hip.ptr(w), _hip.ptr(z), _hip.ptr(near), _hip.ptr(far), N, T, _hip.host_f64(ctx.levels),
+                  len(ctx.levels), ctx.normalize, _hip.ptr(state), _hip.ptr(g_quantiles.float().contiguous()), _hip.ptr(grad_w))
+        return grad_w.view(ctx.shape), None, None, None, None, None
+
+
+def parse_depth_mode(depth_mode):
+    """The `depth_mode` of NeRFRenderer.run -> ("mean" | "mode" | "quantile", level | None, normalize): "mean", "median" (0.5 of the
+    ray's own total), "mode", a number q (that level of the total) or ("absolute", q) (where the accumulated opacity reaches q)."""
+    if isinstance(depth_mode, str):
+        if depth_mode in ("mean", "mode"):
+            return depth_mode, None, True
+        if depth_mode == "median":
+            return "quantile", 0.5, True
+    elif isinstance(depth_mode, (tuple, list)):
+        if len(depth_mode) == 2 and depth_mode[0] == "absolute" and isinstance(depth_mode[1], (int, float)):
+            return "quantile", depth_levels(depth_mode[1])[0], False
+    elif isinstance(depth_mode, (int, float)) and not isinstance(depth_mode, bool):
+        return "quantile", depth_levels(depth_mode)[0], True
+    raise ValueError(f'depth_mode is "mean", "median", "mode", a quantile level in (0, 1] or ("absolute", level), got {depth_mode!r}')
+
+
+# ------------------------------------------------------------------------------------------------
 # fused uniform-render kernels (static hash field)
 # ------------------------------------------------------------------------------------------------
 L2_BYTES_PER_XCD = 4 << 20

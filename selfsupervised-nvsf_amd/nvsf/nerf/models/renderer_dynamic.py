@@ -176,12 +176,14 @@ class NeRFRenderer(nn.Module):
         return d["sigma"].float() * self.density_scale, rgbs
 
     def run_cuda(self, rays_o, rays_d, time, cal_lidar_color=False, dt_gamma=0, bg_color=None, perturb=False,
-                 force_all_rays=False, max_steps=1024, T_thresh=1e-4, hierarchical=False, **kwargs):
+                 force_all_rays=False, max_steps=1024, T_thresh=1e-4, hierarchical=False, depth_mode="mean", depth_stats=False, **kwargs):
         """Occupancy-grid render: training mode packs all samples of the batch (march_rays_train ->
         field -> composite_rays_train, differentiable); evaluation mode advances the surviving rays a few steps
         at a time (march_rays -> field -> composite_rays) until all have terminated."""
         if hierarchical:
             raise ValueError("hierarchical resampling belongs to the uniform render (run); the occupancy-grid march has no coarse pass to resample")
+        if ops.parse_depth_mode(depth_mode)[0] != "mean" or depth_stats:
+            raise ValueError("depth statistics belong to the uniform render (run); the occupancy-grid march has no [N, T] rows of weights and z_vals to take them from")
         out_dim = self.out_lidar_color_dim if cal_lidar_color else self.out_color_dim
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
@@ -302,12 +304,22 @@ class NeRFRenderer(nn.Module):
         return z_vals, weights, weights_sum, depth, image
 
     def run(self, rays_o, rays_d, time, cal_lidar_color=False, num_steps=768, upsample_steps=128, bg_color=None,
-            perturb=False, hierarchical=False, **kwargs):
+            perturb=False, hierarchical=False, depth_mode="mean", depth_stats=False, **kwargs):
         """rays_o, rays_d: [B, N, 3] (B == 1).  Returns the reference's dictionary: depth / image /
         weights_sum (with a `_lidar` suffix for LiDAR rays) plus `weights` and `z_vals` [N, T].
         `hierarchical=True` (with upsample_steps = U > 0): U more samples per ray are drawn from the coarse weights (sample_pdf) and
         merged into the row; `weights` and `z_vals` are then [N, T + U].  The fused one-launch renders are bypassed.  By default
-        `upsample_steps` is ignored, as in the reference (its call site of sample_pdf was cut out)."""
+        `upsample_steps` is ignored, as in the reference (its call site of sample_pdf was cut out).
+        `depth_mode` chooses the statistic returned under `depth`: "mean" (the default: sum w z, nothing more is
+        launched), "median", a quantile level q in (0, 1], ("absolute", q) or "mode" (the strongest return), taken from the rows
+        `weights` / `z_vals` of whichever form rendered them (ops.ray_depth_stats, one launch).  With gradients recorded a quantile
+        stays differentiable through ops.DepthQuantileFn and ops.CompositeWeightsFn: the one-node training render
+        (render_from_rays_train), whose `weights` carry no graph, is bypassed for the fused density forward + compositor; "mode" is
+        piecewise constant and refused.  `depth_stats=True` adds depth_median, depth_mode and depth_std (without grad)."""
+        stat, level, normalize = ops.parse_depth_mode(depth_mode)
+        if stat == "mode" and torch.is_grad_enabled():
+            raise ValueError('depth_mode="mode" is piecewise constant in the weights and has no gradient: render it under torch.no_grad(), '
+                             'or supervise a quantile ("median", a level) instead')
         if hierarchical:
             ops.check_resample_sizes(num_steps, upsample_steps)
         self.out_dim = self.out_lidar_color_dim if cal_lidar_color else self.out_color_dim
@@ -339,7 +351,7 @@ class NeRFRenderer(nn.Module):
             rendered = self._render_hierarchical(rays_o, rays_d, nears, fars, T, U, aabb, noise, u, time, cal_lidar_color, bg, **kwargs)
         elif not record:  # three fused kernels, nothing recorded
             rendered = fused(rays_o, rays_d, nears, fars, T, aabb, noise, cal_lidar_color, bg, time=time, **kwargs)
-        elif whole is not None and (rendered := whole(rays_o, rays_d, nears, fars, T, noise, cal_lidar_color, bg, **kwargs)) is not None:
+        elif whole is not None and stat != "quantile" and (rendered := whole(rays_o, rays_d, nears, fars, T, noise, cal_lidar_color, bg, **kwargs)) is not None:
             pass  # training forward of a field that renders a ray batch as ONE autograd node (network_static: ops.RenderRaysFn)
         elif density_rays is not None and (density_outputs := density_rays(rays_o, rays_d, nears, fars, T, noise, cal_lidar_color, **kwargs)) is not None:
             # training forward of a field that samples, encodes and evaluates its density MLP in one launch (network_static):
@@ -365,11 +377,24 @@ class NeRFRenderer(nn.Module):
         if per_ray_bg is not None:
             image = image + (1 - weights_sum).unsqueeze(-1) * per_ray_bg
 
+        suffix = "_lidar" if cal_lidar_color else ""
+        extras = {}
+        if depth_stats:  # median of the ray's own total, strongest return, spread: one launch
+            stats = ops.ray_depth_stats(weights, z_vals, nears, fars, (0.5,), True)
+            extras = {"depth_median" + suffix: stats["quantiles"][:, 0].view(*prefix), "depth_mode" + suffix: stats["mode"].view(*prefix),
+                      "depth_std" + suffix: stats["std"].view(*prefix)}
+        if stat == "mode":
+            depth = stats["mode"] if depth_stats else ops.ray_depth_stats(weights, z_vals, nears, fars, want=("mode",))["mode"]
+        elif stat == "quantile" and weights.requires_grad:
+            depth = ops.DepthQuantileFn.apply(weights, z_vals, nears, fars, (level,), normalize)[:, 0]
+        elif stat == "quantile" and depth_stats and (level, normalize) == (0.5, True):
+            depth = stats["quantiles"][:, 0]
+        elif stat == "quantile":
+            depth = ops.ray_depth_stats(weights, z_vals, nears, fars, (level,), normalize, ("quantiles",))["quantiles"][:, 0]
         image = image.view(*prefix, self.out_dim)
         depth = depth.view(*prefix)
-        suffix = "_lidar" if cal_lidar_color else ""
         return {"depth" + suffix: depth, "image" + suffix: image, "weights_sum" + suffix: weights_sum, "weights": weights,
-                "z_vals": z_vals}
+                "z_vals": z_vals, **extras}
 
     def render(self, rays_o, rays_d, time, cal_lidar_color=False, staged=False, max_ray_batch=4096, **kwargs):
         """`staged`: evaluate in chunks of max_ray_batch rays and keep only depth / image (:286-316)."""

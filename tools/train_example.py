@@ -2,7 +2,7 @@
 
     python tools/train_example.py --root /path/to/kitti360_nvsf --sequence 1908 [--dynamic] [--epochs 6] [--plain]
                                   [--export-mesh out.ply --mesh-res 256 256 256 --mesh-threshold 10] [--dynamic --flow-loss]
-                                  [--eval-table] [--rgbd-loss] [--annotations boxes.json [--offset X Y Z]]
+                                  [--eval-table] [--rgbd-loss] [--depth-mode {mean,median,mode}] [--annotations boxes.json [--offset X Y Z]]
                                   [--refine [--refine-iterations N]]
                                   [--test-export DIR [--delta-position X Y Z] [--delta-orientation R P Y] [--lidar-channels V] [--lidar-columns N]
                                    [--intrinsics-lidar-new UP FOV] [--intrinsics-hoz-lidar-new UP FOV] [--delta-pos-camera X Y Z]
@@ -42,6 +42,9 @@ exported ray-drop plane is the U-Net's.
 --normal-maps DIR writes, for each evaluation frame, normal_lidar_XXXX.png and normal_XXXX.png: the composited normals sum_i w_i n_i of
 the LiDAR and the camera rays as (n + 1) / 2 in RGB (nvsf/nerf/normals.py).  Both work for either model: with --dynamic the gradient is
 taken at each frame's time, through the space-time encoders and the flow warp.
+--depth-mode median | mode: the evaluation (its range rows, chamfer distance and F-score) and the --test-export clouds
+take a ray's range from the median of its termination distribution, resp. from its strongest return, instead of the mean sum w z that
+floats between two surfaces at an object's edge (run(depth_mode=...): one HIP launch per ray batch on the rows the render returns).
 """
 import argparse
 import os
@@ -108,6 +111,8 @@ def main():
                     "evaluation frame: the rendered normals as (n + 1) / 2 (nvsf/nerf/normals.py; with --dynamic: at each frame's time)")
     ap.add_argument("--eval-table", action="store_true", help="after training, print the report lines of the reference's evaluation table "
                     "(device-side meters, nvsf/nerf/meters.py)")
+    ap.add_argument("--depth-mode", default="mean", choices=["mean", "median", "mode"], help="the range --eval-table and --test-export report per ray: "
+                    "the mean sum w z, the median of the termination distribution or the strongest return (run(depth_mode=...))")
     ap.add_argument("--rgbd-loss", action="store_true", help="camera depth supervision from the LiDAR-projected depth map (FrameSet(camera_depth=True), "
                     "RenderTrainStep(use_rgbd_loss=True)); adds the camera depth RMSE to --eval-table")
     for option, default in (("depth", "l1"), ("raydrop", "mse"), ("intensity", "mse"), ("rgb", "mse")):
@@ -196,7 +201,11 @@ def main():
                               depth_loss=args.depth_loss, raydrop_loss=args.raydrop_loss, intensity_loss=args.intensity_loss,
                               rgb_loss=args.rgb_loss, upsample_steps=args.upsample_steps, distortion_loss=args.distortion_loss,
                               alpha_dist=args.alpha_dist)
-    resample_kw = {"hierarchical": True, "upsample_steps": args.upsample_steps} if args.upsample_steps > 0 else {}
+    render_kw = {"hierarchical": True, "upsample_steps": args.upsample_steps} if args.upsample_steps > 0 else {}
+    if args.depth_mode != "mean":  # evaluation and export only: the training step supervises the mean
+        if getattr(model, "cuda_ray", False):
+            ap.error("--depth-mode reads the [N, T] rows of the uniform render, which the occupancy-grid path does not return")
+        render_kw["depth_mode"] = args.depth_mode
     if not args.plain:
         trainer.attach_error_maps(data)
     it = 0
@@ -237,7 +246,7 @@ def main():
                   f"BCE {np.mean(losses[:5]):.4f} -> {np.mean(losses[-5:]):.4f}", flush=True)
     for label, r in ((("", None),) + ((("refined ", refiner),) if refiner is not None else ())):
         res = evaluate_frames(model, whole, args.num_steps, indices=range(min(len(whole), 4)), ema=trainer.ema,
-                              meters="table" if args.eval_table else None, refiner=r, **resample_kw)
+                              meters="table" if args.eval_table else None, refiner=r, **render_kw)
         if rank == 0:
             print(f"{label}evaluation over {res['frames']} frames: loss {res['loss']:.4f}, PSNR {res['psnr']:.2f} dB, range RMSE "
                   f"{res['depth_rmse_m']:.2f} m, chamfer distance {res['chamfer_distance']:.3f}, F-score {res['f_score']:.3f}")
@@ -250,7 +259,7 @@ def main():
         novel = FrameSet(root, args.sequence, "train", scale, device=dev, training=False, offset=args.offset, sensor=sensor)
         t0 = time.perf_counter()
         counts = export_frames(model, novel, args.test_export, f"{args.sequence}_ep{args.epochs:04d}", args.num_steps, refiner=refiner, ema=trainer.ema,
-                               write=(rank == 0), **resample_kw)
+                               write=(rank == 0), **render_kw)
         torch.cuda.synchronize()
         if rank == 0:
             what = "changed sensors" if novel.sensor is not None else "the recording's sensors"
